@@ -18,8 +18,13 @@ Workloads (BASELINE.json):
          N = 8); the counter-based generator lets every rank synthesise exactly its own shard on its own GPU.
 --reads-per-gpu overrides both with a fixed per-GPU batch (weak scaling).
 
-Prints ONE JSON line (rank 0).  `roofline` is measured live with HIP events on the kernel's stream;
-`cpu_baseline` times the restated Zoe CPU path (oracle/, AVX2 w256) on the host cores over a bounded sample.
+Prints ONE JSON line (rank 0).  `roofline` is measured live with HIP events on the kernel's stream.
+A plain run sets up, warms up, times the steps and prints the line.  --full adds, after the timed region: the oracle check
+of a slice of the batch (--verify), the headline workload with every cell computed and compared (`full_pass_every_cell`), the
+other configs (`secondary`), `cpu_baseline` (the restated Zoe CPU path, oracle/, AVX2 w256, on the host cores over a bounded
+sample) and, for N > 1, the gather-order checks.
+--dump-outputs DIR writes what the last timed step returned (rank 0's batch; a fixed sample of 2^21 reads of a larger one) as
+DIR/score.npy, status.npy, tier.npy (float64 / float32) and read_index.npy (the reads sampled, float64).
 """
 from __future__ import annotations
 
@@ -61,6 +66,7 @@ HBM_PEAK_GBS = 8000.0               # MI355X_MICROARCH.md: 8 TB/s spec
 # (profiles/r01_valu_issue_rates_ubench.txt: half the v_fma_f32/v_add_u32 rate), i.e. 16 lanes/clk/SIMD.
 VALU_LANE_OPS_PEAK = 256 * 4 * 16 * 2.4e9  # 256 CU x 4 SIMD x 16 lanes/clk x 2.4 GHz (32-bit lane-ops/s)
 PACKED_OPS_PER_CELL_PAIR = 7.5      # zsw_score.hip score_kernel_v2 inner loop: 7.5 packed VALU per two cells
+DUMP_SAMPLE = 1 << 21               # reads dumped by --dump-outputs: 2^21 x (8 + 4 + 4 + 8) B = 48 MiB at most
 
 
 def parse():
@@ -68,6 +74,9 @@ def parse():
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=5)
     ap.add_argument("--warmup", type=int, default=1)
+    ap.add_argument("--full", action="store_true", help="after the timed region, also run the checks and other measurements "
+                    "(oracle check, full pass, secondary configs, CPU baseline; each can be left out with its --no-* option)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None, help="write the last timed step's results as DIR/<name>.npy")
     ap.add_argument("--reads-per-gpu", type=int, default=0, help="fixed batch per GPU (weak scaling); default: 10 M at N = 1, "
                     "500 M / N at N > 1 (BASELINE.json configs[1] / configs[3])")
     ap.add_argument("--total-reads", type=int, default=TOTAL_READS_MULTI_GPU, help="total reads of the N > 1 workload")
@@ -79,7 +88,29 @@ def parse():
     ap.add_argument("--backend", default="nccl", help="torch.distributed backend (nccl = RCCL; gloo only to rehearse the "
                     "multi-rank path on a one-GPU box together with --single-device)")
     ap.add_argument("--single-device", action="store_true", help="rehearsal: every rank uses cuda:0")
-    return ap.parse_args()
+    args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be at least 1 and --warmup at least 0")
+    return args
+
+
+def dump_outputs(result, n_reads: int, out_dir: str):
+    """The score batch of the last timed step as .npy files: every read of a batch of up to DUMP_SAMPLE reads, else the same
+    seeded sample of DUMP_SAMPLE read indices in every run (the inputs are seeded too, so two builds compare read by read)."""
+    import torch
+
+    if n_reads <= DUMP_SAMPLE:
+        idx = np.arange(n_reads, dtype=np.int64)
+    else:
+        idx = np.sort(np.random.default_rng(20240917).choice(n_reads, DUMP_SAMPLE, replace=False))
+    sel = torch.from_numpy(idx).to(result.score.device)
+    os.makedirs(out_dir, exist_ok=True)
+    arrays = {"score": result.score[sel].cpu().numpy().view(np.uint32).astype(np.float64),
+              "status": result.status[sel].cpu().numpy().astype(np.float32),
+              "tier": result.tier[sel].cpu().numpy().astype(np.float32),
+              "read_index": idx.astype(np.float64)}
+    for name, a in arrays.items():
+        np.save(os.path.join(out_dir, name + ".npy"), a)
 
 
 def host_cores() -> int:
@@ -585,6 +616,7 @@ def main():
         t = torch.tensor([dt], dtype=torch.float64, device="cpu" if gather_on_host else dev)
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         dt = float(t.item())
+    if world > 1 and args.full:
         # the gathered array must be every rank's shard in read order: own shard, and the first read of every other shard
         # against a single-process score of the same (regenerated) read
         mine = gathered.score_of_rank(rank)
@@ -594,10 +626,12 @@ def main():
                                                              device=local_rank).sw_score_from_i8(reference)
             got = torch.stack([gathered.score_of_rank(r)[0] for r in range(world)]).cpu()
             assert torch.equal(got, probe.score.cpu()), "gathered shards do not start with the right reads"
+    if rank == 0 and args.dump_outputs:
+        dump_outputs(last, n_local, args.dump_outputs)
 
     # parity spot check outside the timed region (rank 0): a slice of the batch against the oracle
     verified = None
-    if rank == 0 and args.verify > 0:
+    if rank == 0 and args.full and args.verify > 0:
         from oracle import oracle
 
         oracle.build()
@@ -652,7 +686,7 @@ def main():
                 "data_dependence": "`value` holds for reads within a few per cent of the reference (the synthetic set: 1 % substitutions, 2 % unrelated reads = "
                                    "the handed-back fraction). The proof rests on k-mers the read shares with the reference: beyond about one substitution per "
                                    "ten bases a read is scored over all its cells. Data-independent floor: full_pass_every_cell.reads_per_s; the curve between: "
-                                   "secondary.score_divergence_sweep",
+                                   "secondary.score_divergence_sweep (both with --full)",
             },
             "roofline": {
                 "bound": "hbm",
@@ -681,13 +715,13 @@ def main():
                                     "instruction_count_source": file_tag(PMC_PROFILE), "instruction_count_measured_in_this_run": False,
                                     "library_fatbin_sha256": LIB_HASH, "stale": constants_state("band")["stale"],
                                     "valu_peak_source": "one wave64 packed/perm/max3 instruction per 4 cycles per SIMD: " + file_tag(VALU_PEAK_SOURCE)}
-        if world == 1 and not args.no_full_pass:
+        if world == 1 and args.full and not args.no_full_pass:
             out["full_pass_every_cell"] = full_pass_headline(zoe_amd, ctx, profiles, reference, last, n_local, args.steps)
-        if not args.no_secondary and world == 1:
+        if world == 1 and args.full and not args.no_secondary:
             del reads, profiles, last
             torch.cuda.empty_cache()
             out["secondary"] = secondary_configs(zoe_amd, synth, ctx, matrix)
-        if not args.no_cpu_baseline and world == 1:
+        if world == 1 and args.full and not args.no_cpu_baseline:
             out["cpu_baseline"] = cpu_baseline(reference, args.cpu_seconds)
         print(json.dumps(out), flush=True)
     if world > 1:

@@ -1,10 +1,10 @@
 """Condenses the rocprofv3 outputs of a round-end run into the files committed under profiles/ (see profiles/README.md).
 
 usage: python tools/refresh_profiles.py r02      # reads gpurun_out/<tag>_prof_head, gpurun_out/<tag>_prof_final, gpurun_out/<tag>_bench_default.json
-On the GPU box the inputs come from:
+On the GPU box the inputs come from (<out>: the directory named above):
   rocprofv3 --kernel-trace --stats --output-format csv -d gpurun_out/<tag>_prof_head -o run -- python3 bench.py --steps 5 --warmup 1 --no-cpu-baseline --verify 0 --no-secondary --no-pruned > gpurun_out/<tag>_prof_head_bench.json
-  rocprofv3 --kernel-trace --stats --output-format csv -d gpurun_out/<tag>_prof_final -o run -- python3 bench.py --steps 3 --warmup 1 --no-cpu-baseline > gpurun_out/<tag>_prof_final_bench.json
-  python3 bench.py > gpurun_out/<tag>_bench_default.json
+  rocprofv3 --kernel-trace --stats --output-format csv -d <out>/<tag>_prof_final -o run -- python3 bench.py --full --steps 3 --warmup 1 --no-cpu-baseline > <out>/<tag>_prof_final_bench.json
+  python3 bench.py --full > <out>/<tag>_bench_default.json
 """
 import csv, glob, json, shutil, sys
 
@@ -38,7 +38,7 @@ with open(f"profiles/{tag}_final_kernel_stats.csv", "w") as f:
     w = csv.writer(f); w.writerow(["Name", "Calls", "TotalDurationNs", "AverageNs", "Percentage", "MinNs", "MaxNs"])
     for r in rows[:40]:
         w.writerow([r["Name"][:110], r["Calls"], r["TotalDurationNs"], r["AverageNs"], r["Percentage"], r["MinNs"], r["MaxNs"]])
-out = [f"# {tag} final: rocprofv3 --kernel-trace --stats on `python3 bench.py --steps 3 --warmup 1 --no-cpu-baseline` (one MI355X).",
+out = [f"# {tag} final: rocprofv3 --kernel-trace --stats on `python3 bench.py --full --steps 3 --warmup 1 --no-cpu-baseline` (one MI355X).",
        "# Headline launches = score_kernel_v2<4,38,0> (10 M reads x 150 bp vs 2 kb: warm-up + 3 timed; its average also contains the",
        f"# 2,048-read parity-check launch and the 1 M-read launches of the `secondary` section, see {tag}_final_headline_summary.txt for the clean figure);",
        "# the other kernels belong to `secondary` (10 M reads exact align; 1 M reads each: 3-pass align, ranges, filter, mixed lengths on side streams)",
