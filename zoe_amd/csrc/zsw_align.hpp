@@ -38,31 +38,31 @@ hipError_t group_reads(const BatchDev& b, const uint8_t* d_status, const uint8_t
 // Third pass of sw_align_3pass (zsw_threepass.hip). list == null: classify pass over all reads (resolves the no-gaps
 // shortcut, queues the rest in dp_list); otherwise the DP pass over `list`.
 struct ThreePassArgs {
-    BatchDev b;
-    const uint8_t* ref;
-    uint32_t ref_len;
-    const ScoringDev* sc;
-    const uint32_t* score;  // ranges results, indexed by read id
-    const uint32_t *rs, *re, *qs, *qe;
-    const uint8_t* status;
-    const uint32_t* list;  // read ids that need the DP (class 2), or null: classify pass over all reads
-    const uint32_t* list_count;
-    uint32_t* dp_list;     // classify pass: reads that need the DP
-    uint32_t* dp_count;
-    uint32_t* dp_need_max;  // classify pass: largest slot need (bytes) among them
-    uint8_t* scratch;       // DP pass: slots * slot_bytes
-    uint32_t slots;
-    uint64_t slot_bytes;
-    uint32_t* cig;          // ciglet pool (traceback order), maxc per read
-    uint32_t maxc;
-    uint64_t pool_base;
-    int by_item;
-    uint64_t* cig_start;
-    uint32_t* cig_raw;
-    zsw_alignment* aln;
-    uint32_t* fb_list;      // ciglet overflow / slot too small -> rerun with larger resources
-    uint32_t* fb_count;
-    int invert;
+    BatchDev b{};
+    const uint8_t* ref = nullptr;
+    uint32_t ref_len = 0;
+    const ScoringDev* sc = nullptr;
+    const uint32_t* score = nullptr;  // ranges results, indexed by read id
+    const uint32_t *rs = nullptr, *re = nullptr, *qs = nullptr, *qe = nullptr;
+    const uint8_t* status = nullptr;
+    const uint32_t* list = nullptr;  // read ids that need the DP (class 2), or null: classify pass over all reads
+    const uint32_t* list_count = nullptr;
+    uint32_t* dp_list = nullptr;     // classify pass: reads that need the DP
+    uint32_t* dp_count = nullptr;
+    uint32_t* dp_need_max = nullptr;  // classify pass: largest slot need (bytes) among them
+    uint8_t* scratch = nullptr;       // DP pass: slots * slot_bytes
+    uint32_t slots = 0;
+    uint64_t slot_bytes = 0;
+    uint32_t* cig = nullptr;          // ciglet pool (traceback order), maxc per read
+    uint32_t maxc = 0;
+    uint64_t pool_base = 0;
+    int by_item = 0;
+    uint64_t* cig_start = nullptr;
+    uint32_t* cig_raw = nullptr;
+    zsw_alignment* aln = nullptr;
+    uint32_t* fb_list = nullptr;      // ciglet overflow / slot too small -> rerun with larger resources
+    uint32_t* fb_count = nullptr;
+    int invert = 0;
     // The shared-profile role (profile_set.rs:552-560: one profile, built from `pseq`, reused for every sequence of the batch):
     // non-null = the roles of three_pass.rs:21-26 are `reference` = read i, `query` = pseq for every i (ranges from
     // zsw_score_ranges_shared_batch: rs/re index the read, qs/qe the profile sequence); `ref` / `ref_len` are then unused.

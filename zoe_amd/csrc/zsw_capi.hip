@@ -74,15 +74,10 @@ hipError_t copy_packed_chunk(zsw_context* ctx, const zsw_batch* reads, size_t fi
     if (e != hipSuccess || cnt == 0) return e;
     Unpack4 u;
     for (int k = 0; k < 16; ++k) u.byte_of[k] = 0;
-    bool seen[16] = {false};
     for (int b = 255; b >= 0; --b) {  // the smallest byte of each index (upper case before lower case)
         const int idx = ctx->h_sc.index_map[b];
-        if (idx < 16) {
-            u.byte_of[idx] = (uint8_t)b;
-            seen[idx] = true;
-        }
+        if (idx < 16) u.byte_of[idx] = (uint8_t)b;
     }
-    (void)seen;
     const uint64_t total = (uint64_t)cnt * stride;
     hipLaunchKernelGGL(unpack4_kernel, dim3((unsigned)std::min<uint64_t>((total + 255) / 256, 65536)), dim3(256), 0, stream,
                        ctx->s_packed.as<uint8_t>() + first * stride, (uint64_t)cnt, L, u, ctx->s_bases.as<uint8_t>() + first * L);
@@ -200,14 +195,8 @@ zsw_error stage(zsw_context* ctx, const zsw_batch* reads, hipStream_t stream, bo
         // of workspace per read, the banded kernel's strip-boundary buffers and the worklist of the reads it hands back. If the device cannot spare them the full pass runs.
         SeedIndex& index = shared ? ctx->seed_shared : ctx->seed;
         if (!index.valid) {
-            if (shared) {
-                ScoringDev t = ctx->h_sc;
-                for (int r = 0; r < t.S; ++r)
-                    for (int q = 0; q < t.S; ++q) t.w[r * t.S + q] = ctx->h_sc.w[q * t.S + r];
-                ZSW_HIP(ctx, seed_index_update(&index, t, ctx->h_pseq.data(), seq_len));
-            } else {
-                ZSW_HIP(ctx, seed_index_update(&index, ctx->h_sc, ctx->h_ref.data(), seq_len));
-            }
+            const uint8_t* seq = shared ? ctx->h_pseq.data() : ctx->h_ref.data();
+            ZSW_HIP(ctx, seed_index_update(&index, shared ? ctx->h_sc_t : ctx->h_sc, seq, seq_len));
         }
         if (index.usable) {
             // ragged batches: a region per length class (the banded pass's buffers are sized per region, by the reads in it)
@@ -260,6 +249,26 @@ zsw_error stage(zsw_context* ctx, const zsw_batch* reads, hipStream_t stream, bo
         ctx->scratch_len = need;
         ctx->exact_slots = slots;
     }
+    return ZSW_OK;
+}
+
+zsw_error stage_reads(zsw_context* ctx, const zsw_batch* reads, hipStream_t stream, Staged* st) {
+    uint32_t dummy_score = 0;
+    uint8_t dummy_status = 0;
+    const zsw_error ze = stage(ctx, reads, stream, false, false, &dummy_score, &dummy_status, nullptr, nullptr, nullptr, st);
+    st->d_score = nullptr;  // (a device batch's result arrays were the dummies, which go out of scope here)
+    st->d_status = nullptr;
+    return ze;
+}
+
+zsw_error stage_align(zsw_context* ctx, const zsw_batch* reads, zsw_alignment* out_aln, uint8_t* out_status, uint32_t* out_inc, uint8_t* out_op,
+                      uint64_t ciglet_cap, uint64_t* out_n_ciglets, hipStream_t stream, Staged* st) {
+    if (!ctx) return ZSW_ERR_INVALID_ARGUMENT;
+    if (!reads || !out_aln || !out_status || !out_n_ciglets || (ciglet_cap && (!out_inc || !out_op)))
+        return fail(ctx, ZSW_ERR_INVALID_ARGUMENT, "null argument");
+    const zsw_error ze = stage_reads(ctx, reads, stream, st);
+    if (ze != ZSW_OK) return ze;
+    *out_n_ciglets = 0;
     return ZSW_OK;
 }
 
@@ -430,12 +439,21 @@ static bool seeded_reverse_possible(zsw_context* ctx, const Staged& st) {
            st.max_len <= SEED_MAX_LEN;
 }
 
-// run_align's first pass in certificate mode: the forward and the reversed seeded pass only (no exact reverse pass, no combine)
+zsw_error reversed_seed_index(zsw_context* ctx, SeedIndex* index, DevBuf* d_rev, const std::vector<uint8_t>& seq, const ScoringDev& sc, hipStream_t stream) {
+    if (index->valid) return ZSW_OK;
+    std::vector<uint8_t> rev(seq.rbegin(), seq.rend());
+    ZSW_HIP(ctx, d_rev->ensure(rev.size() + 16));
+    ZSW_HIP(ctx, hipMemcpyAsync(d_rev->p, rev.data(), rev.size(), hipMemcpyHostToDevice, stream));
+    ZSW_HIP(ctx, hipStreamSynchronize(stream));  // `rev` goes out of scope
+    ZSW_HIP(ctx, seed_index_update(index, sc, rev.data(), rev.size()));
+    return ZSW_OK;
+}
+
+// run_align's first pass in certificate mode: the forward and the reversed seeded pass only (no exact reverse pass, no combine);
+// the RangesDev then holds the forward pass's score, status, tier, re and qe and the reversed pass's rs and qs
 struct RangesCert {
     uint32_t* safe_row;  // in: where the forward pass leaves the late-start rows of sw_simd_align's second pass
     uint8_t* settled;    // in: n bytes; out: 1 = both maxima of the read sit in one cell each, rs / qs hold its starts
-    ScoreOut fwd;        // out: the forward pass's arrays (score, status, tier, ref_end, query_end)
-    uint32_t *rs, *qs;   // out
 };
 
 // forward score+ends (MODE 2), reverse pass on the prefixes, combine; everything stays on the device
@@ -477,7 +495,6 @@ zsw_error ranges_device(zsw_context* ctx, const Staged& st, const ResultRule& ru
     ScoreOut ro;
     ro.score = ws[RW_RSCORE].as<uint32_t>();
     ro.status = ws[RW_RSTATUS].as<uint8_t>();
-    ro.tier = nullptr;
     ro.ref_end = ws[RW_RRS].as<uint32_t>();
     ro.query_end = ws[RW_RQS].as<uint32_t>();
     ro.fb_list = ctx->d_fb_list.as<uint32_t>();
@@ -486,13 +503,9 @@ zsw_error ranges_device(zsw_context* ctx, const Staged& st, const ResultRule& ru
     bool run_exact = true;
     if (seeded_reverse) {
         const size_t R = ctx->ref_len;
-        if (!ctx->seed_rev.valid) {
-            std::vector<uint8_t> rev(ctx->h_ref.rbegin(), ctx->h_ref.rend());
-            ZSW_HIP(ctx, ctx->d_ref_rev.ensure(R + 16));
-            ZSW_HIP(ctx, hipMemcpyAsync(ctx->d_ref_rev.p, rev.data(), R, hipMemcpyHostToDevice, stream));
-            ZSW_HIP(ctx, hipStreamSynchronize(stream));  // `rev` goes out of scope
-            ZSW_HIP(ctx, seed_index_update(&ctx->seed_rev, ctx->h_sc, rev.data(), R));
-        }
+        zsw_error ze = reversed_seed_index(ctx, &ctx->seed_rev, &ctx->d_ref_rev, ctx->h_ref, ctx->h_sc, stream);
+        if (ze != ZSW_OK) return ze;
+        if (cert) *out = RangesDev{fo.score, ro.ref_end, fo.ref_end, ro.query_end, fo.query_end, fo.status, fo.tier};  // rs, qs: reversed pass
         if (ctx->seed_rev.usable) {
             ZSW_HIP(ctx, ws[RW_UNIQ_R].ensure((size_t)n + 4));
             ZSW_HIP(ctx, ws[RW_ULIST].ensure((size_t)n * 4 + 4));
@@ -516,12 +529,7 @@ zsw_error ranges_device(zsw_context* ctx, const Staged& st, const ResultRule& ru
             ZSW_HIP(ctx, launch_settle_reverse(st.b, n, (uint32_t)R, ws[RW_UNIQ_F].as<uint8_t>(), ws[RW_UNIQ_R].as<uint8_t>(), fo.score, fo.status, ro.score,
                                                ro.status, ro.query_end, ro.ref_end, ws[RW_ULIST].as<uint32_t>(), ws[RW_UCOUNT].as<uint32_t>(), stream,
                                                cert ? cert->settled : nullptr));
-            if (cert) {  // the caller takes it from here (the unsettled reads go to sw_simd_align's own second pass)
-                cert->fwd = fo;
-                cert->rs = ro.ref_end;
-                cert->qs = ro.query_end;
-                return ZSW_OK;
-            }
+            if (cert) return ZSW_OK;  // the caller takes it from here (the unsettled reads go to sw_simd_align's own second pass)
             uint32_t left = 0;
             ZSW_HIP(ctx, hipMemcpyAsync(&left, ws[RW_UCOUNT].p, 4, hipMemcpyDeviceToHost, stream));
             ZSW_HIP(ctx, hipStreamSynchronize(stream));
@@ -530,9 +538,6 @@ zsw_error ranges_device(zsw_context* ctx, const Staged& st, const ResultRule& ru
             run_exact = left > 0;
         } else if (cert) {
             ZSW_HIP(ctx, hipMemsetAsync(cert->settled, 0, n, stream));  // no index of the reversed reference: nothing is settled
-            cert->fwd = fo;
-            cert->rs = ro.ref_end;
-            cert->qs = ro.query_end;
             return ZSW_OK;
         }
     }
@@ -556,6 +561,18 @@ zsw_error ranges_device(zsw_context* ctx, const Staged& st, const ResultRule& ru
     return ZSW_OK;
 }
 
+zsw_error copy_ranges_out(zsw_context* ctx, const RangesDev& rd, uint32_t n, bool host, uint32_t* out_score, uint32_t* out_rs, uint32_t* out_re,
+                          uint32_t* out_qs, uint32_t* out_qe, uint8_t* out_status, uint8_t* out_tier, hipStream_t stream) {
+    const hipMemcpyKind kind = host ? hipMemcpyDeviceToHost : hipMemcpyDeviceToDevice;
+    uint32_t* outs[5] = {out_score, out_rs, out_re, out_qs, out_qe};
+    uint32_t* devs[5] = {rd.score, rd.rs, rd.re, rd.qs, rd.qe};
+    for (int k = 0; k < 5; ++k) ZSW_HIP(ctx, hipMemcpyAsync(outs[k], devs[k], (size_t)n * 4, kind, stream));
+    ZSW_HIP(ctx, hipMemcpyAsync(out_status, rd.status, n, kind, stream));
+    if (out_tier) ZSW_HIP(ctx, hipMemcpyAsync(out_tier, rd.tier, n, kind, stream));
+    if (host) ZSW_HIP(ctx, hipStreamSynchronize(stream));
+    return ZSW_OK;
+}
+
 zsw_error run_ranges(zsw_context* ctx, const zsw_batch* reads, const ResultRule& rule, uint32_t* out_score, uint32_t* out_rs,
                      uint32_t* out_re, uint32_t* out_qs, uint32_t* out_qe, uint8_t* out_status, uint8_t* out_tier, void* stream_) {
     DeviceGuard device_guard(ctx);
@@ -565,26 +582,14 @@ zsw_error run_ranges(zsw_context* ctx, const zsw_batch* reads, const ResultRule&
         return fail(ctx, ZSW_ERR_INVALID_ARGUMENT, "null argument");
     const uint32_t n = (uint32_t)reads->n_reads;
     Staged st;
-    {
-        uint32_t dummy_score = 0;
-        uint8_t dummy_status = 0;
-        zsw_error ze = stage(ctx, reads, stream, false, false, &dummy_score, &dummy_status, nullptr, nullptr, nullptr, &st);
-        if (ze != ZSW_OK) return ze;
-    }
-    if (n == 0) return ZSW_OK;
+    zsw_error ze = stage_reads(ctx, reads, stream, &st);
+    if (ze != ZSW_OK || n == 0) return ze;
     RangesDev rd;
     ctx->timer.begin(stream);
-    zsw_error ze = ranges_device(ctx, st, rule, stream, &rd);
+    ze = ranges_device(ctx, st, rule, stream, &rd);
     ctx->timer.end(stream);
     if (ze != ZSW_OK) return ze;
-    const hipMemcpyKind kind = reads->mem == ZSW_MEM_HOST ? hipMemcpyDeviceToHost : hipMemcpyDeviceToDevice;
-    uint32_t* outs[5] = {out_score, out_rs, out_re, out_qs, out_qe};
-    uint32_t* devs[5] = {rd.score, rd.rs, rd.re, rd.qs, rd.qe};
-    for (int k = 0; k < 5; ++k) ZSW_HIP(ctx, hipMemcpyAsync(outs[k], devs[k], (size_t)n * 4, kind, stream));
-    ZSW_HIP(ctx, hipMemcpyAsync(out_status, rd.status, n, kind, stream));
-    if (out_tier) ZSW_HIP(ctx, hipMemcpyAsync(out_tier, rd.tier, n, kind, stream));
-    if (reads->mem == ZSW_MEM_HOST) ZSW_HIP(ctx, hipStreamSynchronize(stream));
-    return ZSW_OK;
+    return copy_ranges_out(ctx, rd, n, reads->mem == ZSW_MEM_HOST, out_score, out_rs, out_re, out_qs, out_qe, out_status, out_tier, stream);
 }
 
 
@@ -594,9 +599,82 @@ __global__ void cert_status_kernel(uint32_t n, const uint8_t* status, const uint
     if (i < n) out[i] = done[i] ? (uint8_t)ZSW_STATUS_UNMAPPED : status[i];
 }
 
-hipError_t launch_cert_status(uint32_t n, const uint8_t* status, const uint8_t* done, uint8_t* out, hipStream_t stream) {
+static hipError_t launch_cert_status(uint32_t n, const uint8_t* status, const uint8_t* done, uint8_t* out, hipStream_t stream) {
     if (n) hipLaunchKernelGGL(cert_status_kernel, dim3((n + 255) / 256), dim3(256), 0, stream, n, status, done, out);
     return hipGetLastError();
+}
+
+// The fields of ThreePassArgs that the certificate pass and the third pass share: batch, scoring, ranges, and the ciglet and output
+// buffers of ctx->a_ws, sized here for 32 ciglets per read. pseq: non-null = the shared-profile role (ThreePassArgs::pseq).
+static zsw_error threepass_args(zsw_context* ctx, const Staged& st, const RangesDev& rd, const uint8_t* pseq, uint32_t pseq_len, int invert,
+                                ThreePassArgs* a) {
+    const uint32_t n = st.b.n_reads;
+    DevBuf* ws = ctx->a_ws;
+    a->maxc = 32;
+    ZSW_HIP(ctx, ws[WS_ALN].ensure((size_t)n * sizeof(zsw_alignment)));
+    ZSW_HIP(ctx, ws[WS_CIGSTART].ensure((size_t)n * 8));
+    ZSW_HIP(ctx, ws[WS_CIGRAW].ensure((size_t)n * 4));
+    ZSW_HIP(ctx, ws[WS_FBLIST].ensure((size_t)n * 4 + 4));
+    ZSW_HIP(ctx, ws[WS_ITEMS].ensure((size_t)n * 4 + 4));
+    ZSW_HIP(ctx, ws[WS_FBCOUNT].ensure(16));
+    ZSW_HIP(ctx, ws[WS_CIG].ensure((size_t)n * a->maxc * 4));
+    a->b = st.b;
+    if (pseq) {
+        a->pseq = pseq;
+        a->pseq_len = pseq_len;
+    } else {
+        a->ref = ctx->d_ref.as<uint8_t>();
+        a->ref_len = (uint32_t)ctx->ref_len;
+    }
+    a->sc = ctx->d_sc.as<ScoringDev>();
+    a->score = rd.score;
+    a->rs = rd.rs;
+    a->re = rd.re;
+    a->qs = rd.qs;
+    a->qe = rd.qe;
+    a->status = rd.status;
+    a->cig = ws[WS_CIG].as<uint32_t>();
+    a->cig_start = ws[WS_CIGSTART].as<uint64_t>();
+    a->cig_raw = ws[WS_CIGRAW].as<uint32_t>();
+    a->aln = ws[WS_ALN].as<zsw_alignment>();
+    a->fb_list = ws[WS_FBLIST].as<uint32_t>();
+    a->fb_count = ws[WS_FBCOUNT].as<uint32_t>();
+    a->invert = invert;
+    return ZSW_OK;
+}
+
+zsw_error certificate_pass(zsw_context* ctx, const Staged& st, const RangesDev& rd, const uint8_t* settled, const uint8_t* pseq, uint32_t pseq_len,
+                           int invert, hipStream_t stream, const uint8_t** pass2_status) {
+    const uint32_t n = st.b.n_reads;
+    DevBuf* ws = ctx->a_ws;
+    ZSW_HIP(ctx, ws[WS_CERT_DONE].ensure((size_t)n + 4));
+    ZSW_HIP(ctx, ws[WS_CERT_STATUS].ensure((size_t)n + 4));
+    ThreePassArgs a;
+    zsw_error ze = threepass_args(ctx, st, rd, pseq, pseq_len, invert, &a);
+    if (ze != ZSW_OK) return ze;
+    int maxw = 0;
+    for (int i = 0; i < ctx->h_sc.S * ctx->h_sc.S; ++i) maxw = std::max(maxw, (int)ctx->h_sc.w[i]);
+    a.cert_ok = settled;
+    a.cert_done = ws[WS_CERT_DONE].as<uint8_t>();
+    a.cert_maxw = maxw;
+    a.cert_go = ctx->h_sc.gap_open;
+    a.cert_ge = ctx->h_sc.gap_extend;
+    // the classify launch writes cert_done for the reads with an alignment only: the others must not keep an earlier call's bytes
+    ZSW_HIP(ctx, hipMemsetAsync(a.cert_done, 0, n, stream));
+    // reads that need the sweeps over their two-run alternatives are listed and take a second, dense launch (ThreePassArgs::sweep_list)
+    ZSW_HIP(ctx, hipMemsetAsync(ws[WS_FBCOUNT].as<uint32_t>() + 2, 0, 4, stream));
+    a.sweep_list = ws[WS_ITEMS].as<uint32_t>();
+    a.sweep_count = ws[WS_FBCOUNT].as<uint32_t>() + 2;
+    hipError_t e = launch_threepass(a, std::min<uint32_t>((n + 63) / 64, 65536u), stream);
+    if (e != hipSuccess) return fail(ctx, ZSW_ERR_HIP, pseq ? "shared align: certificate pass" : "align: certificate pass", e);
+    a.list = a.sweep_list;
+    a.list_count = a.sweep_count;
+    a.sweep_pass = true;
+    e = launch_threepass(a, std::min<uint32_t>((n / 4 + 63) / 64 + 1, 16384u), stream);
+    if (e != hipSuccess) return fail(ctx, ZSW_ERR_HIP, pseq ? "shared align: certificate pass (sweeps)" : "align: certificate pass (sweeps)", e);
+    ZSW_HIP(ctx, launch_cert_status(n, rd.status, a.cert_done, ws[WS_CERT_STATUS].as<uint8_t>(), stream));
+    *pass2_status = ws[WS_CERT_STATUS].as<uint8_t>();
+    return ZSW_OK;
 }
 
 // (grid-stride, one atomic per wavefront at the end: 10 M statuses used to be 156,000 atomics on one word, 1.8 ms)
@@ -662,19 +740,10 @@ zsw_error run_align(zsw_context* ctx, const zsw_batch* reads, const ResultRule& 
                     uint8_t* out_op, uint64_t ciglet_cap, uint64_t* out_n_ciglets, void* stream_) {
     DeviceGuard device_guard(ctx);
     hipStream_t stream = (hipStream_t)stream_;
-    if (!ctx) return ZSW_ERR_INVALID_ARGUMENT;
-    if (!reads || !out_aln || !out_status || !out_n_ciglets || (ciglet_cap && (!out_inc || !out_op)))
-        return fail(ctx, ZSW_ERR_INVALID_ARGUMENT, "null argument");
-    const uint32_t n = (uint32_t)reads->n_reads;
     Staged st;
-    {
-        uint32_t dummy_score = 0;
-        uint8_t dummy_status = 0;
-        zsw_error ze = stage(ctx, reads, stream, false, false, &dummy_score, &dummy_status, nullptr, nullptr, nullptr, &st);
-        if (ze != ZSW_OK) return ze;
-    }
-    *out_n_ciglets = 0;
-    if (n == 0) return ZSW_OK;
+    zsw_error ze = stage_align(ctx, reads, out_aln, out_status, out_inc, out_op, ciglet_cap, out_n_ciglets, stream, &st);
+    const uint32_t n = st.b.n_reads;
+    if (ze != ZSW_OK || n == 0) return ze;
     const bool host = reads->mem == ZSW_MEM_HOST;
     DevBuf* ws = ctx->a_ws;
     ZSW_HIP(ctx, ws[WS_SCORE].ensure((size_t)n * 4 + 4));
@@ -687,7 +756,6 @@ zsw_error run_align(zsw_context* ctx, const zsw_batch* reads, const ResultRule& 
     so.status = ws[WS_STATUS].as<uint8_t>();
     so.tier = ws[WS_TIER].as<uint8_t>();
     so.ref_end = ws[WS_REND].as<uint32_t>();
-    so.query_end = nullptr;
     so.fb_list = ctx->d_fb_list.as<uint32_t>();
     so.fb_count = ctx->d_fb_count.as<uint32_t>();
     // the seeded first pass leaves, per read it accepts, the row from which pass 2 may start with a zero state
@@ -701,76 +769,17 @@ zsw_error run_align(zsw_context* ctx, const zsw_batch* reads, const ResultRule& 
     hipError_t e = hipSuccess;
     const bool certify = seeded_reverse_possible(ctx, st) && !(ctx->flags() & ZSW_DEBUG_ALIGN_NO_CERTIFICATE) && ctx->h_sc.gap_open > 0;
     if (certify) {
-        const uint32_t MAXC0 = 32;
         ZSW_HIP(ctx, ws[WS_CERT_OK].ensure((size_t)n + 4));
-        ZSW_HIP(ctx, ws[WS_CERT_DONE].ensure((size_t)n + 4));
-        ZSW_HIP(ctx, ws[WS_CERT_STATUS].ensure((size_t)n + 4));
-        ZSW_HIP(ctx, ws[WS_ALN].ensure((size_t)n * sizeof(zsw_alignment)));
-        ZSW_HIP(ctx, ws[WS_CIGSTART].ensure((size_t)n * 8));
-        ZSW_HIP(ctx, ws[WS_CIGRAW].ensure((size_t)n * 4));
-        ZSW_HIP(ctx, ws[WS_CIG].ensure((size_t)n * MAXC0 * 4));
-        ZSW_HIP(ctx, ws[WS_FBLIST].ensure((size_t)n * 4 + 4));
-        ZSW_HIP(ctx, ws[WS_FBCOUNT].ensure(16));
-        RangesCert cert;
-        cert.safe_row = so.safe_row;
-        cert.settled = ws[WS_CERT_OK].as<uint8_t>();
-        RangesDev unused;
-        zsw_error ze = ranges_device(ctx, st, rule, stream, &unused, &cert);
+        RangesCert cert{so.safe_row, ws[WS_CERT_OK].as<uint8_t>()};
+        RangesDev rd;
+        ze = ranges_device(ctx, st, rule, stream, &rd, &cert);
         if (ze != ZSW_OK) return ze;
-        so.score = cert.fwd.score;
-        so.status = cert.fwd.status;
-        so.tier = cert.fwd.tier;
-        so.ref_end = cert.fwd.ref_end;
-        int maxw = 0;
-        for (int i = 0; i < ctx->h_sc.S * ctx->h_sc.S; ++i) maxw = std::max(maxw, (int)ctx->h_sc.w[i]);
-        ThreePassArgs a;
-        a.b = st.b;
-        a.ref = ctx->d_ref.as<uint8_t>();
-        a.ref_len = (uint32_t)ctx->ref_len;
-        a.sc = ctx->d_sc.as<ScoringDev>();
-        a.score = so.score;
-        a.rs = cert.rs;
-        a.re = cert.fwd.ref_end;
-        a.qs = cert.qs;
-        a.qe = cert.fwd.query_end;
-        a.status = so.status;
-        a.list = nullptr;
-        a.list_count = nullptr;
-        a.dp_list = nullptr;
-        a.dp_count = nullptr;
-        a.dp_need_max = nullptr;
-        a.scratch = nullptr;
-        a.slots = 0;
-        a.slot_bytes = 0;
-        a.cig = ws[WS_CIG].as<uint32_t>();
-        a.maxc = MAXC0;
-        a.pool_base = 0;
-        a.by_item = 0;
-        a.cig_start = ws[WS_CIGSTART].as<uint64_t>();
-        a.cig_raw = ws[WS_CIGRAW].as<uint32_t>();
-        a.aln = ws[WS_ALN].as<zsw_alignment>();
-        a.fb_list = ws[WS_FBLIST].as<uint32_t>();
-        a.fb_count = ws[WS_FBCOUNT].as<uint32_t>();
-        a.invert = invert;
-        a.cert_ok = cert.settled;
-        a.cert_done = ws[WS_CERT_DONE].as<uint8_t>();
-        a.cert_maxw = maxw;
-        a.cert_go = ctx->h_sc.gap_open;
-        a.cert_ge = ctx->h_sc.gap_extend;
-        // reads that need the sweeps over their two-run alternatives are listed and take a second, dense launch (ThreePassArgs::sweep_list)
-        ZSW_HIP(ctx, ws[WS_ITEMS].ensure((size_t)n * 4 + 4));
-        ZSW_HIP(ctx, hipMemsetAsync(ws[WS_FBCOUNT].as<uint32_t>() + 2, 0, 4, stream));
-        a.sweep_list = ws[WS_ITEMS].as<uint32_t>();
-        a.sweep_count = ws[WS_FBCOUNT].as<uint32_t>() + 2;
-        e = launch_threepass(a, std::min<uint32_t>((n + 63) / 64, 65536u), stream);
-        if (e != hipSuccess) return fail(ctx, ZSW_ERR_HIP, "align: certificate pass", e);
-        a.list = a.sweep_list;
-        a.list_count = a.sweep_count;
-        a.sweep_pass = true;
-        e = launch_threepass(a, std::min<uint32_t>((n / 4 + 63) / 64 + 1, 16384u), stream);
-        if (e != hipSuccess) return fail(ctx, ZSW_ERR_HIP, "align: certificate pass (sweeps)", e);
-        hipLaunchKernelGGL(cert_status_kernel, dim3((n + 255) / 256), dim3(256), 0, stream, n, so.status, ws[WS_CERT_DONE].as<uint8_t>(), ws[WS_CERT_STATUS].as<uint8_t>());
-        pass2_status = ws[WS_CERT_STATUS].as<uint8_t>();
+        so.score = rd.score;
+        so.status = rd.status;
+        so.tier = rd.tier;
+        so.ref_end = rd.re;
+        ze = certificate_pass(ctx, st, rd, cert.settled, nullptr, 0, invert, stream, &pass2_status);
+        if (ze != ZSW_OK) return ze;
     } else {
         e = launch_score(ctx->d_sc.as<ScoringDev>(), ctx->h_sc, st.b, st.max_len, ctx->d_ref.as<uint8_t>(), (uint32_t)ctx->ref_len, rule, so, score_ws(ctx), stream,
                          nullptr, 1);
@@ -892,7 +901,7 @@ zsw_error run_align(zsw_context* ctx, const zsw_batch* reads, const ResultRule& 
         return ZSW_OK;
     };
     ctx->timer.begin(stream);
-    zsw_error ze = run_groups(groups, ws[WS_ITEMS].as<uint32_t>(), false, ws[WS_RING], ws[WS_CIG]);
+    ze = run_groups(groups, ws[WS_ITEMS].as<uint32_t>(), false, ws[WS_RING], ws[WS_CIG]);
     ctx->timer.end(stream);
     if (ze != ZSW_OK) return ze;
     // reads whose traceback left the retained window (or overflowed their ciglet slots): rerun keeping every row
@@ -940,22 +949,12 @@ zsw_error run_threepass(zsw_context* ctx, const zsw_batch* reads, const ResultRu
                         uint64_t* out_n_ciglets, void* stream_) {
     DeviceGuard device_guard(ctx);
     hipStream_t stream = (hipStream_t)stream_;
-    if (!ctx) return ZSW_ERR_INVALID_ARGUMENT;
-    if (!reads || !out_aln || !out_status || !out_n_ciglets || (ciglet_cap && (!out_inc || !out_op)))
-        return fail(ctx, ZSW_ERR_INVALID_ARGUMENT, "null argument");
-    const uint32_t n = (uint32_t)reads->n_reads;
     Staged st;
-    {
-        uint32_t dummy_score = 0;
-        uint8_t dummy_status = 0;
-        zsw_error ze = stage(ctx, reads, stream, false, false, &dummy_score, &dummy_status, nullptr, nullptr, nullptr, &st);
-        if (ze != ZSW_OK) return ze;
-    }
-    *out_n_ciglets = 0;
-    if (n == 0) return ZSW_OK;
+    zsw_error ze = stage_align(ctx, reads, out_aln, out_status, out_inc, out_op, ciglet_cap, out_n_ciglets, stream, &st);
+    if (ze != ZSW_OK || reads->n_reads == 0) return ze;
     RangesDev rd;
     ctx->timer.begin(stream);
-    zsw_error ze = ranges_device(ctx, st, rule, stream, &rd);
+    ze = ranges_device(ctx, st, rule, stream, &rd);
     if (ze != ZSW_OK) return ze;
     return threepass_third_pass(ctx, st, rd, nullptr, 0, reads->mem == ZSW_MEM_HOST, invert, out_aln, out_status, out_tier, out_inc, out_op, ciglet_cap,
                                 out_n_ciglets, stream);
@@ -967,49 +966,15 @@ zsw_error threepass_third_pass(zsw_context* ctx, const Staged& st, const RangesD
                                zsw_alignment* out_aln, uint8_t* out_status, uint8_t* out_tier, uint32_t* out_inc, uint8_t* out_op, uint64_t ciglet_cap,
                                uint64_t* out_n_ciglets, hipStream_t stream) {
     const uint32_t n = st.b.n_reads;
-    zsw_error ze = ZSW_OK;
     DevBuf* ws = ctx->a_ws;
-    const uint32_t MAXC = 32;
-    ZSW_HIP(ctx, ws[WS_ALN].ensure((size_t)n * sizeof(zsw_alignment)));
-    ZSW_HIP(ctx, ws[WS_CIGSTART].ensure((size_t)n * 8));
-    ZSW_HIP(ctx, ws[WS_CIGRAW].ensure((size_t)n * 4));
-    ZSW_HIP(ctx, ws[WS_FBLIST].ensure((size_t)n * 4 + 4));
-    ZSW_HIP(ctx, ws[WS_ITEMS].ensure((size_t)n * 4 + 4));
-    ZSW_HIP(ctx, ws[WS_FBCOUNT].ensure(16));
-    ZSW_HIP(ctx, ws[WS_CIG].ensure((size_t)n * MAXC * 4));
+    ThreePassArgs a;
+    zsw_error ze = threepass_args(ctx, st, rd, pseq, pseq_len, invert, &a);
+    if (ze != ZSW_OK) return ze;
     ZSW_HIP(ctx, hipMemsetAsync(ws[WS_FBCOUNT].p, 0, 16, stream));
     uint32_t* counters = ws[WS_FBCOUNT].as<uint32_t>();  // [0] rerun count, [1] dp count, [2] largest slot need
-    ThreePassArgs a;
-    a.b = st.b;
-    a.ref = ctx->d_ref.as<uint8_t>();
-    a.ref_len = (uint32_t)ctx->ref_len;
-    a.sc = ctx->d_sc.as<ScoringDev>();
-    a.score = rd.score;
-    a.rs = rd.rs;
-    a.re = rd.re;
-    a.qs = rd.qs;
-    a.qe = rd.qe;
-    a.status = rd.status;
-    a.list = nullptr;
-    a.list_count = nullptr;
     a.dp_list = ws[WS_ITEMS].as<uint32_t>();
     a.dp_count = counters + 1;
     a.dp_need_max = counters + 2;
-    a.scratch = nullptr;
-    a.slots = 0;
-    a.slot_bytes = 0;
-    a.cig = ws[WS_CIG].as<uint32_t>();
-    a.maxc = MAXC;
-    a.pool_base = 0;
-    a.by_item = 0;
-    a.cig_start = ws[WS_CIGSTART].as<uint64_t>();
-    a.cig_raw = ws[WS_CIGRAW].as<uint32_t>();
-    a.aln = ws[WS_ALN].as<zsw_alignment>();
-    a.fb_list = ws[WS_FBLIST].as<uint32_t>();
-    a.fb_count = counters;
-    a.invert = invert;
-    a.pseq = pseq;
-    a.pseq_len = pseq_len;
     hipError_t e = launch_threepass(a, std::min<uint32_t>((n + 63) / 64, 65536u), stream);  // classify + no-gaps shortcut
     if (e != hipSuccess) return fail(ctx, ZSW_ERR_HIP, "3-pass classify", e);
     uint32_t h_cnt[3] = {0, 0, 0};
@@ -1039,7 +1004,7 @@ zsw_error threepass_third_pass(zsw_context* ctx, const Staged& st, const RangesD
         return ZSW_OK;
     };
     const uint64_t SLOT_CAP = 96 * 1024;
-    ze = dp_pass(ws[WS_ITEMS].as<uint32_t>(), counters + 1, h_cnt[1], std::min<uint64_t>(std::max<uint32_t>(h_cnt[2], 64), SLOT_CAP), MAXC, 0,
+    ze = dp_pass(ws[WS_ITEMS].as<uint32_t>(), counters + 1, h_cnt[1], std::min<uint64_t>(std::max<uint32_t>(h_cnt[2], 64), SLOT_CAP), a.maxc, 0,
                  ws[WS_CIG], ws[WS_RING]);
     if (ze != ZSW_OK) return ze;
     ZSW_HIP(ctx, hipMemcpyAsync(h_cnt, counters, 4, hipMemcpyDeviceToHost, stream));
@@ -1090,10 +1055,8 @@ extern "C" {
 zsw_error zsw_align_batch(zsw_context* ctx, const zsw_batch* reads, zsw_int_type int_type, int lanes, int invert,
                           zsw_alignment* out_aln, uint8_t* out_status, uint32_t* out_inc, uint8_t* out_op,
                           uint64_t ciglet_cap, uint64_t* out_n_ciglets, void* stream) {
-    if (!ctx) return ZSW_ERR_INVALID_ARGUMENT;
-    if (!valid_lanes(lanes)) return fail(ctx, ZSW_ERR_INVALID_ARGUMENT, "lanes must be a power of two in 2..64");
     ResultRule rule;
-    if (!rule_direct(int_type, ctx->bias, &rule)) return fail(ctx, ZSW_ERR_INVALID_ARGUMENT, "bad int_type");
+    if (zsw_error ze = rule_direct(ctx, int_type, lanes, &rule); ze != ZSW_OK) return ze;
     return run_align(ctx, reads, rule, lanes, lanes, lanes, invert, out_aln, out_status, nullptr, out_inc, out_op, ciglet_cap,
                      out_n_ciglets, stream);
 }
@@ -1101,10 +1064,8 @@ zsw_error zsw_align_batch(zsw_context* ctx, const zsw_batch* reads, zsw_int_type
 zsw_error zsw_align_batch_from(zsw_context* ctx, const zsw_batch* reads, int from_width, int preset_bits, int invert,
                                zsw_alignment* out_aln, uint8_t* out_status, uint8_t* out_tier, uint32_t* out_inc,
                                uint8_t* out_op, uint64_t ciglet_cap, uint64_t* out_n_ciglets, void* stream) {
-    if (!ctx) return ZSW_ERR_INVALID_ARGUMENT;
-    if (preset_bits != 128 && preset_bits != 256 && preset_bits != 512) return fail(ctx, ZSW_ERR_INVALID_ARGUMENT, "preset_bits");
     ResultRule rule;
-    if (!rule_cascade(from_width, &rule)) return fail(ctx, ZSW_ERR_INVALID_ARGUMENT, "from_width");
+    if (zsw_error ze = rule_cascade(ctx, from_width, preset_bits, &rule); ze != ZSW_OK) return ze;
     return run_align(ctx, reads, rule, preset_bits / 8, preset_bits / 16, preset_bits / 32, invert, out_aln, out_status, out_tier,
                      out_inc, out_op, ciglet_cap, out_n_ciglets, stream);
 }
@@ -1212,18 +1173,18 @@ zsw_error zsw_set_scoring(zsw_context* ctx, const int8_t* weights, int S, const 
     s.gap_open = -gap_open;
     s.gap_extend = -gap_extend;
     ctx->bias = -mn;  // WeightMatrix::get_bias / to_biased_matrix (matrices/mod.rs:452-491)
+    // the same scoring with the matrix transposed, for the role-swapped passes of the shared-profile role
+    ScoringDev& t = ctx->h_sc_t;
+    t = s;
+    for (int r = 0; r < S; ++r)
+        for (int q = 0; q < S; ++q) t.w[r * S + q] = s.w[q * S + r];
     ZSW_HIP(ctx, hipSetDevice(ctx->device));
     // asynchronous score calls (on any stream, blocking or not) may still be reading the previous tables
     if (ctx->scoring_set) ZSW_HIP(ctx, hipDeviceSynchronize());
     ZSW_HIP(ctx, ctx->d_sc.ensure(sizeof(ScoringDev)));
     ZSW_HIP(ctx, hipMemcpy(ctx->d_sc.p, &s, sizeof(ScoringDev), hipMemcpyHostToDevice));
-    {  // the same scoring with the matrix transposed, for the score-only calls of the shared-profile role
-        ScoringDev t = s;
-        for (int r = 0; r < S; ++r)
-            for (int q = 0; q < S; ++q) t.w[r * S + q] = s.w[q * S + r];
-        ZSW_HIP(ctx, ctx->d_sc_t.ensure(sizeof(ScoringDev)));
-        ZSW_HIP(ctx, hipMemcpy(ctx->d_sc_t.p, &t, sizeof(ScoringDev), hipMemcpyHostToDevice));
-    }
+    ZSW_HIP(ctx, ctx->d_sc_t.ensure(sizeof(ScoringDev)));
+    ZSW_HIP(ctx, hipMemcpy(ctx->d_sc_t.p, &t, sizeof(ScoringDev), hipMemcpyHostToDevice));
     ctx->scoring_set = true;
     ctx->seed.valid = false;  // the index spells k-mers with the matrix's good residues
     ctx->seed_rev.valid = false;
@@ -1255,19 +1216,15 @@ zsw_error zsw_set_reference(zsw_context* ctx, const uint8_t* reference, size_t l
 
 zsw_error zsw_score_batch(zsw_context* ctx, const zsw_batch* reads, zsw_int_type int_type, int lanes,
                           uint32_t* out_score, uint8_t* out_status, void* stream) {
-    if (!ctx) return ZSW_ERR_INVALID_ARGUMENT;
-    if (!valid_lanes(lanes)) return fail(ctx, ZSW_ERR_INVALID_ARGUMENT, "lanes must be a power of two in 2..64");
     ResultRule rule;
-    if (!rule_direct(int_type, ctx->bias, &rule)) return fail(ctx, ZSW_ERR_INVALID_ARGUMENT, "bad int_type");
+    if (zsw_error ze = rule_direct(ctx, int_type, lanes, &rule); ze != ZSW_OK) return ze;
     return run_score(ctx, reads, rule, false, out_score, out_status, nullptr, nullptr, nullptr, stream);
 }
 
 zsw_error zsw_score_batch_from(zsw_context* ctx, const zsw_batch* reads, int from_width, int preset_bits,
                                uint32_t* out_score, uint8_t* out_status, uint8_t* out_tier, void* stream) {
-    if (!ctx) return ZSW_ERR_INVALID_ARGUMENT;
-    if (preset_bits != 128 && preset_bits != 256 && preset_bits != 512) return fail(ctx, ZSW_ERR_INVALID_ARGUMENT, "preset_bits");
     ResultRule rule;
-    if (!rule_cascade(from_width, &rule)) return fail(ctx, ZSW_ERR_INVALID_ARGUMENT, "from_width");
+    if (zsw_error ze = rule_cascade(ctx, from_width, preset_bits, &rule); ze != ZSW_OK) return ze;
     return run_score(ctx, reads, rule, false, out_score, out_status, out_tier, nullptr, nullptr, stream);
 }
 
@@ -1276,19 +1233,16 @@ zsw_error zsw_score_ends_batch(zsw_context* ctx, const zsw_batch* reads, zsw_int
                                uint8_t* out_status, void* stream) {
     if (!ctx) return ZSW_ERR_INVALID_ARGUMENT;
     if (!out_ref_end || !out_query_end) return fail(ctx, ZSW_ERR_INVALID_ARGUMENT, "null argument");
-    if (!valid_lanes(lanes)) return fail(ctx, ZSW_ERR_INVALID_ARGUMENT, "lanes must be a power of two in 2..64");
     ResultRule rule;
-    if (!rule_direct(int_type, ctx->bias, &rule)) return fail(ctx, ZSW_ERR_INVALID_ARGUMENT, "bad int_type");
+    if (zsw_error ze = rule_direct(ctx, int_type, lanes, &rule); ze != ZSW_OK) return ze;
     return run_score(ctx, reads, rule, true, out_score, out_status, nullptr, out_ref_end, out_query_end, stream);
 }
 
 zsw_error zsw_score_ranges_batch(zsw_context* ctx, const zsw_batch* reads, zsw_int_type int_type, int lanes,
                                  uint32_t* out_score, uint32_t* out_ref_start, uint32_t* out_ref_end,
                                  uint32_t* out_query_start, uint32_t* out_query_end, uint8_t* out_status, void* stream) {
-    if (!ctx) return ZSW_ERR_INVALID_ARGUMENT;
-    if (!valid_lanes(lanes)) return fail(ctx, ZSW_ERR_INVALID_ARGUMENT, "lanes must be a power of two in 2..64");
     ResultRule rule;
-    if (!rule_direct(int_type, ctx->bias, &rule)) return fail(ctx, ZSW_ERR_INVALID_ARGUMENT, "bad int_type");
+    if (zsw_error ze = rule_direct(ctx, int_type, lanes, &rule); ze != ZSW_OK) return ze;
     return run_ranges(ctx, reads, rule, out_score, out_ref_start, out_ref_end, out_query_start, out_query_end, out_status, nullptr, stream);
 }
 
@@ -1296,10 +1250,8 @@ zsw_error zsw_score_ranges_batch_from(zsw_context* ctx, const zsw_batch* reads, 
                                       uint32_t* out_score, uint32_t* out_ref_start, uint32_t* out_ref_end,
                                       uint32_t* out_query_start, uint32_t* out_query_end, uint8_t* out_status, uint8_t* out_tier,
                                       void* stream) {
-    if (!ctx) return ZSW_ERR_INVALID_ARGUMENT;
-    if (preset_bits != 128 && preset_bits != 256 && preset_bits != 512) return fail(ctx, ZSW_ERR_INVALID_ARGUMENT, "preset_bits");
     ResultRule rule;
-    if (!rule_cascade(from_width, &rule)) return fail(ctx, ZSW_ERR_INVALID_ARGUMENT, "from_width");
+    if (zsw_error ze = rule_cascade(ctx, from_width, preset_bits, &rule); ze != ZSW_OK) return ze;
     return run_ranges(ctx, reads, rule, out_score, out_ref_start, out_ref_end, out_query_start, out_query_end, out_status, out_tier,
                       stream);
 }
@@ -1307,20 +1259,16 @@ zsw_error zsw_score_ranges_batch_from(zsw_context* ctx, const zsw_batch* reads, 
 zsw_error zsw_align_3pass_batch(zsw_context* ctx, const zsw_batch* reads, zsw_int_type int_type, int lanes, int invert,
                                 zsw_alignment* out_aln, uint8_t* out_status, uint32_t* out_inc, uint8_t* out_op,
                                 uint64_t ciglet_cap, uint64_t* out_n_ciglets, void* stream) {
-    if (!ctx) return ZSW_ERR_INVALID_ARGUMENT;
-    if (!valid_lanes(lanes)) return fail(ctx, ZSW_ERR_INVALID_ARGUMENT, "lanes must be a power of two in 2..64");
     ResultRule rule;
-    if (!rule_direct(int_type, ctx->bias, &rule)) return fail(ctx, ZSW_ERR_INVALID_ARGUMENT, "bad int_type");
+    if (zsw_error ze = rule_direct(ctx, int_type, lanes, &rule); ze != ZSW_OK) return ze;
     return run_threepass(ctx, reads, rule, invert, out_aln, out_status, nullptr, out_inc, out_op, ciglet_cap, out_n_ciglets, stream);
 }
 
 zsw_error zsw_align_3pass_batch_from(zsw_context* ctx, const zsw_batch* reads, int from_width, int preset_bits, int invert,
                                      zsw_alignment* out_aln, uint8_t* out_status, uint8_t* out_tier, uint32_t* out_inc,
                                      uint8_t* out_op, uint64_t ciglet_cap, uint64_t* out_n_ciglets, void* stream) {
-    if (!ctx) return ZSW_ERR_INVALID_ARGUMENT;
-    if (preset_bits != 128 && preset_bits != 256 && preset_bits != 512) return fail(ctx, ZSW_ERR_INVALID_ARGUMENT, "preset_bits");
     ResultRule rule;
-    if (!rule_cascade(from_width, &rule)) return fail(ctx, ZSW_ERR_INVALID_ARGUMENT, "from_width");
+    if (zsw_error ze = rule_cascade(ctx, from_width, preset_bits, &rule); ze != ZSW_OK) return ze;
     return run_threepass(ctx, reads, rule, invert, out_aln, out_status, out_tier, out_inc, out_op, ciglet_cap, out_n_ciglets, stream);
 }
 

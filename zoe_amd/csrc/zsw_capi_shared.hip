@@ -23,9 +23,8 @@ __global__ void empty_is_unmapped_kernel(uint32_t n, uint8_t* status) {
     if (i < n && status[i] == ZSW_STATUS_EMPTY) status[i] = ZSW_STATUS_UNMAPPED;
 }
 
-__global__ void iota_some_kernel(uint32_t n, const uint8_t* status, const uint8_t* tier, uint8_t want_tier, uint32_t* list, uint32_t* count) {
-    const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
-    const bool take = i < n && status[i] == ZSW_STATUS_SOME && tier[i] == want_tier;
+// appends i to list[] where `take` (one atomic per wavefront; the order of the list is not defined)
+__device__ __forceinline__ void ballot_append(bool take, uint32_t i, uint32_t* list, uint32_t* count) {
     const unsigned long long m = __ballot(take);
     if (m) {
         const int lane = threadIdx.x & 63, leader = __ffsll((long long)m) - 1;
@@ -36,18 +35,15 @@ __global__ void iota_some_kernel(uint32_t n, const uint8_t* status, const uint8_
     }
 }
 
+__global__ void iota_some_kernel(uint32_t n, const uint8_t* status, const uint8_t* tier, uint8_t want_tier, uint32_t* list, uint32_t* count) {
+    const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
+    ballot_append(i < n && status[i] == ZSW_STATUS_SOME && tier[i] == want_tier, i, list, count);
+}
+
 // reads whose ends the role-swapped seeded pass could not settle (unique[i] == 0): the list of the exact shared-role kernel
 __global__ void select_not_unique_kernel(uint32_t n, const uint8_t* unique, uint32_t* list, uint32_t* count) {
     const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
-    const bool take = i < n && unique[i] == 0;
-    const unsigned long long m = __ballot(take);
-    if (m) {
-        const int lane = threadIdx.x & 63, leader = __ffsll((long long)m) - 1;
-        uint32_t base = 0;
-        if (lane == leader) base = atomicAdd(count, (uint32_t)__popcll(m));
-        base = (uint32_t)__shfl((int)base, leader, 64);
-        if (take) list[base + (uint32_t)__popcll(m & ((1ull << lane) - 1ull))] = i;
-    }
+    ballot_append(i < n && unique[i] == 0, i, list, count);
 }
 
 // every read of the batch reversed (same offsets): the other sequence of the reverse pass
@@ -156,9 +152,6 @@ zsw_error shared_ends_device(zsw_context* ctx, const Staged& st, const ResultRul
         ZSW_HIP(ctx, ws[SH_UCOUNT].ensure(16));
         ZSW_HIP(ctx, hipMemsetAsync(ws[SH_UNIQUE].p, 0, n, stream));
         ZSW_HIP(ctx, hipMemsetAsync(ws[SH_UCOUNT].p, 0, 4, stream));
-        ScoringDev h_t = ctx->h_sc;
-        for (int r = 0; r < h_t.S; ++r)
-            for (int q = 0; q < h_t.S; ++q) h_t.w[r * h_t.S + q] = ctx->h_sc.w[q * h_t.S + r];
         ScoreOut o2 = out;
         o2.ref_end = out.query_end;   // rows of the swapped problem are positions of the profile sequence
         o2.query_end = out.ref_end;   // its columns positions of the read
@@ -166,7 +159,7 @@ zsw_error shared_ends_device(zsw_context* ctx, const Staged& st, const ResultRul
         o2.fb_count = ctx->d_fb_count.as<uint32_t>();
         o2.unique = ws[SH_UNIQUE].as<uint8_t>();
         o2.skip_handed_back = true;
-        hipError_t e = launch_score(ctx->d_sc_t.as<ScoringDev>(), h_t, st.b, st.max_len, ctx->d_pseq.as<uint8_t>(), (uint32_t)ctx->pseq_len, rule, o2,
+        hipError_t e = launch_score(ctx->d_sc_t.as<ScoringDev>(), ctx->h_sc_t, st.b, st.max_len, ctx->d_pseq.as<uint8_t>(), (uint32_t)ctx->pseq_len, rule, o2,
                                     score_ws(ctx), stream, nullptr, 3);
         if (e != hipSuccess) return fail(ctx, ZSW_ERR_HIP, "shared ends: role-swapped seeded pass", e);
         hipLaunchKernelGGL(select_not_unique_kernel, dim3((n + 255) / 256), dim3(256), 0, stream, n, ws[SH_UNIQUE].as<uint8_t>(),
@@ -193,18 +186,13 @@ zsw_error run_score_shared(zsw_context* ctx, const zsw_batch* reads, const Resul
     if (ze != ZSW_OK) return ze;
     if (reads->n_reads == 0) return ZSW_OK;
     // roles swapped: the read is the profile of the ordinary kernels, the shared sequence their reference, the matrix transposed
-    ScoringDev h_t = ctx->h_sc;
-    for (int r = 0; r < h_t.S; ++r)
-        for (int q = 0; q < h_t.S; ++q) h_t.w[r * h_t.S + q] = ctx->h_sc.w[q * h_t.S + r];
     ScoreOut out;
     out.score = st.d_score;
     out.status = st.d_status;
     out.tier = st.d_tier;
-    out.ref_end = nullptr;
-    out.query_end = nullptr;
     out.fb_list = ctx->d_fb_list.as<uint32_t>();
     out.fb_count = ctx->d_fb_count.as<uint32_t>();
-    hipError_t e = launch_score(ctx->d_sc_t.as<ScoringDev>(), h_t, st.b, st.max_len, ctx->d_pseq.as<uint8_t>(), (uint32_t)ctx->pseq_len, rule, out,
+    hipError_t e = launch_score(ctx->d_sc_t.as<ScoringDev>(), ctx->h_sc_t, st.b, st.max_len, ctx->d_pseq.as<uint8_t>(), (uint32_t)ctx->pseq_len, rule, out,
                                 score_ws(ctx), stream, &ctx->timer, 0);
     if (e != hipSuccess) return fail(ctx, ZSW_ERR_HIP, "shared score launch", e);
     const uint32_t n = (uint32_t)reads->n_reads;
@@ -227,11 +215,8 @@ zsw_error run_ends_shared(zsw_context* ctx, const zsw_batch* reads, const Result
     ScoreOut out;
     out.score = st.d_score;
     out.status = st.d_status;
-    out.tier = nullptr;
     out.ref_end = st.d_rend;
     out.query_end = st.d_qend;
-    out.fb_list = nullptr;
-    out.fb_count = nullptr;
     ctx->timer.begin(stream);
     ze = shared_ends_device(ctx, st, rule, out, stream);
     ctx->timer.end(stream);
@@ -252,26 +237,14 @@ zsw_error run_ranges_shared(zsw_context* ctx, const zsw_batch* reads, const Resu
     hipStream_t stream = (hipStream_t)stream_;
     SharedStage guard(ctx, true);
     Staged st;
-    {
-        uint32_t dummy_score = 0;
-        uint8_t dummy_status = 0;
-        ze = stage(ctx, reads, stream, false, false, &dummy_score, &dummy_status, nullptr, nullptr, nullptr, &st);
-        if (ze != ZSW_OK) return ze;
-    }
-    const uint32_t n = (uint32_t)reads->n_reads;
-    if (n == 0) return ZSW_OK;
+    ze = stage_reads(ctx, reads, stream, &st);
+    const uint32_t n = st.b.n_reads;
+    if (ze != ZSW_OK || n == 0) return ze;
     RangesDev rd;
     ze = ranges_shared_device(ctx, st, rule, stream, &rd);
     if (ze != ZSW_OK) return ze;
     ctx->timer.end(stream);
-    const hipMemcpyKind kind = reads->mem == ZSW_MEM_HOST ? hipMemcpyDeviceToHost : hipMemcpyDeviceToDevice;
-    uint32_t* outs[5] = {out_score, out_rs, out_re, out_qs, out_qe};
-    const uint32_t* devs[5] = {rd.score, rd.rs, rd.re, rd.qs, rd.qe};
-    for (int k = 0; k < 5; ++k) ZSW_HIP(ctx, hipMemcpyAsync(outs[k], devs[k], (size_t)n * 4, kind, stream));
-    ZSW_HIP(ctx, hipMemcpyAsync(out_status, rd.status, n, kind, stream));
-    if (out_tier) ZSW_HIP(ctx, hipMemcpyAsync(out_tier, rd.tier, n, kind, stream));
-    if (reads->mem == ZSW_MEM_HOST) ZSW_HIP(ctx, hipStreamSynchronize(stream));
-    return ZSW_OK;
+    return copy_ranges_out(ctx, rd, n, reads->mem == ZSW_MEM_HOST, out_score, out_rs, out_re, out_qs, out_qe, out_status, out_tier, stream);
 }
 
 // settled (optional, n bytes): 1 where both maxima of the read sit in one cell each (the two seeded passes agree), else 0
@@ -291,8 +264,6 @@ zsw_error ranges_shared_device(zsw_context* ctx, const Staged& st, const ResultR
     fo.tier = ws[SH_TIER].as<uint8_t>();
     fo.ref_end = ws[SH_REND].as<uint32_t>();
     fo.query_end = ws[SH_QEND].as<uint32_t>();
-    fo.fb_list = nullptr;
-    fo.fb_count = nullptr;
     ctx->timer.begin(stream);
     bool seeded = false;
     ze = shared_ends_device(ctx, st, rule, fo, stream, &seeded);
@@ -302,11 +273,8 @@ zsw_error ranges_shared_device(zsw_context* ctx, const Staged& st, const ResultR
     ScoreOut ro;
     ro.score = ws[SH_RSCORE].as<uint32_t>();
     ro.status = ws[SH_RSTATUS].as<uint8_t>();
-    ro.tier = nullptr;
     ro.ref_end = ws[SH_RRS].as<uint32_t>();
     ro.query_end = ws[SH_RQS].as<uint32_t>();
-    ro.fb_list = nullptr;
-    ro.fb_count = nullptr;
     BatchDev rest = st.b;
     const uint32_t* rest_count = nullptr;
     if (settled) ZSW_HIP(ctx, hipMemsetAsync(settled, 0, n, stream));
@@ -316,16 +284,8 @@ zsw_error ranges_shared_device(zsw_context* ctx, const Staged& st, const ResultR
         // reverse pass of striped.rs:355-388 is restricted to; the cells of the reversed matrix that hold the score are then the
         // same with or without the restriction, and if that is one cell too, it is the start under any tie rule.
         const size_t plen = ctx->pseq_len;
-        ScoringDev h_t = ctx->h_sc;
-        for (int r = 0; r < h_t.S; ++r)
-            for (int q = 0; q < h_t.S; ++q) h_t.w[r * h_t.S + q] = ctx->h_sc.w[q * h_t.S + r];
-        if (!ctx->seed_shared_rev.valid) {
-            std::vector<uint8_t> rev(ctx->h_pseq.rbegin(), ctx->h_pseq.rend());
-            ZSW_HIP(ctx, ctx->d_pseq_rev.ensure(plen + 16));
-            ZSW_HIP(ctx, hipMemcpyAsync(ctx->d_pseq_rev.p, rev.data(), plen, hipMemcpyHostToDevice, stream));
-            ZSW_HIP(ctx, hipStreamSynchronize(stream));  // `rev` goes out of scope
-            ZSW_HIP(ctx, seed_index_update(&ctx->seed_shared_rev, h_t, rev.data(), plen));
-        }
+        ze = reversed_seed_index(ctx, &ctx->seed_shared_rev, &ctx->d_pseq_rev, ctx->h_pseq, ctx->h_sc_t, stream);
+        if (ze != ZSW_OK) return ze;
         if (ctx->seed_shared_rev.usable) {
             ZSW_HIP(ctx, ws[SH_UNIQUE_R].ensure((size_t)n + 4));
             ZSW_HIP(ctx, hipMemsetAsync(ws[SH_UNIQUE_R].p, 0, n, stream));
@@ -340,7 +300,7 @@ zsw_error ranges_shared_device(zsw_context* ctx, const Staged& st, const ResultR
             o3.reads_reversed = true;
             ScoreWorkspace w = score_ws(ctx);
             w.seed = &ctx->seed_shared_rev;
-            hipError_t e3 = launch_score(ctx->d_sc_t.as<ScoringDev>(), h_t, brev, st.max_len, ctx->d_pseq_rev.as<uint8_t>(), (uint32_t)plen, rule, o3, w,
+            hipError_t e3 = launch_score(ctx->d_sc_t.as<ScoringDev>(), ctx->h_sc_t, brev, st.max_len, ctx->d_pseq_rev.as<uint8_t>(), (uint32_t)plen, rule, o3, w,
                                          stream, nullptr, 3);
             if (e3 != hipSuccess) return fail(ctx, ZSW_ERR_HIP, "shared ranges: seeded reverse pass", e3);
             ZSW_HIP(ctx, hipMemsetAsync(ws[SH_UCOUNT].p, 0, 4, stream));
@@ -374,20 +334,12 @@ zsw_error run_threepass_shared(zsw_context* ctx, const zsw_batch* reads, const R
                                uint8_t* out_tier, uint32_t* out_inc, uint8_t* out_op, uint64_t ciglet_cap, uint64_t* out_n_ciglets, void* stream_) {
     zsw_error ze = check_shared(ctx);
     if (ze != ZSW_OK) return ze;
-    if (!reads || !out_aln || !out_status || !out_n_ciglets || (ciglet_cap && (!out_inc || !out_op)))
-        return fail(ctx, ZSW_ERR_INVALID_ARGUMENT, "null argument");
     DeviceGuard device_guard(ctx);
     hipStream_t stream = (hipStream_t)stream_;
     SharedStage guard(ctx, true);
     Staged st;
-    {
-        uint32_t dummy_score = 0;
-        uint8_t dummy_status = 0;
-        ze = stage(ctx, reads, stream, false, false, &dummy_score, &dummy_status, nullptr, nullptr, nullptr, &st);
-        if (ze != ZSW_OK) return ze;
-    }
-    *out_n_ciglets = 0;
-    if (reads->n_reads == 0) return ZSW_OK;
+    ze = stage_align(ctx, reads, out_aln, out_status, out_inc, out_op, ciglet_cap, out_n_ciglets, stream, &st);
+    if (ze != ZSW_OK || reads->n_reads == 0) return ze;
     RangesDev rd;
     ze = ranges_shared_device(ctx, st, rule, stream, &rd);
     if (ze != ZSW_OK) return ze;
@@ -400,21 +352,13 @@ zsw_error run_align_shared(zsw_context* ctx, const zsw_batch* reads, const Resul
                            uint64_t* out_n_ciglets, void* stream_) {
     zsw_error ze = check_shared(ctx);
     if (ze != ZSW_OK) return ze;
-    if (!reads || !out_aln || !out_status || !out_n_ciglets || (ciglet_cap && (!out_inc || !out_op)))
-        return fail(ctx, ZSW_ERR_INVALID_ARGUMENT, "null argument");
     DeviceGuard device_guard(ctx);
     hipStream_t stream = (hipStream_t)stream_;
     SharedStage guard(ctx, true);
     Staged st;
-    {
-        uint32_t dummy_score = 0;
-        uint8_t dummy_status = 0;
-        ze = stage(ctx, reads, stream, false, false, &dummy_score, &dummy_status, nullptr, nullptr, nullptr, &st);
-        if (ze != ZSW_OK) return ze;
-    }
-    const uint32_t n = (uint32_t)reads->n_reads;
-    *out_n_ciglets = 0;
-    if (n == 0) return ZSW_OK;
+    ze = stage_align(ctx, reads, out_aln, out_status, out_inc, out_op, ciglet_cap, out_n_ciglets, stream, &st);
+    const uint32_t n = st.b.n_reads;
+    if (ze != ZSW_OK || n == 0) return ze;
     const bool host = reads->mem == ZSW_MEM_HOST;
     DevBuf* ws = ctx->a_ws;
     ZSW_HIP(ctx, ws[WS_SCORE].ensure((size_t)n * 4 + 4));
@@ -427,9 +371,6 @@ zsw_error run_align_shared(zsw_context* ctx, const zsw_batch* reads, const Resul
     so.status = ws[WS_STATUS].as<uint8_t>();
     so.tier = ws[WS_TIER].as<uint8_t>();
     so.ref_end = ws[WS_REND].as<uint32_t>();
-    so.query_end = nullptr;
-    so.fb_list = nullptr;
-    so.fb_count = nullptr;
     // Certificate mode, as in the read-as-profile role (zsw_capi.hip run_align; tests/models/align_gapless_cert.cpp and
     // align_onegap_cert.cpp check the swapped roles too): the first pass is the whole of sw_simd_score_ranges in this role, whose two
     // seeded passes tell which reads have both maxima in one cell each; a read whose only optimal alignment is gapless or has one gap
@@ -438,16 +379,7 @@ zsw_error run_align_shared(zsw_context* ctx, const zsw_batch* reads, const Resul
     const uint8_t* pass2_status = nullptr;
     const bool certify = !(ctx->flags() & ZSW_DEBUG_ALIGN_NO_CERTIFICATE) && ctx->h_sc.gap_open > 0;
     if (certify) {
-        const uint32_t MAXC0 = 32;
         ZSW_HIP(ctx, ws[WS_CERT_OK].ensure((size_t)n + 4));
-        ZSW_HIP(ctx, ws[WS_CERT_DONE].ensure((size_t)n + 4));
-        ZSW_HIP(ctx, ws[WS_CERT_STATUS].ensure((size_t)n + 4));
-        ZSW_HIP(ctx, ws[WS_ALN].ensure((size_t)n * sizeof(zsw_alignment)));
-        ZSW_HIP(ctx, ws[WS_CIGSTART].ensure((size_t)n * 8));
-        ZSW_HIP(ctx, ws[WS_CIGRAW].ensure((size_t)n * 4));
-        ZSW_HIP(ctx, ws[WS_CIG].ensure((size_t)n * MAXC0 * 4));
-        ZSW_HIP(ctx, ws[WS_FBLIST].ensure((size_t)n * 4 + 4));
-        ZSW_HIP(ctx, ws[WS_FBCOUNT].ensure(16));
         RangesDev rd;
         ze = ranges_shared_device(ctx, st, rule, stream, &rd, ws[WS_CERT_OK].as<uint8_t>());
         ctx->timer.end(stream);
@@ -456,58 +388,9 @@ zsw_error run_align_shared(zsw_context* ctx, const zsw_batch* reads, const Resul
         so.status = rd.status;
         so.tier = rd.tier;
         so.ref_end = rd.re;
-        int maxw = 0;
-        for (int i = 0; i < ctx->h_sc.S * ctx->h_sc.S; ++i) maxw = std::max(maxw, (int)ctx->h_sc.w[i]);
-        ThreePassArgs a;
-        a.b = st.b;
-        a.ref = nullptr;
-        a.ref_len = 0;
-        a.pseq = ctx->d_pseq.as<uint8_t>();  // three_pass.rs:21-26 with the roles of this call: `reference` = read i
-        a.pseq_len = (uint32_t)ctx->pseq_len;
-        a.sc = ctx->d_sc.as<ScoringDev>();
-        a.score = rd.score;
-        a.rs = rd.rs;
-        a.re = rd.re;
-        a.qs = rd.qs;
-        a.qe = rd.qe;
-        a.status = rd.status;
-        a.list = nullptr;
-        a.list_count = nullptr;
-        a.dp_list = nullptr;
-        a.dp_count = nullptr;
-        a.dp_need_max = nullptr;
-        a.scratch = nullptr;
-        a.slots = 0;
-        a.slot_bytes = 0;
-        a.cig = ws[WS_CIG].as<uint32_t>();
-        a.maxc = MAXC0;
-        a.pool_base = 0;
-        a.by_item = 0;
-        a.cig_start = ws[WS_CIGSTART].as<uint64_t>();
-        a.cig_raw = ws[WS_CIGRAW].as<uint32_t>();
-        a.aln = ws[WS_ALN].as<zsw_alignment>();
-        a.fb_list = ws[WS_FBLIST].as<uint32_t>();
-        a.fb_count = ws[WS_FBCOUNT].as<uint32_t>();
-        a.invert = invert;
-        a.cert_ok = ws[WS_CERT_OK].as<uint8_t>();
-        a.cert_done = ws[WS_CERT_DONE].as<uint8_t>();
-        a.cert_maxw = maxw;
-        a.cert_go = ctx->h_sc.gap_open;
-        a.cert_ge = ctx->h_sc.gap_extend;
-        // reads that need the sweeps over their two-run alternatives are listed and take a second, dense launch (ThreePassArgs::sweep_list)
-        ZSW_HIP(ctx, ws[WS_ITEMS].ensure((size_t)n * 4 + 4));
-        ZSW_HIP(ctx, hipMemsetAsync(ws[WS_FBCOUNT].as<uint32_t>() + 2, 0, 4, stream));
-        a.sweep_list = ws[WS_ITEMS].as<uint32_t>();
-        a.sweep_count = ws[WS_FBCOUNT].as<uint32_t>() + 2;
-        hipError_t ce = launch_threepass(a, std::min<uint32_t>((n + 63) / 64, 65536u), stream);
-        if (ce != hipSuccess) return fail(ctx, ZSW_ERR_HIP, "shared align: certificate pass", ce);
-        a.list = a.sweep_list;
-        a.list_count = a.sweep_count;
-        a.sweep_pass = true;
-        ce = launch_threepass(a, std::min<uint32_t>((n / 4 + 63) / 64 + 1, 16384u), stream);
-        if (ce != hipSuccess) return fail(ctx, ZSW_ERR_HIP, "shared align: certificate pass (sweeps)", ce);
-        ZSW_HIP(ctx, launch_cert_status(n, rd.status, ws[WS_CERT_DONE].as<uint8_t>(), ws[WS_CERT_STATUS].as<uint8_t>(), stream));
-        pass2_status = ws[WS_CERT_STATUS].as<uint8_t>();
+        // three_pass.rs:21-26 with the roles of this call: `reference` = read i
+        ze = certificate_pass(ctx, st, rd, ws[WS_CERT_OK].as<uint8_t>(), ctx->d_pseq.as<uint8_t>(), (uint32_t)ctx->pseq_len, invert, stream, &pass2_status);
+        if (ze != ZSW_OK) return ze;
     } else {
         ze = shared_ends_device(ctx, st, rule, so, stream);
         if (ze != ZSW_OK) return ze;
@@ -552,13 +435,10 @@ zsw_error run_align_shared(zsw_context* ctx, const zsw_batch* reads, const Resul
         if (he != hipSuccess) return fail(ctx, ZSW_ERR_HIP, "shared align pass 2", he);
         return ZSW_OK;
     };
-    bool seen[65] = {false};
     for (const Tier& t : tiers) {
-        if (rule.n_tiers == 1 ? t.code != rule.tier_code[0] : false) continue;
         bool in_rule = false;
         for (int k = 0; k < rule.n_tiers; ++k) in_rule = in_rule || rule.tier_code[k] == t.code;
         if (!in_rule) continue;
-        (void)seen;
         uint32_t* d_list = ws[WS_ITEMS].as<uint32_t>();
         uint32_t* d_count = ctx->sh_ws[SH_LIST].as<uint32_t>();
         ZSW_HIP(ctx, hipMemsetAsync(d_count, 0, 4, stream));
@@ -626,57 +506,45 @@ zsw_error zsw_set_profile_sequence(zsw_context* ctx, const uint8_t* sequence, si
 
 zsw_error zsw_score_shared_batch(zsw_context* ctx, const zsw_batch* reads, zsw_int_type int_type, int lanes, uint32_t* out_score,
                                  uint8_t* out_status, void* stream) {
-    if (!ctx) return ZSW_ERR_INVALID_ARGUMENT;
-    if (!valid_lanes(lanes)) return fail(ctx, ZSW_ERR_INVALID_ARGUMENT, "lanes must be a power of two in 2..64");
     ResultRule rule;
-    if (!rule_direct(int_type, ctx->bias, &rule)) return fail(ctx, ZSW_ERR_INVALID_ARGUMENT, "bad int_type");
+    if (zsw_error ze = rule_direct(ctx, int_type, lanes, &rule); ze != ZSW_OK) return ze;
     return run_score_shared(ctx, reads, rule, out_score, out_status, nullptr, stream);
 }
 
 zsw_error zsw_score_shared_batch_from(zsw_context* ctx, const zsw_batch* reads, int from_width, int preset_bits, uint32_t* out_score,
                                       uint8_t* out_status, uint8_t* out_tier, void* stream) {
-    if (!ctx) return ZSW_ERR_INVALID_ARGUMENT;
-    if (preset_bits != 128 && preset_bits != 256 && preset_bits != 512) return fail(ctx, ZSW_ERR_INVALID_ARGUMENT, "preset_bits");
     ResultRule rule;
-    if (!rule_cascade(from_width, &rule)) return fail(ctx, ZSW_ERR_INVALID_ARGUMENT, "from_width");
+    if (zsw_error ze = rule_cascade(ctx, from_width, preset_bits, &rule); ze != ZSW_OK) return ze;
     return run_score_shared(ctx, reads, rule, out_score, out_status, out_tier, stream);
 }
 
 zsw_error zsw_score_ends_shared_batch(zsw_context* ctx, const zsw_batch* reads, zsw_int_type int_type, int lanes, uint32_t* out_score,
                                       uint32_t* out_ref_end, uint32_t* out_query_end, uint8_t* out_status, void* stream) {
-    if (!ctx) return ZSW_ERR_INVALID_ARGUMENT;
-    if (!valid_lanes(lanes)) return fail(ctx, ZSW_ERR_INVALID_ARGUMENT, "lanes must be a power of two in 2..64");
     ResultRule rule;
-    if (!rule_direct(int_type, ctx->bias, &rule)) return fail(ctx, ZSW_ERR_INVALID_ARGUMENT, "bad int_type");
+    if (zsw_error ze = rule_direct(ctx, int_type, lanes, &rule); ze != ZSW_OK) return ze;
     return run_ends_shared(ctx, reads, rule, out_score, out_ref_end, out_query_end, out_status, stream);
 }
 
 zsw_error zsw_score_ranges_shared_batch(zsw_context* ctx, const zsw_batch* reads, zsw_int_type int_type, int lanes, uint32_t* out_score,
                                         uint32_t* out_ref_start, uint32_t* out_ref_end, uint32_t* out_query_start, uint32_t* out_query_end,
                                         uint8_t* out_status, void* stream) {
-    if (!ctx) return ZSW_ERR_INVALID_ARGUMENT;
-    if (!valid_lanes(lanes)) return fail(ctx, ZSW_ERR_INVALID_ARGUMENT, "lanes must be a power of two in 2..64");
     ResultRule rule;
-    if (!rule_direct(int_type, ctx->bias, &rule)) return fail(ctx, ZSW_ERR_INVALID_ARGUMENT, "bad int_type");
+    if (zsw_error ze = rule_direct(ctx, int_type, lanes, &rule); ze != ZSW_OK) return ze;
     return run_ranges_shared(ctx, reads, rule, out_score, out_ref_start, out_ref_end, out_query_start, out_query_end, out_status, nullptr, stream);
 }
 
 zsw_error zsw_score_ranges_shared_batch_from(zsw_context* ctx, const zsw_batch* reads, int from_width, int preset_bits, uint32_t* out_score,
                                              uint32_t* out_ref_start, uint32_t* out_ref_end, uint32_t* out_query_start, uint32_t* out_query_end,
                                              uint8_t* out_status, uint8_t* out_tier, void* stream) {
-    if (!ctx) return ZSW_ERR_INVALID_ARGUMENT;
-    if (preset_bits != 128 && preset_bits != 256 && preset_bits != 512) return fail(ctx, ZSW_ERR_INVALID_ARGUMENT, "preset_bits");
     ResultRule rule;
-    if (!rule_cascade(from_width, &rule)) return fail(ctx, ZSW_ERR_INVALID_ARGUMENT, "from_width");
+    if (zsw_error ze = rule_cascade(ctx, from_width, preset_bits, &rule); ze != ZSW_OK) return ze;
     return run_ranges_shared(ctx, reads, rule, out_score, out_ref_start, out_ref_end, out_query_start, out_query_end, out_status, out_tier, stream);
 }
 
 zsw_error zsw_align_shared_batch(zsw_context* ctx, const zsw_batch* reads, zsw_int_type int_type, int lanes, int invert, zsw_alignment* out_aln,
                                  uint8_t* out_status, uint32_t* out_inc, uint8_t* out_op, uint64_t ciglet_cap, uint64_t* out_n_ciglets, void* stream) {
-    if (!ctx) return ZSW_ERR_INVALID_ARGUMENT;
-    if (!valid_lanes(lanes)) return fail(ctx, ZSW_ERR_INVALID_ARGUMENT, "lanes must be a power of two in 2..64");
     ResultRule rule;
-    if (!rule_direct(int_type, ctx->bias, &rule)) return fail(ctx, ZSW_ERR_INVALID_ARGUMENT, "bad int_type");
+    if (zsw_error ze = rule_direct(ctx, int_type, lanes, &rule); ze != ZSW_OK) return ze;
     return run_align_shared(ctx, reads, rule, lanes, lanes, lanes, invert, out_aln, out_status, nullptr, out_inc, out_op, ciglet_cap, out_n_ciglets,
                             stream);
 }
@@ -684,30 +552,24 @@ zsw_error zsw_align_shared_batch(zsw_context* ctx, const zsw_batch* reads, zsw_i
 zsw_error zsw_align_shared_batch_from(zsw_context* ctx, const zsw_batch* reads, int from_width, int preset_bits, int invert, zsw_alignment* out_aln,
                                       uint8_t* out_status, uint8_t* out_tier, uint32_t* out_inc, uint8_t* out_op, uint64_t ciglet_cap,
                                       uint64_t* out_n_ciglets, void* stream) {
-    if (!ctx) return ZSW_ERR_INVALID_ARGUMENT;
-    if (preset_bits != 128 && preset_bits != 256 && preset_bits != 512) return fail(ctx, ZSW_ERR_INVALID_ARGUMENT, "preset_bits");
     ResultRule rule;
-    if (!rule_cascade(from_width, &rule)) return fail(ctx, ZSW_ERR_INVALID_ARGUMENT, "from_width");
+    if (zsw_error ze = rule_cascade(ctx, from_width, preset_bits, &rule); ze != ZSW_OK) return ze;
     return run_align_shared(ctx, reads, rule, preset_bits / 8, preset_bits / 16, preset_bits / 32, invert, out_aln, out_status, out_tier, out_inc,
                             out_op, ciglet_cap, out_n_ciglets, stream);
 }
 
 zsw_error zsw_align_3pass_shared_batch(zsw_context* ctx, const zsw_batch* reads, zsw_int_type int_type, int lanes, int invert, zsw_alignment* out_aln,
                                        uint8_t* out_status, uint32_t* out_inc, uint8_t* out_op, uint64_t ciglet_cap, uint64_t* out_n_ciglets, void* stream) {
-    if (!ctx) return ZSW_ERR_INVALID_ARGUMENT;
-    if (!valid_lanes(lanes)) return fail(ctx, ZSW_ERR_INVALID_ARGUMENT, "lanes must be a power of two in 2..64");
     ResultRule rule;
-    if (!rule_direct(int_type, ctx->bias, &rule)) return fail(ctx, ZSW_ERR_INVALID_ARGUMENT, "bad int_type");
+    if (zsw_error ze = rule_direct(ctx, int_type, lanes, &rule); ze != ZSW_OK) return ze;
     return run_threepass_shared(ctx, reads, rule, invert, out_aln, out_status, nullptr, out_inc, out_op, ciglet_cap, out_n_ciglets, stream);
 }
 
 zsw_error zsw_align_3pass_shared_batch_from(zsw_context* ctx, const zsw_batch* reads, int from_width, int preset_bits, int invert, zsw_alignment* out_aln,
                                             uint8_t* out_status, uint8_t* out_tier, uint32_t* out_inc, uint8_t* out_op, uint64_t ciglet_cap,
                                             uint64_t* out_n_ciglets, void* stream) {
-    if (!ctx) return ZSW_ERR_INVALID_ARGUMENT;
-    if (preset_bits != 128 && preset_bits != 256 && preset_bits != 512) return fail(ctx, ZSW_ERR_INVALID_ARGUMENT, "preset_bits");
     ResultRule rule;
-    if (!rule_cascade(from_width, &rule)) return fail(ctx, ZSW_ERR_INVALID_ARGUMENT, "from_width");
+    if (zsw_error ze = rule_cascade(ctx, from_width, preset_bits, &rule); ze != ZSW_OK) return ze;
     return run_threepass_shared(ctx, reads, rule, invert, out_aln, out_status, out_tier, out_inc, out_op, ciglet_cap, out_n_ciglets, stream);
 }
 

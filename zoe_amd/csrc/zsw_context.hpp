@@ -45,6 +45,7 @@ struct zsw_context {
     uint32_t cu_count = 256;
     bool scoring_set = false, reference_set = false;
     zsw::ScoringDev h_sc{};
+    zsw::ScoringDev h_sc_t{};  // h_sc with the matrix transposed (d_sc_t on the device): the shared-profile role's role-swapped passes
     int bias = 0;
     zsw::DevBuf d_sc, d_ref, d_fb_list, d_fb_count, d_scratch, d_maxlen, d_bucket_items, d_bucket_counts, d_tile_buf, d_tile_state;
     zsw::DevBuf d_prune, d_prune_list, d_prune_count;  // column-pruned score pass; the worklist and its counters also serve the seeded pass
@@ -142,32 +143,42 @@ inline bool valid_lanes(int lanes) { return lanes == 2 || lanes == 4 || lanes ==
 
 inline uint64_t signed_thr(int bits) { return bits == 8 ? 255ull : bits == 16 ? 65535ull : 4294967295ull; }
 
+// The arguments of a public call with one <T, N>: its result rule, or the error the call returns.
 // score_to_maybe_aligned (striped.rs:610-633) as a threshold on the true score:
 //   signed T  : Overflowed  <=>  best >= T::MAX            <=>  s >= 2^bits - 1
 //   unsigned T: Overflowed  <=>  best + bias + 1 > T::MAX  <=>  s >= T::MAX - bias
-inline bool rule_direct(zsw_int_type t, int bias, ResultRule* r) {
+inline zsw_error rule_direct(zsw_context* ctx, zsw_int_type t, int lanes, ResultRule* r) {
+    if (!ctx) return ZSW_ERR_INVALID_ARGUMENT;
+    if (!valid_lanes(lanes)) return fail(ctx, ZSW_ERR_INVALID_ARGUMENT, "lanes must be a power of two in 2..64");
+    const int bias = ctx->bias;
     r->n_tiers = 1;
     switch (t) {
-        case ZSW_I8: r->thr[0] = signed_thr(8); r->tier_code[0] = 8; return true;
-        case ZSW_I16: r->thr[0] = signed_thr(16); r->tier_code[0] = 16; return true;
-        case ZSW_I32: r->thr[0] = signed_thr(32); r->tier_code[0] = 32; return true;
-        case ZSW_U8: r->thr[0] = 255ull - (uint64_t)bias; r->tier_code[0] = 8; return bias < 255;
-        case ZSW_U16: r->thr[0] = 65535ull - (uint64_t)bias; r->tier_code[0] = 16; return true;
-        case ZSW_U32: r->thr[0] = 4294967295ull - (uint64_t)bias; r->tier_code[0] = 32; return true;
+        case ZSW_I8: r->thr[0] = signed_thr(8); r->tier_code[0] = 8; return ZSW_OK;
+        case ZSW_I16: r->thr[0] = signed_thr(16); r->tier_code[0] = 16; return ZSW_OK;
+        case ZSW_I32: r->thr[0] = signed_thr(32); r->tier_code[0] = 32; return ZSW_OK;
+        case ZSW_U8:
+            r->thr[0] = 255ull - (uint64_t)bias;
+            r->tier_code[0] = 8;
+            if (bias < 255) return ZSW_OK;
+            break;
+        case ZSW_U16: r->thr[0] = 65535ull - (uint64_t)bias; r->tier_code[0] = 16; return ZSW_OK;
+        case ZSW_U32: r->thr[0] = 4294967295ull - (uint64_t)bias; r->tier_code[0] = 32; return ZSW_OK;
     }
-    return false;
+    return fail(ctx, ZSW_ERR_INVALID_ARGUMENT, "bad int_type");
 }
 
-// or_else_overflowed chain (profile_set.rs:71-107): i8 -> i16 -> i32 from `from_width`
-inline bool rule_cascade(int from_width, ResultRule* r) {
-    if (from_width != 8 && from_width != 16 && from_width != 32) return false;
+// The arguments of a public _from call: the or_else_overflowed chain (profile_set.rs:71-107), i8 -> i16 -> i32 from `from_width`
+inline zsw_error rule_cascade(zsw_context* ctx, int from_width, int preset_bits, ResultRule* r) {
+    if (!ctx) return ZSW_ERR_INVALID_ARGUMENT;
+    if (preset_bits != 128 && preset_bits != 256 && preset_bits != 512) return fail(ctx, ZSW_ERR_INVALID_ARGUMENT, "preset_bits");
+    if (from_width != 8 && from_width != 16 && from_width != 32) return fail(ctx, ZSW_ERR_INVALID_ARGUMENT, "from_width");
     r->n_tiers = 0;
     for (int w = from_width; w <= 32; w *= 2) {
         r->thr[r->n_tiers] = signed_thr(w);
         r->tier_code[r->n_tiers] = (uint8_t)w;
         ++r->n_tiers;
     }
-    return true;
+    return ZSW_OK;
 }
 
 struct Staged {
@@ -183,6 +194,11 @@ struct Staged {
 // zsw_capi.hip
 zsw_error stage(zsw_context* ctx, const zsw_batch* reads, hipStream_t stream, bool want_tier, bool want_ends, uint32_t* out_score,
                 uint8_t* out_status, uint8_t* out_tier, uint32_t* out_rend, uint32_t* out_qend, Staged* st, bool defer_bases_copy = false);
+// stage() for the calls whose results stay in library workspace (ranges, alignments): no score / status arrays of the caller
+zsw_error stage_reads(zsw_context* ctx, const zsw_batch* reads, hipStream_t stream, Staged* st);
+// prologue of the alignment calls: null checks, stage_reads(), *out_n_ciglets = 0 (the caller returns at once for an empty batch)
+zsw_error stage_align(zsw_context* ctx, const zsw_batch* reads, zsw_alignment* out_aln, uint8_t* out_status, uint32_t* out_inc, uint8_t* out_op,
+                      uint64_t ciglet_cap, uint64_t* out_n_ciglets, hipStream_t stream, Staged* st);
 ScoreWorkspace score_ws(zsw_context* ctx);
 zsw_error unstage(zsw_context* ctx, const zsw_batch* reads, hipStream_t stream, const Staged& st, uint32_t* out_score, uint8_t* out_status,
                   uint8_t* out_tier, uint32_t* out_rend, uint32_t* out_qend);
@@ -198,13 +214,21 @@ struct RangesDev {  // device arrays of sw_simd_score_ranges for every read (lib
     uint32_t *score, *rs, *re, *qs, *qe;
     uint8_t *status, *tier;
 };
+// the ranges to the caller's arrays (a host batch: the call returns once they are there)
+zsw_error copy_ranges_out(zsw_context* ctx, const RangesDev& rd, uint32_t n, bool host, uint32_t* out_score, uint32_t* out_rs, uint32_t* out_re,
+                          uint32_t* out_qs, uint32_t* out_qe, uint8_t* out_status, uint8_t* out_tier, hipStream_t stream);
+// the seed index of a reversed sequence (`seq` back to front, uploaded to `d_rev`) under `sc`, unless it is valid already
+zsw_error reversed_seed_index(zsw_context* ctx, SeedIndex* index, DevBuf* d_rev, const std::vector<uint8_t>& seq, const ScoringDev& sc, hipStream_t stream);
 // sw_align_3pass's third pass (zsw_threepass.hip) over ranges that are already on the device, results to the caller's arrays; the
 // caller has opened ctx->timer's interval. pseq: non-null = the shared-profile role (ThreePassArgs::pseq).
 zsw_error threepass_third_pass(zsw_context* ctx, const Staged& st, const RangesDev& rd, const uint8_t* pseq, uint32_t pseq_len, bool host, int invert,
                                zsw_alignment* out_aln, uint8_t* out_status, uint8_t* out_tier, uint32_t* out_inc, uint8_t* out_op, uint64_t ciglet_cap,
                                uint64_t* out_n_ciglets, hipStream_t stream);
-// statuses as a literal second pass sees them: reads whose alignment a certificate pass wrote (done[i]) do not take part
-hipError_t launch_cert_status(uint32_t n, const uint8_t* status, const uint8_t* done, uint8_t* out, hipStream_t stream);
+// The certificate pass of sw_simd_align in both roles (tests/models/align_gapless_cert.cpp, align_onegap_cert.cpp): the classify
+// launches of zsw_threepass.hip write the alignment of every read of `rd` they can certify (settled[i]: both maxima of read i sit in
+// one cell each). *pass2_status: the statuses the literal second pass sees — a certified read does not take part. pseq: as above.
+zsw_error certificate_pass(zsw_context* ctx, const Staged& st, const RangesDev& rd, const uint8_t* settled, const uint8_t* pseq, uint32_t pseq_len,
+                           int invert, hipStream_t stream, const uint8_t** pass2_status);
 // zsw_capi_shared.hip: the settlement of a reversed seeded pass (a read is
 // done if both maxima sit in one cell each and the scores agree; the others are listed for the exact reverse kernel)
 hipError_t launch_settle_reverse(const BatchDev& b, uint32_t n, uint32_t other_len, const uint8_t* uf, const uint8_t* ur, const uint32_t* fscore,

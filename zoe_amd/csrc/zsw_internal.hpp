@@ -57,13 +57,13 @@ struct BatchDev {
 };
 
 struct ScoreOut {
-    uint32_t* score;
-    uint8_t* status;
-    uint8_t* tier;      // may be null
-    uint32_t* ref_end;  // ends kernels only (may be null)
-    uint32_t* query_end;
-    uint32_t* fb_list;  // reads that need the exact 32-bit kernel
-    uint32_t* fb_count;
+    uint32_t* score = nullptr;
+    uint8_t* status = nullptr;
+    uint8_t* tier = nullptr;       // may be null
+    uint32_t* ref_end = nullptr;   // ends kernels only (may be null)
+    uint32_t* query_end = nullptr;
+    uint32_t* fb_list = nullptr;   // reads that need the exact 32-bit kernel
+    uint32_t* fb_count = nullptr;
     // optional (alignment's first pass): per read, the row from which the second pass may start with a zero state
     // (seed_safe_start, zsw_seed.hpp); the caller presets 0xffffffff = no certificate, the seeded window kernel fills the rest
     uint32_t* safe_row = nullptr;
