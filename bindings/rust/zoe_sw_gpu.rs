@@ -143,6 +143,7 @@ unsafe extern "C" {
     fn zsw_timing_read_window(ctx: *mut ZswContext, seconds: *mut f64, launches: *mut u64) -> i32;
     fn zsw_debug_set(ctx: *mut ZswContext, flags: u32) -> i32;
     fn zsw_debug_band_records(ctx: *mut ZswContext, records: *mut i32) -> i32;
+    fn zsw_debug_cert_records(ctx: *mut ZswContext, records: *mut i32) -> i32;
     fn zsw_prune_rescored(ctx: *mut ZswContext, out_reads: *mut u64) -> i32;
     fn zsw_set_option(ctx: *mut ZswContext, option: i32, value: i64) -> i32;
 }
@@ -773,6 +774,15 @@ impl GpuContext {
     /// `records` must be null or device memory for `8 * n_reads` `i32` that outlives the following calls.
     pub unsafe fn debug_band_records(&self, records: *mut i32) -> Result<(), GpuError> {
         self.check(zsw_debug_band_records(self.raw, records), 0, 0)
+    }
+
+    /// `zsw_debug_cert_records`: tests only — the certificate pass of the alignment calls reports, per read, its verdict
+    /// (4 `i32` per read in device memory: verdict class, deciding parameter, tie count, decided by the sweep launch; null = off).
+    ///
+    /// # Safety
+    /// `records` must be null or device memory for `4 * n_reads` `i32` that outlives the following calls.
+    pub unsafe fn debug_cert_records(&self, records: *mut i32) -> Result<(), GpuError> {
+        self.check(zsw_debug_cert_records(self.raw, records), 0, 0)
     }
 
     /// `zsw_set_option(ZSW_OPTION_EXACT_PRUNING)`: the exact column-pruned first pass (same results for every input,

@@ -390,6 +390,18 @@ zsw_error zsw_debug_set(zsw_context* ctx, uint32_t flags);
  * of the following calls, NULL = off (the default). */
 zsw_error zsw_debug_band_records(zsw_context* ctx, int32_t* records);
 
+/* Tests only (tests/test_gpu_cert.py): the certificate pass of the alignment calls (zsw_threepass.hip, classify and sweep launches;
+ * the decision is zoe_amd/csrc/zsw_cert.hpp) writes, for every read with an alignment, four int32 into records[4 * read]:
+ * [0] the verdict class — 0 a maximum not in one cell, 1 gapless certified, 2 one gap certified, 3 rejected: the diagonal does not
+ * add up to the score, 4 rejected: the potential does not rule out three or more gap runs (one gap: or fewer than two pairs, or
+ * gap_extend == 0), 5 rejected: an alignment with two gap runs reaches the score, 6 rejected: no single or adjacent set of one-run
+ * placements reaches exactly the score, 7 deferred to the sweep launch (final only if that launch did not run) —; [1] the deciding
+ * parameter — class 1: the run lengths k swept; 2 and 6: the last best placement (pairs before the run); 5: the first run's signed
+ * length (a deletion counts +); 3: the diagonal's sum —; [2] one gap (2 and 6): the placements that reach the best score;
+ * [3] 1 = decided by the sweep launch. Reads without an alignment and calls outside certificate mode leave their records alone.
+ * records: device memory for 4 int32 per read of the following calls, NULL = off (the default). Results do not change. */
+zsw_error zsw_debug_cert_records(zsw_context* ctx, int32_t* records);
+
 /* Reads of the context's last score call that the seeded (or column-pruned) pass handed back — no anchor, or a bound check
  * failed — and that were scored over all their cells (0 if the call did not take such a pass). Synchronises the device.
  * Diagnostics for tests and bench.py. */

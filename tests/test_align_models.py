@@ -1,7 +1,8 @@
 """CPU checks of the alignment kernel's arithmetic (no GPU): the closed form of Zoe's lazy-F loop (striped.rs:528-553)
 and the packed row update the gfx950 kernel is compiled from (zoe_amd/csrc/zsw_align_pk.hpp), both compared cell by
-cell with the oracle's literal restatement of sw_simd_align; and the bound checks of the column-pruned first pass
-(zoe_amd/csrc/zsw_score_prune.hip) against the full DP matrix."""
+cell with the oracle's literal restatement of sw_simd_align; the bound checks of the column-pruned first pass
+(zoe_amd/csrc/zsw_score_prune.hip) against the full DP matrix; and the alignment certificates (zoe_amd/csrc/zsw_cert.hpp) against
+counting Gotoh and the literal sw_simd_align, with mutants of the header that the models must catch."""
 import os
 import subprocess
 
@@ -109,28 +110,73 @@ def test_reversed_pass_over_whole_sequences_model(tmp_path, seed):
 
 @pytest.mark.parametrize("seed", [20261005, 8])
 def test_gapless_alignment_certificate_model(tmp_path, seed):
-    """The certificate that lets sw_simd_align's second pass be skipped (zsw_capi.hip run_align, zsw_threepass.hip classify pass in
-    certificate mode): both maxima in one cell each, ranges of equal length whose diagonal adds up to the score, and the score beyond
-    maxw * (n - 1) - 2 * gap_open. The oracle's literal sw_simd_align (striped.rs:449-598 restated) must then return the gapless
-    diagonal at N = 2 .. 64 in 16-bit lanes and N = 16, 32 in 8-bit lanes; ten scoring schemes, repeats, homopolymer runs, N, junk
-    ends, reads with indels (never certified). (Dropping the score condition produces a counter-example within 3,000 iterations.)"""
-    out = subprocess.run([_build(tmp_path, "align_gapless_cert"), "500", str(seed)], capture_output=True, text=True, timeout=900)
+    """The gapless certificate that lets sw_simd_align's second pass be skipped (zoe_amd/csrc/zsw_cert.hpp, compiled for the host as
+    the classify pass of zsw_threepass.hip compiles it, with its split into a classify and a sweep launch): both maxima in one cell
+    each, ranges of equal length n whose diagonal adds up to the score S, S > maxw * (n - 1) - 3 * gap_open (three or more gap runs),
+    and for every run length k with maxw * (n - k) - 2 * gap_open - 2 * (k - 1) * gap_extend >= S the best placement of an insertion and
+    a deletion of k below S (one sweep per k and order). Every certificate is checked against a Gotoh that counts the optimal
+    alignments between the corners (exactly one) and against the oracle's literal sw_simd_align at N = 2 .. 64 in i16 lanes, N = 16,
+    32 in i8 and u8 lanes, N = 4, 16 in u16 lanes, N = 8 in i32 and u32 lanes, and with the roles swapped; sixteen schemes (an
+    asymmetric matrix, three letters, gap_extend 0 and == gap_open among them), repeats, homopolymer runs, N, junk ends, indel pairs
+    of the same length a few bases apart, substitution counts around the potential's threshold."""
+    out = subprocess.run([_build(tmp_path, "align_gapless_cert"), "250", str(seed)], capture_output=True, text=True, timeout=900)
     assert out.returncode == 0, out.stdout + out.stderr
     assert "align_gapless_cert OK" in out.stdout
 
 
 @pytest.mark.parametrize("seed", [20261005, 6])
 def test_one_gap_alignment_certificate_model(tmp_path, seed):
-    """The second certificate of run_align (zsw_threepass.hip, classify pass in certificate mode): both maxima in one cell each,
-    ranges that differ by g, one placement of ONE gap run of g between the corners — or a run of adjacent placements, of which the
-    walk from the end takes the last — reaches the score (one sweep over the prefix sums of the two diagonals), and the score lies beyond maxw * min(rlen, qlen) - 2 * gap_open - max(g - 2, 0) * gap_extend,
-    which no alignment with two gap runs reaches. The oracle's literal sw_simd_align must then return [p M][g D|I][m - p M] at
-    N = 2 .. 64 in 16-bit lanes and N = 16, 32 in 8-bit lanes; ten schemes, gaps of 1-5 inside repeats and homopolymer runs (tied
-    placements), reads with a second gap. (Taking any tied placement but the last, or dropping the two-run bound, produces a
-    counter-example within 3,000 iterations.)"""
-    out = subprocess.run([_build(tmp_path, "align_onegap_cert"), "500", str(seed)], capture_output=True, text=True, timeout=900)
+    """The one-gap certificate (zsw_cert.hpp as above): both maxima in one cell each, ranges that differ by g, m = min(rlen, qlen) >= 2,
+    gap_extend > 0, S > maxw * m - 3 * gap_open - max(g - 3, 0) * gap_extend (three or more runs), one placement of ONE gap run of g
+    between the corners — or a run of adjacent placements, of which the walk from the end takes the last — reaches exactly S (one sweep
+    over the prefix sums of the two diagonals), and for every pair of runs (ra, rlen - qlen - ra) with |ra| <= amax that the potential
+    does not rule out the best placement stays below S. Every certificate is checked against a Gotoh that counts the optimal alignments
+    between the corners (exactly the tied placements) and against the oracle's literal sw_simd_align at the widths above and with the
+    roles swapped; sixteen schemes, gaps of 1-5 inside repeats and homopolymer runs (tied placements), second indels a few bases away
+    (two runs at exactly S) and farther away (around amax)."""
+    out = subprocess.run([_build(tmp_path, "align_onegap_cert"), "250", str(seed)], capture_output=True, text=True, timeout=900)
     assert out.returncode == 0, out.stdout + out.stderr
     assert "align_onegap_cert OK" in out.stdout
+
+
+# One textual change each to zsw_cert.hpp (the target text occurs exactly once), the model that must then fail, and its seed.
+# (amax one smaller is provably harmless: a pair of runs within reach of S has |ra| <= (X + g) / 2, and amax carries a margin of one.)
+CERT_MUTANTS = [
+    ("the gapless sweep's verdict ignored", "                if (cert_gapless_two_runs(wt, rlen, k, dir, c)) {",
+     "                if (false && cert_gapless_two_runs(wt, rlen, k, dir, c)) {", "align_gapless_cert", 20261005),
+    ("deferred one-gap reads certified without the sweep launch",
+     "            r.verdict = CERT_DEFERRED;\n            r.deferred = true;\n            return r;\n        }\n        if (cert_one",
+     "            r.verdict = CERT_ONE_GAP;\n            return r;\n        }\n        if (cert_one", "align_onegap_cert", 20261005),
+    ("the first tied placement instead of the last", "    r.param = (int32_t)best_p;", "    r.param = (int32_t)first_p;",
+     "align_onegap_cert", 20261005),
+    (">= S becomes > S in the one-gap two-run rejection", "    return pzM - cost + best_alt >= S;", "    return pzM - cost + best_alt > S;",
+     "align_onegap_cert", 20261005),
+    (">= S becomes > S in the gapless two-run rejection", "c.ge * ((long long)k - 1) >= 0;", "c.ge * ((long long)k - 1) > 0;",
+     "align_gapless_cert", 20261005),
+    ("amax two smaller", "(X + g) / 2 + 1 : 0", "(X + g) / 2 - 1 : 0", "align_onegap_cert", 20261005),
+    ("3 * gap_open becomes 2 * gap_open in the gapless three-run potential",
+     "    return (long long)score > c.maxw * ((long long)n - 1) - 3ll * c.go;",
+     "    return (long long)score > c.maxw * ((long long)n - 1) - 2ll * c.go;", "align_gapless_cert", 20261005),
+]
+
+
+@pytest.mark.parametrize("name,old,new,model,seed", CERT_MUTANTS, ids=[m[0] for m in CERT_MUTANTS])
+def test_certificate_models_kill_mutants_of_the_shipped_header(tmp_path, name, old, new, model, seed):
+    """The models have teeth: each mutant of zsw_cert.hpp, compiled into the model with a reduced set of widths (<i16, 16> and the
+    swapped <i16, 8>), makes the model fail at the committed iteration count — a certificate whose optimal alignments between the corners
+    are not the certified ones, one that the literal sw_simd_align does not return, or (3 * gap_open -> 2 * gap_open, which only loses
+    certificates) no read left that needs the sweeps."""
+    src = open(os.path.join(ROOT, "zoe_amd", "csrc", "zsw_cert.hpp")).read()
+    assert src.count(old) == 1, f"mutation target of {name!r} is not unique in zsw_cert.hpp"
+    header = tmp_path / "zsw_cert.hpp"
+    header.write_text(src.replace(old, new))
+    exe = str(tmp_path / model)
+    subprocess.run(["g++", "-O1", "-std=c++17", "-Wno-unknown-pragmas", "-DZSW_CERT_FEW_WIDTHS", f'-DZSW_CERT_HEADER="{header}"', "-o", exe,
+                    os.path.join(ROOT, "tests", "models", model + ".cpp")], check=True)
+    out = subprocess.run([exe, "250", str(seed)], capture_output=True, text=True, timeout=600)
+    print(out.stdout[-2000:])
+    assert out.returncode != 0, f"mutant survived: {name}\n{out.stdout}"
+    assert f"{model} OK" not in out.stdout
 
 
 @pytest.mark.parametrize("seed", [20261005, 4])

@@ -514,7 +514,15 @@ def test_reads_with_one_optimal_alignment_skip_the_second_pass(za, oracle):
         return a, time.perf_counter() - t0
 
     got, t_cert = timed(za.SeqSrc.Reference(ref))
-    gotq = prof.sw_align_from_i8(za.SeqSrc.Query(ref))
+    cert_rec = torch.full((n, 4), -7, dtype=torch.int32, device="cuda")  # zsw_debug_cert_records: the verdict per read
+    ctx.debug_cert_records(cert_rec)
+    try:
+        gotq = prof.sw_align_from_i8(za.SeqSrc.Query(ref))
+        torch.cuda.synchronize()
+    finally:
+        ctx.debug_cert_records(None)
+    certified = np.isin(cert_rec[:400_000, 0].cpu().numpy(), (1, 2))  # gapless or one gap run (include/zoe_sw.h)
+    assert certified.mean() >= 0.8, f"only {certified.mean():.3f} of the synthetic reads were certified"
     ctx.debug_set(_lib.DEBUG_ALIGN_NO_CERTIFICATE)
     try:
         want, t_lit = timed(za.SeqSrc.Reference(ref))

@@ -424,7 +424,14 @@ def test_exact_alignment_with_the_shared_profile_skips_the_literal_pass_where_on
         return a, time.perf_counter() - t0
 
     aq, t_cert = timed(za.SeqBatchSrc.Query(rb))
-    ar, _ = timed(za.SeqBatchSrc.Reference(rb))
+    cert_rec = torch.full((len(reads), 4), -7, dtype=torch.int32, device="cuda")  # zsw_debug_cert_records: the verdict per read
+    ctx.debug_cert_records(cert_rec)
+    try:
+        ar, _ = timed(za.SeqBatchSrc.Reference(rb))
+    finally:
+        ctx.debug_cert_records(None)
+    certified = np.isin(cert_rec[:8000, 0].cpu().numpy(), (1, 2))  # gapless or one gap run (include/zoe_sw.h)
+    assert certified.mean() >= 0.8, f"only {certified.mean():.3f} of the synthetic reads were certified"
     ctx.debug_set(_lib.DEBUG_ALIGN_NO_CERTIFICATE)
     try:
         lq, t_lit = timed(za.SeqBatchSrc.Query(rb))

@@ -262,6 +262,15 @@ class SwContext:
         self._band_records = records
         self.check(self.lib.zsw_debug_band_records(self.h, C.c_void_p(records.data_ptr() if records is not None else None)))
 
+    def debug_cert_records(self, records=None):
+        """zsw_debug_cert_records (tests): the certificate pass of the alignment calls writes 4 int32 per read — verdict class,
+        deciding parameter, tie count, decided by the sweep launch — into `records` (a CUDA int32 tensor of 4 * n_reads elements
+        that the caller keeps alive); None switches it off."""
+        if records is not None:
+            assert records.is_cuda and records.dtype == _torch().int32 and records.is_contiguous()
+        self._cert_records = records
+        self.check(self.lib.zsw_debug_cert_records(self.h, C.c_void_p(records.data_ptr() if records is not None else None)))
+
     def set_profile_sequence(self, sequence: bytes):
         """zsw_set_profile_sequence: the sequence the shared profile is built from (the library itself skips the work when it is the
         one already set: no copy of it is kept on this side, which another binding of the same context could leave stale)"""

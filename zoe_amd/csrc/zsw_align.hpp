@@ -68,14 +68,15 @@ struct ThreePassArgs {
     // zsw_score_ranges_shared_batch: rs/re index the read, qs/qe the profile sequence); `ref` / `ref_len` are then unused.
     const uint8_t* pseq = nullptr;
     uint32_t pseq_len = 0;
-    // Certificate mode of the classify pass (sw_simd_align's second pass skipped, zsw_capi.hip run_align; host model
-    // tests/models/align_gapless_cert.cpp): cert_ok[i] = both maxima of read i sit in one cell each (forward and reversed seeded
-    // pass, mode 3). A read whose ranges have equal lengths n, whose diagonal adds up to its score S and whose S exceeds
-    // cert_maxw * (n - 1) - 3 * cert_go, and whose two-run alternatives stay below it (classify pass), has exactly one optimal alignment, the diagonal: it is written here (cert_done[i] = 1) and
-    // is what sw_simd_align returns at every <T, N>; every other read is left to the literal striped kernel (cert_done[i] = 0).
+    // Certificate mode of the classify pass (sw_simd_align's second pass skipped, zsw_capi.hip run_align; the decision is
+    // zsw_cert.hpp's cert_decide, with the host models tests/models/align_gapless_cert.cpp and align_onegap_cert.cpp):
+    // cert_ok[i] = both maxima of read i sit in one cell each (forward and reversed seeded pass, mode 3). A read whose only optimal
+    // alignment is the gapless diagonal or has one gap run gets it here (cert_done[i] = 1), which is what sw_simd_align returns at
+    // every <T, N>; every other read is left to the literal striped kernel (cert_done[i] = 0).
     const uint8_t* cert_ok = nullptr;
     uint8_t* cert_done = nullptr;
-    int cert_maxw = 0, cert_go = 0, cert_ge = 0;  // (the one-gap certificate, tests/models/align_onegap_cert.cpp, needs gap_extend too)
+    int cert_maxw = 0, cert_go = 0, cert_ge = 0;
+    int32_t* cert_rec = nullptr;  // zsw_debug_cert_records: CERT_RECORD_INTS per read (verdict, parameter, ties, sweep launch)
     // The sweeps over the two-run alternatives cost a read several times the rest of the certificate, and one read in seven needs
     // them: with one thread per read the other lanes of its wavefront would wait. The classify launch therefore lists those reads
     // (sweep_list / sweep_count) and a second launch — list = that list, sweep_pass = true: classify code, sweeps included — takes

@@ -4,6 +4,7 @@
 #include <utility>
 
 #include "zsw_context.hpp"
+#include "zsw_cert.hpp"
 #include "zsw_synth.h"
 
 using namespace zsw;
@@ -652,11 +653,10 @@ zsw_error certificate_pass(zsw_context* ctx, const Staged& st, const RangesDev& 
     ThreePassArgs a;
     zsw_error ze = threepass_args(ctx, st, rd, pseq, pseq_len, invert, &a);
     if (ze != ZSW_OK) return ze;
-    int maxw = 0;
-    for (int i = 0; i < ctx->h_sc.S * ctx->h_sc.S; ++i) maxw = std::max(maxw, (int)ctx->h_sc.w[i]);
     a.cert_ok = settled;
     a.cert_done = ws[WS_CERT_DONE].as<uint8_t>();
-    a.cert_maxw = maxw;
+    a.cert_maxw = cert_maxw(ctx->h_sc.w, ctx->h_sc.S);
+    a.cert_rec = ctx->cert_dbg;
     a.cert_go = ctx->h_sc.gap_open;
     a.cert_ge = ctx->h_sc.gap_extend;
     // the classify launch writes cert_done for the reads with an alignment only: the others must not keep an earlier call's bytes
@@ -1416,6 +1416,12 @@ zsw_error zsw_pack4_host(zsw_context* ctx, const uint8_t* bases, uint64_t n_read
 zsw_error zsw_debug_band_records(zsw_context* ctx, int32_t* records) {
     if (!ctx) return ZSW_ERR_INVALID_ARGUMENT;
     ctx->band_dbg = records;
+    return ZSW_OK;
+}
+
+zsw_error zsw_debug_cert_records(zsw_context* ctx, int32_t* records) {
+    if (!ctx) return ZSW_ERR_INVALID_ARGUMENT;
+    ctx->cert_dbg = records;
     return ZSW_OK;
 }
 

@@ -10,6 +10,7 @@
 // Flag bytes and the two DP rows of a read live in a per-thread slot of HBM scratch (a 150 x 160 box is 24 KB); a slot is
 // sized for the attempt in progress (band first), see the DP pass.
 #include "zsw_align.hpp"
+#include "zsw_cert.hpp"
 
 namespace zsw {
 
@@ -129,18 +130,14 @@ __global__ __launch_bounds__(64) void threepass_kernel(ThreePassArgs a) {
         if (!a.list || a.sweep_pass) {
             // classify pass: the no-gaps shortcut (three_pass.rs:37-58) is resolved here, the rest is queued for the DP pass
             // (certificate mode: only reads with one optimal alignment, which must be this diagonal; the rest is not touched)
-            // Certificate mode (run_align): a.cert_ok[id] = both maxima of the read sit in one cell each, so every alignment that
-            // scores `score` runs from (rs, qs) to (re - 1, qe - 1). Equal ranges: it must be the diagonal, and no path with an
-            // insertion and a deletion may reach it (tests/models/align_gapless_cert.cpp). Ranges that differ by g: one placement
-            // of ONE gap run of g (or a run of adjacent placements) must reach it, and no path with two runs may (tests/models/align_onegap_cert.cpp).
+            // Certificate mode (run_align, run_align_shared): a.cert_ok[id] = both maxima of the read sit in one cell each, so every
+            // alignment that scores `score` runs from (rs, qs) to (re - 1, qe - 1); zsw_cert.hpp decides whether the diagonal or one
+            // gap run is the only one (tests/models/align_gapless_cert.cpp, align_onegap_cert.cpp); the rest is not touched.
             const bool cert = a.cert_ok != nullptr;
             const bool defer = a.sweep_list != nullptr && !a.sweep_pass;  // reads that need the sweeps wait for the second launch
             bool deferred = false;
-            const bool uniq = !cert || (a.cert_ok[id] && re > rs && qe > qs);
             if (a.cert_done) a.cert_done[id] = 0;
-            // (gapless certificate: three or more gap runs are ruled out by the potential — at most n - 1 pairs, 3 * gap_open —, two runs,
-            // an insertion and a deletion of the same length k in either order, by the potential too or by the sweep below)
-            if (uniq && qlen == rlen && (!cert || (long long)score > (long long)a.cert_maxw * ((long long)rlen - 1) - 3ll * a.cert_go)) {
+            auto diag_sum = [&]() -> int64_t {
                 int64_t sum = 0;
                 uint32_t k = 0;
                 for (; k + 4 <= qlen; k += 4) {  // four residues per (unaligned) load
@@ -151,130 +148,40 @@ __global__ __launch_bounds__(64) void threepass_kernel(ThreePassArgs a) {
                     for (int j = 0; j < 4; ++j) sum += wt((uint8_t)(rw >> (8 * j)), (uint8_t)(qw >> (8 * j)));
                 }
                 for (; k < qlen; ++k) sum += wt(reference[rs + k], query[qs + k]);
-                bool only = (sum < 0 ? 0u : (uint32_t)sum) == score;
-                if (only && cert && defer && (long long)a.cert_maxw * ((long long)rlen - 1) - 2ll * a.cert_go >= (long long)score) {
-                    only = false;  // (k = 1 is not ruled out by the potential: sweeps needed)
-                    deferred = true;
+                return sum;
+            };
+            auto emit = [&](uint32_t gap_len, uint32_t place) {  // [qs S][m - place M][gap_len D|I][place M][len - qe S], traceback order
+                const uint32_t m = rlen < qlen ? rlen : qlen;
+                w.push(query_len - qe, 'S');
+                w.push(m - place, 'M');
+                w.push(gap_len, rlen > qlen ? 'D' : 'I');
+                w.push(place, 'M');
+                w.push(qs, 'S');
+                w.flush();
+                out.ref_start = rs;
+                out.ref_end = re;
+                out.query_start = qs;
+                out.query_end = qe;
+                done = true;
+            };
+            if (cert) {
+                auto wbox = [&](uint32_t i, uint32_t j) -> int32_t { return wt(reference[rs + i], query[qs + j]); };
+                const CertScheme cs{a.cert_maxw, a.cert_go, a.cert_ge};
+                const CertResult cr = cert_decide(wbox, diag_sum, a.cert_ok[id] != 0, rs, re, qs, qe, score, cs, defer);
+                deferred = cr.deferred;
+                if (a.cert_rec) {
+                    int32_t* rec = a.cert_rec + (uint64_t)id * CERT_RECORD_INTS;
+                    rec[0] = cr.verdict;
+                    rec[1] = cr.param;
+                    rec[2] = cr.ties;
+                    rec[3] = a.sweep_pass ? 1 : 0;
                 }
-                if (only && cert) {
-                    // paths with two runs of k: pairs 0 .. i-1 on the diagonal, run, pairs i .. j-1 on the diagonal k rows (dir 0) or
-                    // k columns (dir 1) away, run, pairs j+k .. n-1 on the diagonal again: score - 2go - 2ge(k-1) + A(j) - B(i) with
-                    // A(j) = Q(j) - P0(j+k), B(i) = Q(i) - P0(i), 1 <= i <= j <= n-k-1 (tests/models/align_gapless_cert.cpp)
-                    const long long n_ = (long long)rlen, S_ = (long long)score;
-                    for (uint32_t k = 1; k < rlen && only; ++k) {
-                        if ((long long)a.cert_maxw * (n_ - k) - 2ll * a.cert_go - 2ll * a.cert_ge * ((long long)k - 1) < S_) break;
-                        for (int dir = 0; dir < 2 && only; ++dir) {
-                            const uint8_t* r1 = reference + rs + (dir == 0 ? k : 0);
-                            const uint8_t* q1 = query + qs + (dir == 0 ? 0 : k);
-                            int64_t qv = 0, p0j = 0, p0jk = 0, low = INT64_MAX, best_alt = INT64_MIN;
-                            for (uint32_t t = 0; t < k; ++t) p0jk += wt(reference[rs + t], query[qs + t]);
-                            for (uint32_t j = 1; j + k + 1 <= rlen; ++j) {
-                                qv += wt(r1[j - 1], q1[j - 1]);
-                                p0j += wt(reference[rs + j - 1], query[qs + j - 1]);
-                                p0jk += wt(reference[rs + j + k - 1], query[qs + j + k - 1]);
-                                const int64_t bj = qv - p0j;
-                                low = bj < low ? bj : low;
-                                const int64_t v = qv - p0jk - low;
-                                best_alt = v > best_alt ? v : best_alt;
-                            }
-                            if (best_alt != INT64_MIN && best_alt - 2ll * a.cert_go - 2ll * a.cert_ge * ((long long)k - 1) >= 0) only = false;
-                        }
-                    }
-                }
-                if (only) {
-                    w.push(query_len - qe, 'S');
-                    w.push(qe - qs, 'M');
-                    w.push(qs, 'S');
-                    w.flush();
-                    out.ref_start = rs;
-                    out.ref_end = re;
-                    out.query_start = qs;
-                    out.query_end = qe;
-                    done = true;
-                }
-            } else if (cert && uniq && qlen != rlen) {
-                const bool del = rlen > qlen;  // the run consumes reference rows
-                const uint32_t g = del ? rlen - qlen : qlen - rlen, m = del ? qlen : rlen;
-                // three or more runs: ruled out by the potential; two runs: by the potential or by the sweeps below
-                const long long three_runs = (long long)a.cert_maxw * m - 3ll * a.cert_go - (long long)(g > 3 ? g - 3 : 0) * a.cert_ge;
-                if (m >= 2 && a.cert_ge > 0 && (long long)score > three_runs) {
-                    // second diagonal: the pairs behind the run
-                    const uint8_t* r1 = reference + rs + (del ? g : 0);
-                    const uint8_t* q1 = query + qs + (del ? 0 : g);
-                    int64_t t1 = 0;
-                    for (uint32_t k = 0; k < m; ++k) t1 += wt(r1[k], q1[k]);
-                    const int64_t gap = (int64_t)a.cert_go + (int64_t)(g - 1) * a.cert_ge;
-                    int64_t p0 = 0, p1 = 0, best = INT64_MIN;
-                    uint32_t best_p = 0, first_p = 0, n_best = 0;
-                    for (uint32_t p = 1; p < m; ++p) {
-                        p0 += wt(reference[rs + p - 1], query[qs + p - 1]);
-                        p1 += wt(r1[p - 1], q1[p - 1]);
-                        const int64_t sc = p0 + (t1 - p1) - gap;
-                        if (sc > best) {
-                            best = sc;
-                            best_p = first_p = p;
-                            n_best = 1;
-                        } else if (sc == best) {
-                            ++n_best;
-                            best_p = p;
-                        }
-                    }
-                    // one placement, or adjacent ones (a gap inside a homopolymer run): the walk from the end takes the last
-                    bool only = best_p - first_p == n_best - 1 && best == (int64_t)score;
-                    if (only) {
-                        // two runs of signed lengths ra and rb = gs - ra (a deletion counts +, an insertion -): i pairs on the first
-                        // diagonal, run ra, j - i pairs on the diagonal ra away, run rb, the rest on the last diagonal:
-                        // P0(i) + Pa(j) - Pa(i) + Pz(M) - Pz(j) - cost, 1 <= i <= j <= M - 1 (tests/models/align_onegap_cert.cpp)
-                        const long long gs = (long long)rlen - (long long)qlen, S_ = (long long)score;
-                        // |ra| + |rb| <= X or the potential rules the pair out; |ra| + |gs - ra| >= 2 |ra| - g
-                        const long long X = ((long long)a.cert_maxw * m - 2ll * a.cert_go - S_) / a.cert_ge + 2;
-                        const long long amax = X >= 0 ? (X + g) / 2 + 1 : 0;
-                        for (long long ra = -amax; ra <= amax && only; ++ra) {
-                            const long long rb = gs - ra;
-                            if (ra == 0 || rb == 0) continue;
-                            const long long ap = ra > 0 ? ra : 0, an = ra < 0 ? -ra : 0, bp = rb > 0 ? rb : 0, bn = rb < 0 ? -rb : 0;
-                            const long long M = (long long)rlen - ap - bp;
-                            if (M < 2) continue;
-                            const long long cost = 2ll * a.cert_go + (long long)a.cert_ge * (ap + an + bp + bn - 2);
-                            if ((long long)a.cert_maxw * M - cost < S_) continue;
-                            if (defer) {
-                                only = false;
-                                deferred = true;
-                                break;
-                            }
-                            const uint8_t* ra_r = reference + rs + ap;
-                            const uint8_t* ra_q = query + qs + an;
-                            const uint8_t* rz_r = reference + rs + ap + bp;
-                            const uint8_t* rz_q = query + qs + an + bn;
-                            int64_t pzM = 0;
-                            for (long long t = 0; t < M; ++t) pzM += wt(rz_r[t], rz_q[t]);
-                            int64_t s0 = 0, sa = 0, sz = 0, low = INT64_MAX, best_alt = INT64_MIN;
-                            for (long long j = 1; j <= M - 1; ++j) {
-                                s0 += wt(reference[rs + j - 1], query[qs + j - 1]);
-                                sa += wt(ra_r[j - 1], ra_q[j - 1]);
-                                sz += wt(rz_r[j - 1], rz_q[j - 1]);
-                                const int64_t bj = sa - s0;
-                                low = bj < low ? bj : low;
-                                const int64_t v = sa - sz - low;
-                                best_alt = v > best_alt ? v : best_alt;
-                            }
-                            if (pzM - cost + best_alt >= S_) only = false;
-                        }
-                    }
-                    if (only) {
-                        w.push(query_len - qe, 'S');
-                        w.push(m - best_p, 'M');
-                        w.push(g, del ? 'D' : 'I');
-                        w.push(best_p, 'M');
-                        w.push(qs, 'S');
-                        w.flush();
-                        out.ref_start = rs;
-                        out.ref_end = re;
-                        out.query_start = qs;
-                        out.query_end = qe;
-                        done = true;
-                    }
-                }
+                if (cr.verdict == CERT_GAPLESS) emit(0, 0);
+                else if (cr.verdict == CERT_ONE_GAP) emit(rlen > qlen ? rlen - qlen : qlen - rlen, (uint32_t)cr.param);
+            } else if (qlen == rlen) {
+                // the no-gaps shortcut of three_pass.rs:37-58
+                const int64_t sum = diag_sum();
+                if ((sum < 0 ? 0u : (uint32_t)sum) == score) emit(0, 0);
             }
             if (deferred) a.sweep_list[atomicAdd(a.sweep_count, 1u)] = id;
             if (!done && a.cert_ok) continue;
