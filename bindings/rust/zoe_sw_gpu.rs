@@ -792,7 +792,8 @@ impl GpuContext {
         self.check(unsafe { zsw_set_option(self.raw, 1, i64::from(on)) }, 0, 0)
     }
 
-    /// `zsw_prune_rescored`: reads of the last column-pruned score call that were rescored over all their cells.
+    /// `zsw_prune_rescored`: reads the forward seeded (or column-pruned) pass of the last call handed back and that were
+    /// rescored over all their cells (the reversed pass of the ranges and alignment calls is not counted).
     pub fn prune_rescored(&self) -> Result<u64, GpuError> {
         let mut n = 0u64;
         // SAFETY: live context, valid out-pointer

@@ -17,7 +17,8 @@
  *   SeqSrc::make_alignment / Alignment::invert               src/alignment/mod.rs:176-190, types/output.rs:396-425
  *
  * Plain pointers and sizes only; no hidden global state; one context per GPU (zsw_group for several); a context may
- * be used from one host thread at a time.  Every function returns a zsw_error and never aborts.  A call leaves the
+ * be used from one host thread at a time, and from one stream at a time: consecutive asynchronous calls on the same stream are
+ * ordered, calls on two streams must not overlap on one context.  Every function returns a zsw_error and never aborts.  A call leaves the
  * calling thread's current HIP device as it found it.  At most 2^31-1 reads per call.
  * Results are bit-identical to the reference's CPU path: score and status for every read; for the
  * alignment calls also ranges and CIGAR of the stated <T,N> instantiation.
@@ -238,7 +239,10 @@ zsw_error zsw_align_3pass_shared_batch_from(zsw_context* ctx, const zsw_batch* r
  * (src/alignment/sneaky_snake.rs:78-131): the SneakySnake edit-distance filter between a read and a candidate window of the
  * context's reference; `threshold` is the allowed edits as a fraction of the read length. Bytes are compared raw, as in the
  * reference (no index map). ref_start / ref_len / out_pass live where `reads->mem` says. A window that leaves the reference
- * is ZSW_ERR_INVALID_ARGUMENT for host arrays and ZSW_FILTER_BAD_WINDOW in out_pass for device arrays. */
+ * is ZSW_ERR_INVALID_ARGUMENT for host arrays and ZSW_FILTER_BAD_WINDOW in out_pass for device arrays.
+ * reads->encoding must be ZSW_ENCODING_BYTES, in host and in device memory: packed residue indices are not the bytes the filter
+ * compares, so ZSW_ENCODING_PACKED4 (and any unknown value) is ZSW_ERR_INVALID_ARGUMENT before anything is copied. Host offsets
+ * that go backwards are ZSW_ERR_INVALID_ARGUMENT, as in the scoring calls. */
 typedef enum zsw_filter_result {
     ZSW_FILTER_REJECT = 0,      /* Some(false) */
     ZSW_FILTER_PASS = 1,        /* Some(true)  */
@@ -402,9 +406,14 @@ zsw_error zsw_debug_band_records(zsw_context* ctx, int32_t* records);
  * records: device memory for 4 int32 per read of the following calls, NULL = off (the default). Results do not change. */
 zsw_error zsw_debug_cert_records(zsw_context* ctx, int32_t* records);
 
-/* Reads of the context's last score call that the seeded (or column-pruned) pass handed back — no anchor, or a bound check
+/* Reads of the context's last call that the seeded (or column-pruned) first pass handed back — no anchor, or a bound check
  * failed — and that were scored over all their cells (0 if the call did not take such a pass). Synchronises the device.
- * Diagnostics for tests and bench.py. */
+ * Read-as-profile role, every entry point (score, ends, ranges, alignment, 3-pass alignment): the hand-backs of the FORWARD pass.
+ * The reversed seeded pass of the ranges and alignment calls is not counted: the reads it cannot settle are not rescored, they
+ * go to the exact reverse kernel (or sw_simd_align's own second pass) with every read whose maximum is not in one cell.
+ * Shared-profile role: zsw_score_shared_batch(_from) count the hand-backs of the role-swapped pass in the same way; the ends,
+ * ranges and alignment calls of that role report 0, because their seeded passes rescore nothing — a read handed back joins the
+ * reads with ties under the shared role's own kernel. Diagnostics for tests and bench.py. */
 zsw_error zsw_prune_rescored(zsw_context* ctx, uint64_t* out_reads);
 
 #ifdef __cplusplus

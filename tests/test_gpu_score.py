@@ -581,6 +581,62 @@ def test_host_batch_pipeline_matches_device_batch(za, oracle, dna):
     torch.cuda.empty_cache()
 
 
+def test_host_pipeline_ends_and_tiers_match_every_other_route(oracle, dna):
+    """The chunked host pipeline beyond the score: 4.6 M reads of 151 bases (odd: a packed read ends in half a byte) are three
+    chunks as bytes (0.5 M, 4 M, 0.1 M) and four as packed reads (0.5 M, 1 M, 2 M, 1.1 M; zsw_capi.hip run_score). Through
+    zsw_score_ends_batch (the pipeline copies ref_end / query_end back per chunk) and zsw_score_batch_from (tiers), as bytes and
+    packed: the pipeline, ZSW_DEBUG_NO_PIPELINE and the device-resident call agree on every read and every array; the oracle on
+    100 reads on either side of every chunk boundary and at both ends of the batch; the guard entries stay."""
+    import ctypes as C
+
+    import torch
+
+    import abi_helpers as ah
+    import zoe_amd as za
+    from zoe_amd import _lib, synth
+
+    n, L = 4_600_000, 151
+    lib = _lib.load()
+    ref = synth.reference_host(2000)
+    h = ah.new_context(_lib, lib, dna, -10, -1, ref)
+    try:
+        rb = synth.reads_device(za.SwContext.get(0), ref, 31, n, L)
+        torch.cuda.synchronize()
+        host = rb.bases.cpu().numpy()
+        del rb
+        torch.cuda.empty_cache()
+        rs = ah.ReadSet("pipeline", ref, [], L, np.zeros(0, dtype=np.int64), np.zeros(0, dtype=np.int64))
+        rs._flat, rs.reads = host, range(n)  # (4.6 M reads stay one array: Presented needs the flat bytes and the count only)
+        ends, tiers = ah.ENTRY["zsw_score_ends_batch"], ah.ENTRY["zsw_score_batch_from"]
+        results = {}
+        for pres in ("device-fixed", "host-fixed", "host-packed4"):
+            p = ah.Presented(_lib, rs, pres, lib, h, dna.mapping.index_map)
+            for flags in ((0,) if pres == "device-fixed" else (0, _lib.DEBUG_NO_PIPELINE)):
+                assert lib.zsw_debug_set(h, flags) == 0
+                for e in (ends, tiers):
+                    results[(pres, flags, e.name)] = ah.Call(_lib, lib, h, e, p).run().collect()
+            del p
+            torch.cuda.empty_cache()
+        for e in (ends, tiers):
+            want = results[("device-fixed", 0, e.name)]
+            for pres in ("host-fixed", "host-packed4"):
+                for flags in (0, _lib.DEBUG_NO_PIPELINE):
+                    ah.assert_same(results[(pres, flags, e.name)], want, f"{e.name} {pres} debug flags {flags}")
+        idx = sorted({i for b in (0, 500_000, 1_500_000, 3_500_000, 4_500_000, n) for i in range(max(0, b - 100), min(n, b + 100))})
+        sc = osc(oracle, dna, -10, -1)
+        read = lambda i: host[i * L:(i + 1) * L].tobytes()
+        o_ends = ah.pmap(lambda i: oracle.score_ends("i16", 16, sc, read(i), ref), idx)
+        o_casc = ah.pmap(lambda i: oracle.cascade_score(8, 256, sc, read(i), ref), idx)
+        ge, gt = results[("host-packed4", 0, ends.name)], results[("host-packed4", 0, tiers.name)]
+        for i, (st, (s, re_, qe)), (st2, s2, t2) in zip(idx, o_ends, o_casc):
+            assert int(ge["status"][i]) == st and (int(gt["status"][i]), int(gt["tier"][i])) == (st2, t2), i
+            if st == S_:
+                assert (int(ge["score"][i]), int(ge["ref_end"][i]), int(ge["query_end"][i]), int(gt["score"][i])) == (s, re_, qe, s2), i
+    finally:
+        lib.zsw_destroy(h)
+        torch.cuda.empty_cache()
+
+
 def test_long_reads_are_scored_tile_by_tile(za, oracle, dna, debug):
     """Reads longer than the widest strip configuration (2,432 columns) run as several TILED launches of the packed kernel, the
     strip boundary of every reference row passing through HBM: score, ends and ranges must equal the oracle, for DNA and for

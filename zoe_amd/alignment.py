@@ -283,7 +283,8 @@ class SwContext:
         self.check(self.lib.zsw_set_option(self.h, int(option), int(value)), profile_errors=False)
 
     def prune_rescored(self) -> int:
-        """zsw_prune_rescored: reads the last score call's seeded (or column-pruned) pass handed back to the full pass."""
+        """zsw_prune_rescored: reads the last call's forward seeded (or column-pruned) pass handed back to the full pass
+        (the reversed pass of the ranges and alignment calls is not counted; include/zoe_sw.h)."""
         v = C.c_uint64(0)
         self.check(self.lib.zsw_prune_rescored(self.h, C.byref(v)))
         return int(v.value)

@@ -1280,8 +1280,14 @@ zsw_error zsw_sneaky_snake_batch(zsw_context* ctx, const zsw_batch* reads, const
     if (!reads || !ref_start || !ref_len || !out_pass) return fail(ctx, ZSW_ERR_INVALID_ARGUMENT, "null argument");
     if (reads->n_reads > 0x7fffffffull) return fail(ctx, ZSW_ERR_INVALID_ARGUMENT, "n_reads > 2^31-1 per call");
     if (reads->n_reads && !reads->bases) return fail(ctx, ZSW_ERR_INVALID_ARGUMENT, "null bases");
+    // the filter compares raw bytes (no index map): residue indices packed two to a byte have no meaning here
+    if (reads->encoding != ZSW_ENCODING_BYTES)
+        return fail(ctx, ZSW_ERR_INVALID_ARGUMENT, "zsw_sneaky_snake_batch: zsw_batch.encoding must be ZSW_ENCODING_BYTES (the filter compares raw bytes)");
     const uint32_t n = (uint32_t)reads->n_reads;
     if (n == 0) return ZSW_OK;
+    if (reads->mem == ZSW_MEM_HOST && reads->offsets)
+        for (uint32_t i = 0; i < n; ++i)
+            if (reads->offsets[i + 1] < reads->offsets[i]) return fail(ctx, ZSW_ERR_INVALID_ARGUMENT, "offsets not monotone");
     hipStream_t stream = (hipStream_t)stream_;
     ZSW_HIP(ctx, hipSetDevice(ctx->device));
     BatchDev b{};

@@ -329,7 +329,8 @@ zsw_error group_align(zsw_group* g, const zsw_batch* reads, zsw_alignment* out_a
         const ShardAlign& s = sh[(size_t)i];
         for (uint64_t k = 0; k < count; ++k) {
             zsw_alignment a = s.aln[k];
-            a.ciglet_offset += base;
+            // (a read without an alignment keeps the all-zero record the single-context call writes)
+            if (s.status[k] == ZSW_STATUS_SOME) a.ciglet_offset += base;
             out_aln[first + k] = a;
             out_status[first + k] = s.status[k];
             if (out_tier) out_tier[first + k] = s.tier[k];

@@ -657,7 +657,9 @@ hipError_t launch_score(const ScoringDev* d_sc, const ScoringDev& h_sc, const Ba
             }
         }
         if (pe != hipSuccess) return pe;
-        hipLaunchKernelGGL(add_count_kernel, dim3(1), dim3(1), 0, stream, counter, ws.prune_fail_count + 1);
+        // zsw_prune_rescored counts the reads scored over all their cells HERE: a pass whose handed-back reads the caller settles by
+        // other means (the reversed pass of the ranges, the shared role's ends) adds nothing
+        if (!out.skip_handed_back) hipLaunchKernelGGL(add_count_kernel, dim3(1), dim3(1), 0, stream, counter, ws.prune_fail_count + 1);
         return hipGetLastError();
     };
     // Column-pruned pass over the items of `bb` (reads of at most kPruneClasses[cls].max_len bases), then score_kernel_v2 over the
