@@ -109,6 +109,11 @@ unsafe extern "C" {
     fn zsw_align_batch_from(ctx: *mut ZswContext, reads: *const ZswBatch, from_width: i32, preset_bits: i32, invert: i32, out_aln: *mut ZswAlignment, out_status: *mut u8, out_tier: *mut u8, out_inc: *mut u32, out_op: *mut u8, ciglet_cap: u64, out_n_ciglets: *mut u64, stream: *mut c_void) -> i32;
     fn zsw_align_3pass_batch(ctx: *mut ZswContext, reads: *const ZswBatch, int_type: i32, lanes: i32, invert: i32, out_aln: *mut ZswAlignment, out_status: *mut u8, out_inc: *mut u32, out_op: *mut u8, ciglet_cap: u64, out_n_ciglets: *mut u64, stream: *mut c_void) -> i32;
     fn zsw_align_3pass_batch_from(ctx: *mut ZswContext, reads: *const ZswBatch, from_width: i32, preset_bits: i32, invert: i32, out_aln: *mut ZswAlignment, out_status: *mut u8, out_tier: *mut u8, out_inc: *mut u32, out_op: *mut u8, ciglet_cap: u64, out_n_ciglets: *mut u64, stream: *mut c_void) -> i32;
+    fn zsw_set_complement(ctx: *mut ZswContext, table: *const u8) -> i32;
+    fn zsw_score_strands_batch_from(ctx: *mut ZswContext, reads: *const ZswBatch, from_width: i32, preset_bits: i32, out_score: *mut u32, out_status: *mut u8, out_tier: *mut u8, out_strand: *mut u8, stream: *mut c_void) -> i32;
+    fn zsw_orient_batch(ctx: *mut ZswContext, reads: *const ZswBatch, strand: *const u8, out_bases: *mut u8, stream: *mut c_void) -> i32;
+    fn zsw_align_3pass_strands_batch_from(ctx: *mut ZswContext, reads: *const ZswBatch, from_width: i32, preset_bits: i32, invert: i32, out_aln: *mut ZswAlignment, out_status: *mut u8, out_tier: *mut u8, out_strand: *mut u8, out_inc: *mut u32, out_op: *mut u8, ciglet_cap: u64, out_n_ciglets: *mut u64, stream: *mut c_void) -> i32;
+    fn zsw_strand_counts(ctx: *mut ZswContext, out: *mut u64) -> i32;
     fn zsw_set_profile_sequence(ctx: *mut ZswContext, sequence: *const u8, len: usize, mem: i32) -> i32;
     fn zsw_score_shared_batch(ctx: *mut ZswContext, reads: *const ZswBatch, int_type: i32, lanes: i32, out_score: *mut u32, out_status: *mut u8, stream: *mut c_void) -> i32;
     fn zsw_score_shared_batch_from(ctx: *mut ZswContext, reads: *const ZswBatch, from_width: i32, preset_bits: i32, out_score: *mut u32, out_status: *mut u8, out_tier: *mut u8, stream: *mut c_void) -> i32;
@@ -144,6 +149,7 @@ unsafe extern "C" {
     fn zsw_debug_set(ctx: *mut ZswContext, flags: u32) -> i32;
     fn zsw_debug_band_records(ctx: *mut ZswContext, records: *mut i32) -> i32;
     fn zsw_debug_cert_records(ctx: *mut ZswContext, records: *mut i32) -> i32;
+    fn zsw_debug_strand_records(ctx: *mut ZswContext, records: *mut i32) -> i32;
     fn zsw_prune_rescored(ctx: *mut ZswContext, out_reads: *mut u64) -> i32;
     fn zsw_set_option(ctx: *mut ZswContext, option: i32, value: i64) -> i32;
 }
@@ -698,6 +704,77 @@ impl GpuContext {
             // SAFETY: as above
             unsafe { zsw_align_3pass_batch_from(self.raw, &c, cascade.from_width, cascade.preset_bits, invert, aln, st, tier, inc, op, cap, need, ptr::null_mut()) }
         })
+    }
+
+    /// `zsw_set_complement`: the byte -> complementary byte table of the strand-aware calls; `None` restores the IUPAC default.
+    pub fn set_complement(&self, table: Option<&[u8; 256]>) -> Result<(), GpuError> {
+        // SAFETY: live context; the table is copied by the call
+        self.check(unsafe { zsw_set_complement(self.raw, table.map_or(ptr::null(), |t| t.as_ptr())) }, 0, 0)
+    }
+
+    /// Per read: the better of `sw_score_from_i{from_width}` on the read and on its reverse complement
+    /// (`Nucleotides::to_reverse_complement`), ties to the forward strand: (score, width that answered, strand: 0 forward, 1 reverse).
+    pub fn sw_score_strands_from_batch<const S: usize, Q: AsRef<[u8]>>(
+        &self, reads: &[Q], reference: &[u8], scoring: &Scoring<'_, S>, cascade: Cascade,
+    ) -> Result<Vec<(Result<MaybeAligned<u32>, ProfileError>, u8, u8)>, GpuError> {
+        self.configure(scoring, reference)?;
+        let batch = HostBatch::new(reads);
+        let n = reads.len();
+        let (mut score, mut status, mut tier, mut strand) = (vec![0u32; n.max(1)], vec![0u8; n.max(1)], vec![0u8; n.max(1)], vec![0u8; n.max(1)]);
+        // SAFETY: output arrays hold n entries
+        let code = unsafe {
+            zsw_score_strands_batch_from(self.raw, &batch.as_c(), cascade.from_width, cascade.preset_bits, score.as_mut_ptr(), status.as_mut_ptr(), tier.as_mut_ptr(),
+                                         strand.as_mut_ptr(), ptr::null_mut())
+        };
+        self.check(code, scoring.gap_open, scoring.gap_extend)?;
+        Ok((0..n).map(|i| (maybe(status[i], || score[i]), tier[i], strand[i])).collect())
+    }
+
+    /// `zsw_orient_batch`: the reads with every read of strand 1 replaced by its reverse complement.
+    pub fn orient_batch<Q: AsRef<[u8]>>(&self, reads: &[Q], strand: &[u8]) -> Result<Vec<Vec<u8>>, GpuError> {
+        assert_eq!(reads.len(), strand.len());
+        let batch = HostBatch::new(reads);
+        let mut out = vec![0u8; batch.bases.len()];
+        // SAFETY: out holds as many bytes as the batch, strand one entry per read
+        self.check(unsafe { zsw_orient_batch(self.raw, &batch.as_c(), strand.as_ptr(), out.as_mut_ptr(), ptr::null_mut()) }, 0, 0)?;
+        Ok((0..reads.len()).map(|i| out[batch.offsets[i] as usize..batch.offsets[i + 1] as usize].to_vec()).collect())
+    }
+
+    /// Per read: `profiles.sw_align_from_i{from_width}_3pass(seq)` of the read or of its reverse complement, whichever scores
+    /// higher (ties: forward); coordinates are those of the sequence as aligned. The vectors are the widths that answered and the strands.
+    pub fn sw_align_3pass_strands_from_batch<const S: usize, Q: AsRef<[u8]>>(
+        &self, reads: &[Q], reference: &[u8], scoring: &Scoring<'_, S>, cascade: Cascade, other: OtherSeq,
+    ) -> Result<(Vec<Result<MaybeAligned<Alignment<u32>>, ProfileError>>, Vec<u8>, Vec<u8>), GpuError> {
+        self.configure(scoring, reference)?;
+        let batch = HostBatch::new(reads);
+        let c = batch.as_c();
+        let invert = i32::from(other == OtherSeq::Query);
+        let mut strand = vec![0u8; reads.len().max(1)];
+        let strand_ptr = strand.as_mut_ptr();
+        let (out, tier) = self.align_with(reads.len(), scoring.gap_open, scoring.gap_extend, |aln, st, tier, inc, op, cap, need| {
+            // SAFETY: all arrays were sized by align_with; strand holds one entry per read
+            unsafe { zsw_align_3pass_strands_batch_from(self.raw, &c, cascade.from_width, cascade.preset_bits, invert, aln, st, tier, strand_ptr, inc, op, cap, need, ptr::null_mut()) }
+        })?;
+        strand.truncate(reads.len());
+        Ok((out, tier, strand))
+    }
+
+    /// `zsw_strand_counts` of the last strand-aware call: reads settled forward by proof, settled reverse by proof, scored on
+    /// both strands, answered as reverse.
+    pub fn strand_counts(&self) -> Result<[u64; 4], GpuError> {
+        let mut c = [0u64; 4];
+        // SAFETY: live context, four entries
+        self.check(unsafe { zsw_strand_counts(self.raw, c.as_mut_ptr()) }, 0, 0)?;
+        Ok(c)
+    }
+
+    /// `zsw_debug_strand_records`: tests only — the strand-aware calls report, per read, the supports, the whole-reference bounds,
+    /// the strand that ran first and whether the read was settled by proof (8 `i32` per read in device memory; null = off).
+    ///
+    /// # Safety
+    /// `records` must be null or device memory for `8 * n_reads` `i32` that outlives the following calls.
+    pub unsafe fn debug_strand_records(&self, records: *mut i32) -> Result<(), GpuError> {
+        self.check(zsw_debug_strand_records(self.raw, records), 0, 0)
     }
 
     /// Per read: `sneaky_snake(&reference[start..start+len], read, threshold)` -> `Option<bool>`.

@@ -4,7 +4,10 @@
 // POS = ref_range.start + 1, CIGAR = states, AS:i = score.
 //
 //   g++ -O2 -std=c++17 -Iinclude examples/zsw_driver.cpp -o examples/zsw_driver -Lzoe_amd -lzoe_sw_hip -Wl,-rpath,$PWD/zoe_amd
-//   ./examples/zsw_driver reference.txt reads.fastq [--score-only | --3pass]
+//   ./examples/zsw_driver reference.txt reads.fastq [--score-only | --3pass | --both-strands]
+// --both-strands: every read is aligned on whichever strand scores higher (sw_align_strands_from_i8_3pass); a read answered by
+// its reverse complement gets flag 16, SEQ reverse complemented and QUAL reversed, and POS / CIGAR are those of that sequence.
+#include <algorithm>
 #include <cstring>
 #include <fstream>
 #include <iostream>
@@ -31,11 +34,12 @@ static std::string read_reference(const std::string& path, std::string* name) {
 
 int main(int argc, char** argv) {
     if (argc < 3) {
-        std::cerr << "usage: zsw_driver reference.(fa|txt) reads.fastq [--score-only | --3pass]\n";
+        std::cerr << "usage: zsw_driver reference.(fa|txt) reads.fastq [--score-only | --3pass | --both-strands]\n";
         return 2;
     }
     const bool score_only = argc > 3 && !std::strcmp(argv[3], "--score-only");
     const bool three_pass = argc > 3 && !std::strcmp(argv[3], "--3pass");  // sw_align_from_i8_3pass instead of sw_align_from_i8
+    const bool both_strands = argc > 3 && !std::strcmp(argv[3], "--both-strands");  // sw_align_strands_from_i8_3pass
     try {
         std::string ref_name;
         const std::string reference = read_reference(argv[1], &ref_name);
@@ -58,12 +62,21 @@ int main(int argc, char** argv) {
                 std::cout << names[i] << '\t' << (scores[i].is_some() ? std::to_string(scores[i].value) : std::string("*")) << '\n';
             return 0;
         }
-        auto alns = three_pass ? profiles.sw_align_from_i8_3pass(reference) : profiles.sw_align_from_i8(reference);
+        auto alns = both_strands ? profiles.sw_align_strands_from_i8_3pass(reference)
+                    : three_pass ? profiles.sw_align_from_i8_3pass(reference)
+                                 : profiles.sw_align_from_i8(reference);
+        std::vector<uint8_t> strand(reads.size(), 0);
+        if (both_strands) {  // SEQ and QUAL as aligned: the reverse complement of a read answered on the reverse strand, its qualities reversed
+            strand = profiles.last_strands();
+            reads = profiles.orient(strand);
+            for (size_t i = 0; i < reads.size(); ++i)
+                if (strand[i]) std::reverse(quals[i].begin(), quals[i].end());
+        }
         std::cout << "@HD\tVN:1.6\n@SQ\tSN:" << ref_name << "\tLN:" << reference.size() << '\n';
         for (size_t i = 0; i < reads.size(); ++i) {
             if (alns[i].is_some()) {
                 const zoe::Alignment& a = alns[i].value;
-                std::cout << names[i] << "\t0\t" << ref_name << '\t' << a.ref_start + 1 << "\t255\t" << a.cigar() << "\t*\t0\t0\t" << reads[i]
+                std::cout << names[i] << '\t' << (strand[i] ? 16 : 0) << '\t' << ref_name << '\t' << a.ref_start + 1 << "\t255\t" << a.cigar() << "\t*\t0\t0\t" << reads[i]
                           << '\t' << quals[i] << "\tAS:i:" << a.score << '\n';
             } else {
                 std::cout << names[i] << "\t4\t*\t0\t0\t*\t*\t0\t0\t" << reads[i] << '\t' << quals[i] << '\n';

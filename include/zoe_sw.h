@@ -181,6 +181,54 @@ zsw_error zsw_align_3pass_batch_from(zsw_context* ctx, const zsw_batch* reads, i
                                      zsw_alignment* out_aln, uint8_t* out_status, uint8_t* out_tier, uint32_t* out_inc,
                                      uint8_t* out_op, uint64_t ciglet_cap, uint64_t* out_n_ciglets, void* stream);
 
+/* ---- reads from either strand -------------------------------------------------------------- */
+/* Reads from a sequencer come from both strands; about half of them match the reference only as their reverse complement
+ * (Nucleotides::to_reverse_complement, src/data/types/nucleotides/mod.rs; the "Reversibility" notes on Alignment,
+ * src/alignment/types/output.rs:233-256). With rc(read) = the read reversed, every byte sent through the context's complement
+ * table, and f one of the entry points above: F_i = f(read_i), R_i = f(rc(read_i)). The strand-aware result of read i is F_i
+ * unless R_i ranks strictly higher — ZSW_STATUS_OVERFLOWED > ZSW_STATUS_SOME by score > ZSW_STATUS_UNMAPPED = ZSW_STATUS_EMPTY;
+ * ties go to the forward strand. out_strand[i] = 0 (forward) or 1 (reverse); everything else of the result is bit for bit
+ * what f returns for the chosen orientation, with coordinates in the sequence as aligned, i.e. in rc(read_i) for strand 1:
+ * what a SAM record with flag 16 carries.
+ * The library does not score both orientations of every read: k-mers of both orientations looked up in the
+ * reference index bound what either orientation can score at all, the more promising one is scored first, and the other one
+ * only if that bound does not already rank it below. Same results for every input; ZSW_OPTION_EXACT_PRUNING = 0, or a matrix or
+ * reference the index cannot serve, scores every read on both strands.
+ * Not covered: zsw_group_*, the direct (one <T, N>) calls, the ends and ranges calls, the shared-profile role — orient the reads
+ * with zsw_orient_batch once the strands are known and use any entry point on the oriented batch. */
+
+/* Optional. table[b] = the byte of the base complementary to byte b. NULL restores the default: the IUPAC nucleotide complement
+ * (A<->T, C<->G, U->A, R<->Y, K<->M, B<->V, D<->H; S, W, N themselves), case preserved, every other byte mapped to itself. */
+zsw_error zsw_set_complement(zsw_context* ctx, const uint8_t* table /* 256 entries */);
+
+/* zsw_score_batch_from under the contract above; out_tier is optional, out_strand is not. Host and device batches, fixed and
+ * ragged, ZSW_ENCODING_BYTES; ZSW_ENCODING_PACKED4 returns ZSW_ERR_UNSUPPORTED (a packed residue index has no complement byte).
+ * The call synchronises the stream once, to read the number of reads that need their other strand scored (and, like every call,
+ * once more for a ragged device batch, whose size comes back from the device). Device workspace: the oriented copy of the batch,
+ * a second batch of the reads scored on both strands, 8 bytes per read — for a host batch also the staged batch itself, three
+ * times its bytes in all; kept by the context until zsw_destroy or zsw_set_option(ZSW_OPTION_EXACT_PRUNING, 0).
+ * A host batch crosses PCIe whole, in one copy, before the first kernel: the chunked copies that zsw_score_batch_from overlaps with
+ * its kernels for large fixed-length host batches are not used here (not measured; keep large batches on the device). */
+zsw_error zsw_score_strands_batch_from(zsw_context* ctx, const zsw_batch* reads, int from_width, int preset_bits,
+                                       uint32_t* out_score, uint8_t* out_status, uint8_t* out_tier, uint8_t* out_strand, void* stream);
+
+/* out_bases = the batch with every read i of strand[i] != 0 replaced by rc(read_i), the others copied: the same layout and the same
+ * offsets as the input, in host or device memory as the input (strand and out_bases live where reads->mem says; out_bases must
+ * not overlap reads->bases). Needs neither scoring nor reference. ZSW_ENCODING_PACKED4 returns ZSW_ERR_UNSUPPORTED. Applying it
+ * twice with the same strands restores the input if the complement table is an involution (the default is, but for U). */
+zsw_error zsw_orient_batch(zsw_context* ctx, const zsw_batch* reads, const uint8_t* strand, uint8_t* out_bases, void* stream);
+
+/* zsw_align_3pass_batch_from under the contract above: the strand decision of zsw_score_strands_batch_from, then ONE alignment run
+ * on the oriented batch. Arguments as zsw_align_3pass_batch_from, plus out_strand. */
+zsw_error zsw_align_3pass_strands_batch_from(zsw_context* ctx, const zsw_batch* reads, int from_width, int preset_bits, int invert,
+                                             zsw_alignment* out_aln, uint8_t* out_status, uint8_t* out_tier, uint8_t* out_strand,
+                                             uint32_t* out_inc, uint8_t* out_op, uint64_t ciglet_cap, uint64_t* out_n_ciglets, void* stream);
+
+/* Counters of the context's last strand-aware call: out[0] reads settled on the forward strand by proof (the reverse strand was
+ * never scored), out[1] settled on the reverse strand by proof, out[2] scored on both strands, out[3] answered as reverse.
+ * out[0] + out[1] + out[2] = the reads of the call. Synchronises the device. */
+zsw_error zsw_strand_counts(zsw_context* ctx, uint64_t* out /* 4 entries */);
+
 /* ---- shared profile: one profile, many sequences ------------------------------------------- */
 /* The other role of the striped functions (sw/mod.rs:63-67: "the profile can be aligned against any number of different
  * sequences"; SharedProfiles, profile_set.rs:552-560; Nucleotides::into_shared_profile, nucleotides/mod.rs:295-299): the
@@ -406,6 +454,14 @@ zsw_error zsw_debug_band_records(zsw_context* ctx, int32_t* records);
  * records: device memory for 4 int32 per read of the following calls, NULL = off (the default). Results do not change. */
 zsw_error zsw_debug_cert_records(zsw_context* ctx, int32_t* records);
 
+/* Tests only (tests/test_gpu_strands.py): the strand-aware calls (zsw_strand.hip) write, for every read, eight int32 into
+ * records[8 * read]: [0] / [1] the support of the anchor vote on the forward / reverse strand, [2] / [3] the whole-reference bound
+ * of the forward / reverse strand (no local alignment of that orientation scores more; -1: no bound), [4] the strand that ran
+ * first, [5] 1 = settled by proof (the other strand was not scored), [6], [7] 0. The host model (tests/models/strand_bound.cpp)
+ * computes [0..4] from the read; the test requires equality. Without a usable index: 0, 0, -1, -1, 0. records: device memory for
+ * 8 int32 per read of the following calls, NULL = off (the default). Results do not change. */
+zsw_error zsw_debug_strand_records(zsw_context* ctx, int32_t* records);
+
 /* Reads of the context's last call that the seeded (or column-pruned) first pass handed back — no anchor, or a bound check
  * failed — and that were scored over all their cells (0 if the call did not take such a pass). Synchronises the device.
  * Read-as-profile role, every entry point (score, ends, ranges, alignment, 3-pass alignment): the hand-backs of the FORWARD pass.
@@ -413,7 +469,9 @@ zsw_error zsw_debug_cert_records(zsw_context* ctx, int32_t* records);
  * go to the exact reverse kernel (or sw_simd_align's own second pass) with every read whose maximum is not in one cell.
  * Shared-profile role: zsw_score_shared_batch(_from) count the hand-backs of the role-swapped pass in the same way; the ends,
  * ranges and alignment calls of that role report 0, because their seeded passes rescore nothing — a read handed back joins the
- * reads with ties under the shared role's own kernel. Diagnostics for tests and bench.py. */
+ * reads with ties under the shared role's own kernel. After a strand-aware call: the hand-backs of the LAST score pass it ran —
+ * the pass over the second batch (the reads scored on both strands), or the first pass if no read needed its other strand.
+ * Diagnostics for tests and bench.py. */
 zsw_error zsw_prune_rescored(zsw_context* ctx, uint64_t* out_reads);
 
 #ifdef __cplusplus

@@ -326,6 +326,28 @@ class LocalProfilesBatch : public ProfileBatchBase {
         }
         return out;
     }
+    // Reads from either strand (zsw_score_strands_batch_from): per read the better of sw_score_from_i{8,16,32} on the read and on
+    // its reverse complement (Nucleotides::to_reverse_complement), ties to the forward strand; last_strands() says which it was
+    std::vector<MaybeAligned<uint32_t>> sw_score_strands_from_i8(const std::string& reference) { return score_strands_from(reference, 8); }
+    std::vector<MaybeAligned<uint32_t>> sw_score_strands_from_i16(const std::string& reference) { return score_strands_from(reference, 16); }
+    std::vector<MaybeAligned<uint32_t>> sw_score_strands_from_i32(const std::string& reference) { return score_strands_from(reference, 32); }
+    // zsw_align_3pass_strands_batch_from: sw_align_from_i{8,16,32}_3pass of the read or of its reverse complement, whichever scores
+    // higher; coordinates are those of the sequence as aligned (a SAM record with flag 16 for strand 1)
+    std::vector<MaybeAligned<Alignment>> sw_align_strands_from_i8_3pass(const std::string& seq, bool seq_is_query = false) { return align_strands_from(seq, seq_is_query, 8); }
+    std::vector<MaybeAligned<Alignment>> sw_align_strands_from_i16_3pass(const std::string& seq, bool seq_is_query = false) { return align_strands_from(seq, seq_is_query, 16); }
+    std::vector<MaybeAligned<Alignment>> sw_align_strands_from_i32_3pass(const std::string& seq, bool seq_is_query = false) { return align_strands_from(seq, seq_is_query, 32); }
+    // the strand that answered each read of the last strand-aware call: 0 forward, 1 reverse complement
+    const std::vector<uint8_t>& last_strands() const { return strand_; }
+    // the reads with every read of strand[i] != 0 replaced by its reverse complement (zsw_orient_batch)
+    std::vector<std::string> orient(const std::vector<uint8_t>& strand) {
+        if (strand.size() != size()) throw GpuError(ZSW_ERR_INVALID_ARGUMENT, "one strand per read");
+        zsw_batch b = batch();
+        std::vector<uint8_t> out(bases_.size());
+        ctx_.check(zsw_orient_batch(ctx_.raw(), &b, strand.data(), out.data(), nullptr));
+        std::vector<std::string> reads(size());
+        for (size_t i = 0; i < size(); ++i) reads[i].assign(out.begin() + offsets_[i], out.begin() + offsets_[i + 1]);
+        return reads;
+    }
     // the width that answered each read of the last cascade call (8, 16 or 32)
     const std::vector<uint8_t>& last_tiers() const { return tier_; }
 
@@ -338,6 +360,29 @@ class LocalProfilesBatch : public ProfileBatchBase {
             return (three_pass ? zsw_align_3pass_batch_from : zsw_align_batch_from)(ctx_.raw(), &b, width, preset_, seq_is_query, aln, st,
                                                                                    tier_.data(), inc, op, cap, total, nullptr);
         });
+    }
+    std::vector<MaybeAligned<Alignment>> align_strands_from(const std::string& seq, bool seq_is_query, int width) {
+        set_reference(seq);
+        zsw_batch b = batch();
+        tier_.assign(size(), 0);
+        strand_.assign(size(), 0);
+        return collect([&](zsw_alignment* aln, uint8_t* st, uint32_t* inc, uint8_t* op, uint64_t cap, uint64_t* total) {
+            return zsw_align_3pass_strands_batch_from(ctx_.raw(), &b, width, preset_, seq_is_query, aln, st, tier_.data(), strand_.data(), inc, op, cap, total,
+                                                      nullptr);
+        });
+    }
+    std::vector<MaybeAligned<uint32_t>> score_strands_from(const std::string& reference, int width) {
+        set_reference(reference);
+        const size_t n = size();
+        zsw_batch b = batch();
+        std::vector<uint32_t> score(n);
+        std::vector<uint8_t> status(n);
+        tier_.assign(n, 0);
+        strand_.assign(n, 0);
+        ctx_.check(zsw_score_strands_batch_from(ctx_.raw(), &b, width, preset_, score.data(), status.data(), tier_.data(), strand_.data(), nullptr));
+        std::vector<MaybeAligned<uint32_t>> out(n);
+        for (size_t i = 0; i < n; ++i) out[i] = {(Status)status[i], score[i]};
+        return out;
     }
     std::vector<MaybeAligned<ScoreAndRanges>> ranges_from(const std::string& reference, int width) {
         set_reference(reference);
@@ -365,7 +410,7 @@ class LocalProfilesBatch : public ProfileBatchBase {
         return out;
     }
     int preset_;
-    std::vector<uint8_t> tier_;
+    std::vector<uint8_t> tier_, strand_;
 };
 
 // The other role of the striped functions (sw/mod.rs:63-67; SharedProfiles, profile_set.rs:552-560;

@@ -44,6 +44,7 @@ SYMBOLS = [
     "zsw_group_create", "zsw_group_destroy", "zsw_group_size", "zsw_group_context", "zsw_group_last_error_string", "zsw_group_set_scoring",
     "zsw_group_set_reference", "zsw_group_score_batch_from", "zsw_group_score_batch_from_device", "zsw_group_align_batch_from",
     "zsw_group_align_3pass_batch_from",
+    "zsw_set_complement", "zsw_score_strands_batch_from", "zsw_orient_batch", "zsw_align_3pass_strands_batch_from", "zsw_strand_counts", "zsw_debug_strand_records",
 ]
 
 
@@ -157,5 +158,11 @@ def load() -> C.CDLL:
     lib.zsw_group_score_batch_from_device.argtypes = [vp, C.POINTER(ZswBatch), C.c_int, C.c_int, C.POINTER(vp), C.POINTER(vp)]
     lib.zsw_group_align_batch_from.argtypes = [vp, C.POINTER(ZswBatch), C.c_int, C.c_int, C.c_int, vp, vp, vp, vp, vp, C.c_uint64, C.POINTER(C.c_uint64)]
     lib.zsw_group_align_3pass_batch_from.argtypes = lib.zsw_group_align_batch_from.argtypes
+    lib.zsw_set_complement.argtypes = [vp, vp]
+    lib.zsw_score_strands_batch_from.argtypes = [vp, C.POINTER(ZswBatch), C.c_int, C.c_int, u32p, u8p, u8p, u8p, vp]
+    lib.zsw_orient_batch.argtypes = [vp, C.POINTER(ZswBatch), u8p, u8p, vp]
+    lib.zsw_align_3pass_strands_batch_from.argtypes = [vp, C.POINTER(ZswBatch), C.c_int, C.c_int, C.c_int, vp, u8p, u8p, u8p, u32p, u8p, C.c_uint64, C.POINTER(C.c_uint64), vp]
+    lib.zsw_strand_counts.argtypes = [vp, C.POINTER(C.c_uint64)]
+    lib.zsw_debug_strand_records.argtypes = [vp, vp]
     _lib = lib
     return lib

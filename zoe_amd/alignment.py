@@ -271,6 +271,44 @@ class SwContext:
         self._cert_records = records
         self.check(self.lib.zsw_debug_cert_records(self.h, C.c_void_p(records.data_ptr() if records is not None else None)))
 
+    def debug_strand_records(self, records=None):
+        """zsw_debug_strand_records (tests): the strand-aware calls write 8 int32 per read — support of the anchor vote forward /
+        reverse, whole-reference bound forward / reverse (-1: none), the strand that ran first, 1 = settled by proof, 0, 0 — into
+        `records` (a CUDA int32 tensor of 8 * n_reads elements that the caller keeps alive); None switches it off."""
+        if records is not None:
+            assert records.is_cuda and records.dtype == _torch().int32 and records.is_contiguous()
+        self._strand_records = records
+        self.check(self.lib.zsw_debug_strand_records(self.h, C.c_void_p(records.data_ptr() if records is not None else None)))
+
+    def set_complement(self, table=None):
+        """zsw_set_complement: table[b] = the byte of the base complementary to byte b (256 entries: bytes or a uint8 array);
+        None restores the default, the IUPAC nucleotide complement with the case preserved."""
+        if table is None:
+            self.check(self.lib.zsw_set_complement(self.h, None))
+            return
+        t = np.ascontiguousarray(np.frombuffer(bytes(table), dtype=np.uint8) if isinstance(table, (bytes, bytearray)) else table, dtype=np.uint8)
+        if t.size != 256:
+            raise ValueError("a complement table has 256 entries")
+        self.check(self.lib.zsw_set_complement(self.h, t.ctypes.data))
+
+    def orient(self, reads: "ReadBatch", strand) -> "ReadBatch":
+        """zsw_orient_batch: a ReadBatch of the same layout with every read of strand[i] != 0 replaced by its reverse complement
+        (`Nucleotides::to_reverse_complement`); `strand`: a CUDA uint8 tensor with one entry per read."""
+        torch = _torch()
+        assert strand.is_cuda and strand.dtype == torch.uint8 and strand.numel() >= reads.n_reads
+        strand = strand.contiguous()
+        out = torch.empty_like(reads.bases)
+        b = reads.c_batch()
+        self.check(self.lib.zsw_orient_batch(self.h, C.byref(b), strand.data_ptr(), out.data_ptr(), self.stream()))
+        return ReadBatch(out, reads.n_reads, fixed_len=reads.fixed_len, offsets=reads.offsets, min_len=reads.min_len)
+
+    def strand_counts(self):
+        """zsw_strand_counts of the last strand-aware call: (settled forward by proof, settled reverse by proof, scored on both
+        strands, answered as reverse)."""
+        c = (C.c_uint64 * 4)()
+        self.check(self.lib.zsw_strand_counts(self.h, c))
+        return tuple(int(x) for x in c)
+
     def set_profile_sequence(self, sequence: bytes):
         """zsw_set_profile_sequence: the sequence the shared profile is built from (the library itself skips the work when it is the
         one already set: no copy of it is kept on this side, which another binding of the same context could leave stale)"""
@@ -465,6 +503,7 @@ class ScoreBatch:
     query_end: Optional["object"] = None
     ref_start: Optional["object"] = None
     query_start: Optional["object"] = None
+    strand: Optional["object"] = None  # strand-aware calls: 0 = the read as given, 1 = its reverse complement
 
     def maybe_aligned(self, i: int):
         st = int(self.status[i])
@@ -480,6 +519,7 @@ class AlignmentBatch:
     inc: np.ndarray
     op: np.ndarray
     tier: Optional[np.ndarray] = None
+    strand: Optional[np.ndarray] = None  # strand-aware calls: 0 = the read as given, 1 = its reverse complement (coordinates are its)
 
     def cigar(self, i: int) -> str:
         r = self.records[i]
@@ -537,7 +577,7 @@ class _ProfileBatchBase:
         self.ctx.set_scoring(self.matrix, self.gap_open, self.gap_extend)
         self.ctx.set_reference(reference)
 
-    def _align(self, seq: SeqSrc, direct, from_width=None, preset=None, three_pass: bool = False) -> AlignmentBatch:
+    def _align(self, seq: SeqSrc, direct, from_width=None, preset=None, three_pass: bool = False, strands: bool = False) -> AlignmentBatch:
         torch = _torch()
         self._prep(seq.seq)
         n = self.reads.n_reads
@@ -545,6 +585,7 @@ class _ProfileBatchBase:
         aln = torch.zeros(max(n, 1) * ALN_DTYPE.itemsize, dtype=torch.uint8, device=dev)
         status = torch.zeros(max(n, 1), dtype=torch.uint8, device=dev)
         tier = torch.zeros(max(n, 1), dtype=torch.uint8, device=dev)
+        strand = torch.zeros(max(n, 1), dtype=torch.uint8, device=dev)
         cap = max(8 * n, 64)  # typical reads need 1-3 ciglets; the call reports the exact total when this is too small
         b = self.reads.c_batch()
         total = C.c_uint64(0)
@@ -553,7 +594,11 @@ class _ProfileBatchBase:
             op = torch.empty(cap, dtype=torch.uint8, device=dev)
             fn_direct = self.ctx.lib.zsw_align_3pass_batch if three_pass else self.ctx.lib.zsw_align_batch
             fn_from = self.ctx.lib.zsw_align_3pass_batch_from if three_pass else self.ctx.lib.zsw_align_batch_from
-            if direct is not None:
+            if strands:  # zsw_align_3pass_strands_batch_from: the cascade's 3-pass call on whichever strand scores higher
+                rc = self.ctx.lib.zsw_align_3pass_strands_batch_from(self.ctx.h, C.byref(b), from_width, preset, int(seq.is_query), aln.data_ptr(),
+                                                                     status.data_ptr(), tier.data_ptr(), strand.data_ptr(), inc.data_ptr(), op.data_ptr(),
+                                                                     cap, C.byref(total), self.ctx.stream())
+            elif direct is not None:
                 rc = fn_direct(self.ctx.h, C.byref(b), direct[0], direct[1], int(seq.is_query), aln.data_ptr(),
                                                   status.data_ptr(), inc.data_ptr(), op.data_ptr(), cap, C.byref(total), self.ctx.stream())
             else:
@@ -568,7 +613,10 @@ class _ProfileBatchBase:
         torch.cuda.synchronize(dev)
         t = int(total.value)
         h_aln, h_status, h_inc, h_op, h_tier = _to_host(aln[: n * ALN_DTYPE.itemsize], status[:n], inc[:t], op[:t], tier[:n])
-        return AlignmentBatch(h_status, h_aln.view(ALN_DTYPE), h_inc.view(np.uint32), h_op, h_tier if direct is None else None)
+        out = AlignmentBatch(h_status, h_aln.view(ALN_DTYPE), h_inc.view(np.uint32), h_op, h_tier if direct is None else None)
+        if strands:
+            out.strand = _to_host(strand[:n])[0]
+        return out
 
 
 class StripedProfileBatch(_ProfileBatchBase):
@@ -696,6 +744,40 @@ class LocalProfilesBatch(_ProfileBatchBase):
 
     def sw_score_from_i32(self, reference) -> ScoreBatch:
         return self._score_from(reference, 32)
+
+    def _score_strands_from(self, reference, width: int) -> ScoreBatch:
+        """zsw_score_strands_batch_from: per read the better of sw_score_from_i{width} on the read and on its reverse complement
+        (ties: forward); ScoreBatch.strand says which one answered."""
+        torch = _torch()
+        self._prep(reference)
+        n = self.reads.n_reads
+        dev = self.reads.bases.device
+        score = torch.empty(max(n, 1), dtype=torch.int32, device=dev)
+        status, tier, strand = (torch.empty(max(n, 1), dtype=torch.uint8, device=dev) for _ in range(3))
+        b = self.reads.c_batch()
+        self.ctx.check(self.ctx.lib.zsw_score_strands_batch_from(self.ctx.h, C.byref(b), width, self.preset, score.data_ptr(), status.data_ptr(),
+                                                                 tier.data_ptr(), strand.data_ptr(), self.ctx.stream()))
+        return ScoreBatch(score[:n], status[:n], tier=tier[:n], strand=strand[:n])
+
+    def sw_score_strands_from_i8(self, reference) -> ScoreBatch:
+        return self._score_strands_from(reference, 8)
+
+    def sw_score_strands_from_i16(self, reference) -> ScoreBatch:
+        return self._score_strands_from(reference, 16)
+
+    def sw_score_strands_from_i32(self, reference) -> ScoreBatch:
+        return self._score_strands_from(reference, 32)
+
+    def sw_align_strands_from_i8_3pass(self, seq: SeqSrc) -> AlignmentBatch:
+        """zsw_align_3pass_strands_batch_from: sw_align_from_i8_3pass of the read or of its reverse complement, whichever scores
+        higher (ties: forward); AlignmentBatch.strand says which, and the coordinates are those of the sequence as aligned."""
+        return self._align(seq, None, 8, self.preset, three_pass=True, strands=True)
+
+    def sw_align_strands_from_i16_3pass(self, seq: SeqSrc) -> AlignmentBatch:
+        return self._align(seq, None, 16, self.preset, three_pass=True, strands=True)
+
+    def sw_align_strands_from_i32_3pass(self, seq: SeqSrc) -> AlignmentBatch:
+        return self._align(seq, None, 32, self.preset, three_pass=True, strands=True)
 
     def _ranges_from(self, seq: SeqSrc, width: int) -> ScoreBatch:
         """profile_set.rs:313-362: sw_score_ranges over the tiers i{width} -> i32 of this preset"""

@@ -5,6 +5,7 @@
 
 #include "zsw_context.hpp"
 #include "zsw_cert.hpp"
+#include "zsw_strand.hpp"
 #include "zsw_synth.h"
 
 using namespace zsw;
@@ -1127,6 +1128,7 @@ void zsw_destroy(zsw_context* ctx) {
     for (DevBuf& b : ctx->a_ws) b.release();
     for (DevBuf& b : ctx->r_ws) b.release();
     for (DevBuf& b : ctx->sh_ws) b.release();
+    for (DevBuf& b : ctx->st_ws) b.release();
     seed_index_release(&ctx->seed);
     seed_index_release(&ctx->seed_rev);
     ctx->d_ref_rev.release();
@@ -1440,6 +1442,7 @@ zsw_error zsw_set_option(zsw_context* ctx, zsw_option option, int64_t value) {
             ZSW_HIP(ctx, hipDeviceSynchronize());
             ctx->d_prune.release();
             ctx->d_seed_work.release();
+            for (int k : {ST_IN, ST_ORIENT, ST_SECOND, ST_ORIENT_FINAL}) ctx->st_ws[k].release();  // the strand calls' copies of the batch
         }
         return ZSW_OK;
     }

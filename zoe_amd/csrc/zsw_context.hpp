@@ -97,6 +97,14 @@ struct zsw_context {
     // seeded pass over the reversed reads (zsw_capi_shared.hip, run_ranges_shared); built with the first such call
     zsw::SeedIndex seed_shared_rev;
     bool shared_seedable = false;  // set by the shared entry points whose kernels can take the seeded pass (score; ends with MODE 3)
+    // strand-aware calls (zsw_strand.hip): the complement table (empty = the IUPAC default), workspace — the staged batch of a host
+    // call, the oriented copy, the second batch of the reads scored on both strands and its results, 8 bytes per read of what the
+    // seed kernel found, the list of unsettled reads and the counters of zsw_strand_counts — and the host copy a host batch is
+    // oriented into for the 3-pass call
+    std::vector<uint8_t> complement;
+    zsw::DevBuf st_ws[24];
+    std::vector<uint8_t> h_orient;
+    int32_t* strand_dbg = nullptr;  // zsw_debug_strand_records
 };
 
 namespace zsw {
@@ -192,6 +200,11 @@ struct Staged {
     uint32_t* d_qend = nullptr;
 };
 
+// zsw_capi.hip: the bodies of zsw_score_batch(_from) and zsw_align_3pass_batch(_from), which the strand-aware calls run on oriented batches
+zsw_error run_score(zsw_context* ctx, const zsw_batch* reads, const ResultRule& rule, bool want_ends, uint32_t* out_score, uint8_t* out_status,
+                    uint8_t* out_tier, uint32_t* out_rend, uint32_t* out_qend, void* stream);
+zsw_error run_threepass(zsw_context* ctx, const zsw_batch* reads, const ResultRule& rule, int invert, zsw_alignment* out_aln, uint8_t* out_status,
+                        uint8_t* out_tier, uint32_t* out_inc, uint8_t* out_op, uint64_t ciglet_cap, uint64_t* out_n_ciglets, void* stream);
 // zsw_capi.hip
 zsw_error stage(zsw_context* ctx, const zsw_batch* reads, hipStream_t stream, bool want_tier, bool want_ends, uint32_t* out_score,
                 uint8_t* out_status, uint8_t* out_tier, uint32_t* out_rend, uint32_t* out_qend, Staged* st, bool defer_bases_copy = false);

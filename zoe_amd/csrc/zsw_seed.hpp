@@ -293,6 +293,115 @@ ZSW_SEED_HD SeedRead seed_read(const SeedParams& p, int len, GetCell cell, Looku
     return out;
 }
 
+// ---- whole-reference bound (zsw_strand.hip: which strand of a read has to be scored at all) ---------------------------------
+// Claim W: no local alignment of the sequence against the reference scores more than SeedWhole::u (host model:
+// tests/models/strand_bound.cpp, against the full Gotoh matrix). It is the "above" claim with the diagonal restriction dropped:
+// `set` holds the sampled k-mers that are usable and occur NOWHERE in the index, so for a path anywhere in the matrix "every
+// exact occurrence it uses lies where the set allows one" is vacuously true — it uses none. A path that spans such a k-mer
+// completely cannot traverse it exactly and loses lambda of the span's potential for it; seed_span_bound maximises what is left
+// over the columns a path may span. The index enters every reference window with up to SEED_WILD_MAX non-good residues under
+// every spelling, so "occurs nowhere" already covers the windows a path can cross at the price of a few wildcards, and
+// seed_analyze caps lambda by what SEED_WILD_MAX + 1 of them cost: a path through a window the index left out pays lambda too.
+// The sweep is seed_read's (layout, usable k-mers, the run >= lam rule for the columns in front of a k-mer, seed_lambda).
+// A sequence that is not swept (shorter than min_len, no k-mer fits) gets u = t_all, the potential of all its columns.
+struct SeedSweep {
+    int m, stride, c0, lam;
+    int t_all;
+    int pot_lo[SEED_MAX_KMERS], pot_hi[SEED_MAX_KMERS];
+    bool usable[SEED_MAX_KMERS];
+    uint32_t codes[SEED_MAX_KMERS];
+};
+
+struct SeedWhole {
+    int t_all;    // potential of all columns
+    int u;        // claim W's bound
+    int support;  // of the anchor vote (seed_vote): how many sampled k-mers agree on a diagonal
+};
+
+template <class GetCell>
+ZSW_SEED_HD void seed_whole_sweep(const SeedParams& p, int len, int min_len, GetCell cell, SeedSweep* s) {
+    seed_layout(len, p.K, p.spacer, &s->m, &s->stride, &s->c0);
+    if (len < min_len) s->m = 0;
+    const int m = s->m, stride = s->stride, c0 = s->c0;
+    s->lam = seed_lambda(p, stride);
+    int pot = 0, c = 0;
+#pragma unroll
+    for (int j = 0; j < SEED_MAX_KMERS; ++j) {
+        s->pot_lo[j] = s->pot_hi[j] = 0;
+        s->usable[j] = false;
+        s->codes[j] = 0;
+        if (j >= m) continue;
+        const int cj = c0 + j * stride;
+        int run = p.ins_col;  // what an insertion run from inside the previous k-mer loses on its way into this one (seed_read)
+        for (; c < cj; ++c) {
+            const int wpc = (int)(cell(c) & 0xffu);
+            pot += wpc;
+            run += wpc + p.ge;
+        }
+        uint32_t code = 0;
+        bool ok = j == 0 || run >= s->lam;
+        for (int k = 0; k < p.K; ++k, ++c) {
+            const uint32_t x = cell(c);
+            pot += (int)(x & 0xffu);
+            ok = ok && (x >> 8) != 0xffu;
+            code |= ((x >> 8) & 3u) << (2 * k);
+            if (k == 0) s->pot_lo[j] = pot;
+            if (k == p.K - 2) s->pot_hi[j] = pot;
+        }
+        s->usable[j] = ok;
+        s->codes[j] = code;  // looked up either way; seed_whole_finish uses the entry of a usable k-mer only
+    }
+    for (; c < len; ++c) pot += (int)(cell(c) & 0xffu);
+    s->t_all = pot;
+}
+
+// f1s / l1s: the index entries of s.codes (first / last position + 1, 0 = the k-mer does not occur)
+ZSW_SEED_HD SeedWhole seed_whole_finish(const SeedParams& p, const SeedSweep& s, const uint32_t* f1s, const uint32_t* l1s) {
+    SeedWhole out;
+    out.t_all = s.t_all;
+    out.u = s.t_all;
+    out.support = 0;
+    if (s.m == 0) return out;
+    bool set[SEED_MAX_KMERS], has[SEED_MAX_KMERS];
+    int dlo[SEED_MAX_KMERS], dhi[SEED_MAX_KMERS];
+#pragma unroll
+    for (int j = 0; j < SEED_MAX_KMERS; ++j) {
+        const bool in = j < s.m && s.usable[j];
+        has[j] = in && f1s[j] != 0;
+        set[j] = in && f1s[j] == 0;
+        const int cj = s.c0 + j * s.stride;
+        dlo[j] = has[j] ? (int)(f1s[j] - 1) - cj : 0;
+        dhi[j] = has[j] ? (int)(l1s[j] - 1) - cj : 0;
+    }
+    int dt = 0;
+    out.support = seed_vote(s.m, has, dlo, dhi, p.tol, &dt);
+    out.u = seed_span_bound(s.m, s.pot_lo, s.pot_hi, s.t_all, set, s.lam);
+    return out;
+}
+
+template <class GetCell, class Lookup>
+ZSW_SEED_HD SeedWhole seed_whole_bound(const SeedParams& p, int len, int min_len, GetCell cell, Lookup look) {
+    SeedSweep s;
+    seed_whole_sweep(p, len, min_len, cell, &s);
+    uint32_t f1s[SEED_MAX_KMERS], l1s[SEED_MAX_KMERS];
+#pragma unroll
+    for (int j = 0; j < SEED_MAX_KMERS; ++j) {
+        f1s[j] = l1s[j] = 0;
+        look(s.codes[j], &f1s[j], &l1s[j]);
+    }
+    return seed_whole_finish(p, s, f1s, l1s);
+}
+
+// A bound as the 16 bits the strand pass stores per read: 0xffff stands for "no bound" (a potential beyond 65,534)
+ZSW_SEED_HD uint32_t seed_bound_u16(int u) { return u < 0 || u > 0xfffe ? 0xffffu : (uint32_t)u; }
+
+// The strand decision: p ran first and scored s_p (some_p: its status is SOME), u_o bounds the other strand o. True = o need not
+// be scored: it ranks below p, or ties it while p is the forward strand (ties go forward). u_o < 0: no bound.
+ZSW_SEED_HD bool seed_strand_settled(bool some_p, long long s_p, long long u_o, int p) {
+    if (!some_p || u_o < 0) return false;
+    return u_o < s_p || (u_o == s_p && p == 0);
+}
+
 // ---- banded pass (seed_band_kernel): the computed cells are a band of diagonals around the anchor, strip by strip ----------
 // Strip k holds query columns [kC, (k+1)C) and the reference rows [top_k, bot_k) = [dt + kC - Wu, dt + (k+1)C + Wd) (clamped to
 // the reference; dt = the smaller / larger anchor of the lane's two reads). Cells of a strip's columns in rows < top_k lie ABOVE
