@@ -150,6 +150,7 @@ unsafe extern "C" {
     fn zsw_debug_band_records(ctx: *mut ZswContext, records: *mut i32) -> i32;
     fn zsw_debug_cert_records(ctx: *mut ZswContext, records: *mut i32) -> i32;
     fn zsw_debug_strand_records(ctx: *mut ZswContext, records: *mut i32) -> i32;
+    fn zsw_debug_score_launches(ctx: *mut ZswContext, records: *mut u32, capacity: u32, out_n: *mut u32) -> i32;
     fn zsw_prune_rescored(ctx: *mut ZswContext, out_reads: *mut u64) -> i32;
     fn zsw_set_option(ctx: *mut ZswContext, option: i32, value: i64) -> i32;
 }
@@ -775,6 +776,22 @@ impl GpuContext {
     /// `records` must be null or device memory for `8 * n_reads` `i32` that outlives the following calls.
     pub unsafe fn debug_strand_records(&self, records: *mut i32) -> Result<(), GpuError> {
         self.check(zsw_debug_strand_records(self.raw, records), 0, 0)
+    }
+
+    /// `zsw_debug_score_launches`: tests only — the score kernels the last call launched, one `[kind, G, C, mode]` per launch in
+    /// launch order (`kind`: `zsw_launch_kind` of the header; `(G, C)`: the strip configuration; `mode`: the MODE the kernel was
+    /// built with). Host bookkeeping: no device work, no synchronisation.
+    pub fn debug_score_launches(&self) -> Result<Vec<[u32; 4]>, GpuError> {
+        let mut n = 0u32;
+        // SAFETY: live context; capacity 0 writes nothing but the count
+        self.check(unsafe { zsw_debug_score_launches(self.raw, std::ptr::null_mut(), 0, &mut n) }, 0, 0)?;
+        let mut rec = vec![[0u32; 4]; n as usize];
+        if n > 0 {
+            // SAFETY: `rec` holds 4 * n entries; the list does not change between the two calls (no call staged a batch)
+            self.check(unsafe { zsw_debug_score_launches(self.raw, rec.as_mut_ptr() as *mut u32, n, &mut n) }, 0, 0)?;
+        }
+        rec.truncate(n as usize);
+        Ok(rec)
     }
 
     /// Per read: `sneaky_snake(&reference[start..start+len], read, threshold)` -> `Option<bool>`.

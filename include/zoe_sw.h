@@ -462,6 +462,37 @@ zsw_error zsw_debug_cert_records(zsw_context* ctx, int32_t* records);
  * 8 int32 per read of the following calls, NULL = off (the default). Results do not change. */
 zsw_error zsw_debug_strand_records(zsw_context* ctx, int32_t* records);
 
+/* Tests only (tests/test_gpu_strip_edges.py): which score kernels the context's last call launched. The score launchers
+ * (launch_score and launch_score_rev, zsw_score.hip) note every kernel launch they issue in a host-side list that is emptied
+ * when a call stages its batch; no device work, no synchronisation, results do not change. A record is four uint32:
+ * (kind, G, C, mode) — kind is a zsw_launch_kind, (G, C) the strip configuration the kernel was instantiated for (lanes per read
+ * pair, columns per lane; 0, 0 for the exact 32-bit kernel), mode the MODE the kernel was instantiated with (0 score, 1 + ref_end,
+ * 2 + both ends: a request the launcher serves with another instantiation, such as mode 1 of the 8..32-letter kernels or
+ * mode 3 of the seeded passes' hand-backs, shows the one that ran; ZSW_LAUNCH_SEED_BAND alone can show 3, seed_band_kernel has
+ * that instantiation: ends + "the maximum sits in one cell"). For the two seeded kinds (G, C) is the configuration of the length
+ * class the pass ran for. Launches that decide on the device whether they do anything (ScoreArgsV2::gate_lo / gate_hi) are
+ * recorded as issued; so is every tile of the tiled kernels. A launcher that finds no item on the host launches and records nothing. A strand-aware call reports the
+ * launches of the last batch it staged. records: host memory for 4 * capacity uint32, may be NULL when capacity is 0; *out_n is
+ * the number of launches. When capacity < *out_n nothing is written (ZSW_OK all the same): call again with that capacity. */
+typedef enum zsw_launch_kind {
+    ZSW_LAUNCH_V1_FAST = 0,        /* score_kernel, four-entry table (query residues >= 4 score 0) */
+    ZSW_LAUNCH_V1_BIASED = 1,      /* score_kernel, biased byte table */
+    ZSW_LAUNCH_V2 = 2,             /* score_kernel_v2 */
+    ZSW_LAUNCH_WIDE = 3,           /* score_kernel_v2, LDS table (8..32 letters) */
+    ZSW_LAUNCH_V1_FAST_REV = 4,    /* reverse pass of the ranges: score_kernel reversed, four-entry table */
+    ZSW_LAUNCH_V1_BIASED_REV = 5,  /* ... biased byte table */
+    ZSW_LAUNCH_WIDE_REV = 6,       /* ... LDS table */
+    ZSW_LAUNCH_TILE_V2 = 7,        /* one tile of reads longer than the widest strip configuration */
+    ZSW_LAUNCH_TILE_WIDE = 8,      /* ... LDS table */
+    ZSW_LAUNCH_TILE_W32 = 9,       /* ... in 32-bit lanes (scores beyond the packed range; the reverse pass of such reads) */
+    ZSW_LAUNCH_EXACT32 = 10,       /* exact32_kernel over a whole batch or length class */
+    ZSW_LAUNCH_EXACT32_WORKLIST = 11, /* exact32_kernel over the device-side worklist (usually empty) */
+    ZSW_LAUNCH_SEED_WINDOW = 12,   /* seeded pass: whole rows around the anchor (seed_window_kernel) */
+    ZSW_LAUNCH_SEED_BAND = 13,     /* seeded pass: band of diagonals (seed_band_kernel), one record per tier */
+    ZSW_LAUNCH_PRUNED = 14         /* column-pruned pass (strip + window kernels of zsw_score_prune.hip), one record per pass */
+} zsw_launch_kind;
+zsw_error zsw_debug_score_launches(zsw_context* ctx, uint32_t* records, uint32_t capacity, uint32_t* out_n);
+
 /* Reads of the context's last call that the seeded (or column-pruned) first pass handed back — no anchor, or a bound check
  * failed — and that were scored over all their cells (0 if the call did not take such a pass). Synchronises the device.
  * Read-as-profile role, every entry point (score, ends, ranges, alignment, 3-pass alignment): the hand-backs of the FORWARD pass.

@@ -30,6 +30,9 @@ DEBUG_SCORE_PRUNE, DEBUG_SCORE_PRUNE_ANY_SIZE, DEBUG_PRUNE_STRIP, DEBUG_ALIGN_LO
 DEBUG_NO_ROW_CHUNKS = 8192
 DEBUG_RANGES_EXACT_REVERSE = 16384
 DEBUG_ALIGN_NO_CERTIFICATE = 32768
+# zsw_launch_kind: the first entry of a zsw_debug_score_launches record
+(LAUNCH_V1_FAST, LAUNCH_V1_BIASED, LAUNCH_V2, LAUNCH_WIDE, LAUNCH_V1_FAST_REV, LAUNCH_V1_BIASED_REV, LAUNCH_WIDE_REV, LAUNCH_TILE_V2, LAUNCH_TILE_WIDE,
+ LAUNCH_TILE_W32, LAUNCH_EXACT32, LAUNCH_EXACT32_WORKLIST, LAUNCH_SEED_WINDOW, LAUNCH_SEED_BAND, LAUNCH_PRUNED) = range(15)
 OPTION_EXACT_PRUNING = 1
 INT_TYPES = {"i8": 0, "i16": 1, "i32": 2, "u8": 3, "u16": 4, "u32": 5}
 
@@ -44,7 +47,7 @@ SYMBOLS = [
     "zsw_group_create", "zsw_group_destroy", "zsw_group_size", "zsw_group_context", "zsw_group_last_error_string", "zsw_group_set_scoring",
     "zsw_group_set_reference", "zsw_group_score_batch_from", "zsw_group_score_batch_from_device", "zsw_group_align_batch_from",
     "zsw_group_align_3pass_batch_from",
-    "zsw_set_complement", "zsw_score_strands_batch_from", "zsw_orient_batch", "zsw_align_3pass_strands_batch_from", "zsw_strand_counts", "zsw_debug_strand_records",
+    "zsw_set_complement", "zsw_score_strands_batch_from", "zsw_orient_batch", "zsw_align_3pass_strands_batch_from", "zsw_strand_counts", "zsw_debug_strand_records", "zsw_debug_score_launches",
 ]
 
 
@@ -164,5 +167,6 @@ def load() -> C.CDLL:
     lib.zsw_align_3pass_strands_batch_from.argtypes = [vp, C.POINTER(ZswBatch), C.c_int, C.c_int, C.c_int, vp, u8p, u8p, u8p, u32p, u8p, C.c_uint64, C.POINTER(C.c_uint64), vp]
     lib.zsw_strand_counts.argtypes = [vp, C.POINTER(C.c_uint64)]
     lib.zsw_debug_strand_records.argtypes = [vp, vp]
+    lib.zsw_debug_score_launches.argtypes = [vp, u32p, C.c_uint32, u32p]
     _lib = lib
     return lib

@@ -280,6 +280,16 @@ class SwContext:
         self._strand_records = records
         self.check(self.lib.zsw_debug_strand_records(self.h, C.c_void_p(records.data_ptr() if records is not None else None)))
 
+    def debug_score_launches(self):
+        """zsw_debug_score_launches (tests): the score kernels the last call launched, as a list of (kind, G, C, mode) tuples in
+        launch order — kind is a _lib.LAUNCH_* value, (G, C) the strip configuration, mode the MODE the kernel was built with."""
+        n = C.c_uint32(0)
+        self.check(self.lib.zsw_debug_score_launches(self.h, None, 0, C.byref(n)))
+        rec = np.zeros((n.value, 4), dtype=np.uint32)
+        if n.value:
+            self.check(self.lib.zsw_debug_score_launches(self.h, C.c_void_p(rec.ctypes.data), n.value, C.byref(n)))
+        return [tuple(int(v) for v in r) for r in rec[: n.value]]
+
     def set_complement(self, table=None):
         """zsw_set_complement: table[b] = the byte of the base complementary to byte b (256 entries: bytes or a uint8 array);
         None restores the default, the IUPAC nucleotide complement with the case preserved."""

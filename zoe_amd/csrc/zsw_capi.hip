@@ -90,6 +90,7 @@ zsw_error stage(zsw_context* ctx, const zsw_batch* reads, hipStream_t stream, bo
                 uint32_t* out_score, uint8_t* out_status, uint8_t* out_tier, uint32_t* out_rend, uint32_t* out_qend,
                 Staged* st, bool defer_bases_copy) {
     if (!ctx) return ZSW_ERR_INVALID_ARGUMENT;
+    ctx->score_launches.clear();  // zsw_debug_score_launches reports the launches of this call
     if (!ctx->scoring_set || !ctx->reference_set) return fail(ctx, ZSW_ERR_NOT_CONFIGURED, "scoring/reference not set");
     if (!reads || !out_score || !out_status) return fail(ctx, ZSW_ERR_INVALID_ARGUMENT, "null argument");
     if (reads->n_reads > 0x7fffffffull) return fail(ctx, ZSW_ERR_INVALID_ARGUMENT, "n_reads > 2^31-1 per call");
@@ -286,6 +287,7 @@ ScoreWorkspace score_ws(zsw_context* ctx) {
     w.tile_state = ctx->d_tile_state.as<uint4>();
     w.side = ctx->side;
     w.debug = ctx->flags();
+    w.launch_log = &ctx->score_launches;
     if (ctx->seed_ready) {
         w.seed = ctx->shared_call ? &ctx->seed_shared : &ctx->seed;
         w.seed_work = ctx->d_seed_work.as<uint8_t>();
@@ -1430,6 +1432,15 @@ zsw_error zsw_debug_band_records(zsw_context* ctx, int32_t* records) {
 zsw_error zsw_debug_cert_records(zsw_context* ctx, int32_t* records) {
     if (!ctx) return ZSW_ERR_INVALID_ARGUMENT;
     ctx->cert_dbg = records;
+    return ZSW_OK;
+}
+
+zsw_error zsw_debug_score_launches(zsw_context* ctx, uint32_t* records, uint32_t capacity, uint32_t* out_n) {
+    if (!ctx) return ZSW_ERR_INVALID_ARGUMENT;
+    if (!out_n || (capacity && !records)) return fail(ctx, ZSW_ERR_INVALID_ARGUMENT, "null argument");
+    const size_t n = ctx->score_launches.size() / 4;
+    *out_n = (uint32_t)n;
+    if (n <= capacity && n) memcpy(records, ctx->score_launches.data(), n * 4 * sizeof(uint32_t));
     return ZSW_OK;
 }
 

@@ -121,7 +121,13 @@ struct ScoreWorkspace {
     int32_t* band_dbg = nullptr;  // zsw_debug_band_records
     unsigned long long* chunk_keys = nullptr;  // one per read: row-chunked full pass over the reads the seeded pass hands back (long references)
     uint32_t debug = 0;           // ZSW_DEBUG_* bits of the context (zsw_debug_set) | its options: kernel-selection overrides
+    std::vector<uint32_t>* launch_log = nullptr;  // zsw_debug_score_launches: the context's list, four entries per kernel launch
 };
+
+// zsw_debug_score_launches: one record per kernel launch of the score launchers (host bookkeeping only)
+inline void note_launch(std::vector<uint32_t>* log, uint32_t kind, int G, int C, int mode) {
+    if (log) log->insert(log->end(), {kind, (uint32_t)G, (uint32_t)C, (uint32_t)mode});
+}
 
 hipError_t launch_score(const ScoringDev* d_sc, const ScoringDev& h_sc, const BatchDev& b, uint32_t max_len,
                         const uint8_t* d_ref, uint32_t ref_len, const ResultRule& rule, const ScoreOut& out,

@@ -477,12 +477,15 @@ hipError_t launch_score(const ScoringDev* d_sc, const ScoringDev& h_sc, const Ba
     a2.tile_state = nullptr;
     a2.rev_ref_end = nullptr;
     a2.rev_query_end = nullptr;
+    std::vector<uint32_t>* const launches = ws.launch_log;  // zsw_debug_score_launches
     auto launch_one = [&](const BatchDev& bb, int g, int c) -> hipError_t {
         if (wide) {
             if (build_tables_wide(h_sc, g, &a2)) {
                 a2.b = bb;
+                if (bb.n_items) note_launch(launches, ZSW_LAUNCH_WIDE, g, c, mode == 0 ? 0 : 2);
                 return launch_table_cfg_v2_wide(a2, g, c, mode, stream);
             }
+            note_launch(launches, ZSW_LAUNCH_EXACT32, 0, 0, std::min(mode, 2));
             hipLaunchKernelGGL(exact32_kernel, dim3(exact_grid), dim3(64), 0, stream, bb, (const uint32_t*)nullptr,
                                (const uint32_t*)nullptr, d_ref, ref_len, d_sc, rule, out, ws.scratch, (uint32_t)ws.slots,
                                ws.scratch_len, (const uint32_t*)nullptr, (const uint32_t*)nullptr);
@@ -490,9 +493,11 @@ hipError_t launch_score(const ScoringDev* d_sc, const ScoringDev& h_sc, const Ba
         }
         if (use_v2 && build_tables_v2(h_sc, g, &a2)) {
             a2.b = bb;
+            if (bb.n_items) note_launch(launches, ZSW_LAUNCH_V2, g, c, std::min(mode, 2));
             return launch_table_cfg_v2(a2, g, c, mode, stream);
         }
         a.b = bb;
+        if (bb.n_items) note_launch(launches, fast ? ZSW_LAUNCH_V1_FAST : ZSW_LAUNCH_V1_BIASED, g, c, std::min(mode, 2));
         return launch_table_cfg(a, g, c, fast, mode, stream);
     };
     // Reads longer than the widest strip configuration: TILE_COLS query columns per launch, the strip boundary of every
@@ -518,6 +523,7 @@ hipError_t launch_score(const ScoringDev* d_sc, const ScoringDev& h_sc, const Ba
                 a2.tile_q0 = t * (uint32_t)TILE_COLS;
                 a2.tile_in = t ? buf[(t - 1) & 1] : nullptr;
                 a2.tile_out = t + 1 < n_tiles ? buf[t & 1] : nullptr;
+                if (a2.b.n_items) note_launch(launches, wide ? ZSW_LAUNCH_TILE_WIDE : ZSW_LAUNCH_TILE_V2, TILE_G, TILE_C, mode == 0 ? 0 : 2);
                 hipError_t te = launch_tile_v2(a2, wide, mode, stream);
                 if (te != hipSuccess) return te;
             }
@@ -552,6 +558,7 @@ hipError_t launch_score(const ScoringDev* d_sc, const ScoringDev& h_sc, const Ba
                         a2.tile_q0 = t * (uint32_t)TILE_COLS;
                         a2.tile_in = t ? buf[(t - 1) & 1] : nullptr;
                         a2.tile_out = t + 1 < n_tiles ? buf[t & 1] : nullptr;
+                        if (a2.b.n_items) note_launch(launches, ZSW_LAUNCH_TILE_W32, TILE_G, TILE_C, mode == 0 ? 0 : 2);
                         we = launch_tile_w32(a2, out.fb_list + first, mode, stream);
                         if (we != hipSuccess) return we;
                     }
@@ -559,11 +566,13 @@ hipError_t launch_score(const ScoringDev* d_sc, const ScoringDev& h_sc, const Ba
                 return hipSuccess;
             }
         }
+        note_launch(launches, ZSW_LAUNCH_EXACT32_WORKLIST, 0, 0, std::min(mode, 2));
         hipLaunchKernelGGL(exact32_kernel, dim3(exact_grid), dim3(64), 0, stream, b, out.fb_list, out.fb_count, d_ref, ref_len, d_sc,
                            rule, out, ws.scratch, (uint32_t)ws.slots, ws.scratch_len, (const uint32_t*)nullptr, (const uint32_t*)nullptr);
         return hipGetLastError();
     };
     auto exact_all = [&](const BatchDev& bb) {
+        note_launch(launches, ZSW_LAUNCH_EXACT32, 0, 0, std::min(mode, 2));
         hipLaunchKernelGGL(exact32_kernel, dim3(exact_grid), dim3(64), 0, stream, bb, (const uint32_t*)nullptr,
                            (const uint32_t*)nullptr, d_ref, ref_len, d_sc, rule, out, ws.scratch, (uint32_t)ws.slots, ws.scratch_len, (const uint32_t*)nullptr, (const uint32_t*)nullptr);
         return hipGetLastError();
@@ -602,7 +611,7 @@ hipError_t launch_score(const ScoringDev* d_sc, const ScoringDev& h_sc, const Ba
         pe = launch_score_seeded(ap, g, c, longest, *ws.seed, ws.seed_work + work_off, seed_workspace_bytes(bb.n_items, longest, band_grid_cap), ws.seed_gtab,
                                  ws.prune_fail_list + list_off, counter, mode, band_ok ? &ab : nullptr, gtab_band, ws.band_dbg,
                                  (ws.debug & ZSW_DEBUG_SEED_WIDE_BAND) ? 0xffffffffu : (ws.debug & ZSW_DEBUG_SCORE_PRUNE_ANY_SIZE) ? 0u : SEED_NARROW_MIN_READS, band_grid_cap, stream,
-                                 ws.window_timer, out.narrow_only, out.reads_reversed && out.skip_handed_back);
+                                 ws.window_timer, out.narrow_only, out.reads_reversed && out.skip_handed_back, launches);
         if (pe != hipSuccess) return pe;
         ap.b.items = ws.prune_fail_list + list_off;
         ap.n_items_dev = counter;
@@ -623,6 +632,7 @@ hipError_t launch_score(const ScoringDev* d_sc, const ScoringDev& h_sc, const Ba
                 ap.chunk_keys = ws.chunk_keys;
                 const uint32_t zgrid = (bb.n_items + 255) / 256;
                 hipLaunchKernelGGL(chunk_zero_kernel, dim3(zgrid), dim3(256), 0, stream, ap.b.items, counter, bb.n_items, ws.chunk_keys);
+                note_launch(launches, ZSW_LAUNCH_V2, g, c, std::min(mode, 2));
                 pe = launch_table_cfg_v2(ap, g, c, mode, stream);
                 if (pe != hipSuccess) return pe;
                 hipLaunchKernelGGL(chunk_finalize_kernel, dim3(zgrid), dim3(256), 0, stream, ap.b, counter, ws.chunk_keys, ap.limit, rule, out, std::min(mode, 2));
@@ -651,7 +661,10 @@ hipError_t launch_score(const ScoringDev* d_sc, const ScoringDev& h_sc, const Ba
                     }
                     ah.gate_lo = lo;
                     ah.gate_hi = hi;
-                    if (lo < bb.n_items) pe = launch_table_cfg_v2(ah, other ? g2 : g, other ? c2 : c, mode, stream);
+                    if (lo < bb.n_items) {
+                        note_launch(launches, ZSW_LAUNCH_V2, other ? g2 : g, other ? c2 : c, std::min(mode, 2));
+                        pe = launch_table_cfg_v2(ah, other ? g2 : g, other ? c2 : c, mode, stream);
+                    }
                     lo = hi;
                 }
             }
@@ -691,6 +704,7 @@ hipError_t launch_score(const ScoringDev* d_sc, const ScoringDev& h_sc, const Ba
         pe = launch_score_pruned(ap, cls, n_cls, floor_strip, floor_window, h_sc, ws.prune_work, ws.prune_bytes, ws.prune_chunk,
                                  ws.prune_fail_list, ws.prune_fail_count, mode, wide, stream, &est_failed);
         if (pe != hipSuccess) return pe;
+        note_launch(launches, ZSW_LAUNCH_PRUNED, kPruneClasses[cls].g, kPruneClasses[cls].cp, std::min(mode, 2));
         // a short list of handed-back reads is latency-bound in the narrowest configuration (20,000 reads of 150 residues: 3.4 ms
         // at four lanes per pair, every block walking all R rows): with the probe's estimate it takes the small-batch configuration
         if (est_failed != 0xffffffffu) (void)score_config_for_batch(kPruneClasses[last].max_len, est_failed + est_failed / 4 + 1024, &Gr, &Cr);
@@ -698,6 +712,7 @@ hipError_t launch_score(const ScoringDev* d_sc, const ScoringDev& h_sc, const Ba
         a2.b = bb;
         a2.b.items = ws.prune_fail_list;
         a2.n_items_dev = ws.prune_fail_count;
+        note_launch(launches, wide ? ZSW_LAUNCH_WIDE : ZSW_LAUNCH_V2, Gr, Cr, wide ? (mode == 0 ? 0 : 2) : std::min(mode, 2));
         pe = wide ? launch_table_cfg_v2_wide(a2, Gr, Cr, mode, stream) : launch_table_cfg_v2(a2, Gr, Cr, mode, stream);
         a2.n_items_dev = nullptr;
         if (pe != hipSuccess) return pe;
@@ -940,6 +955,7 @@ hipError_t launch_score_rev(const ScoringDev* d_sc, const ScoringDev& h_sc, cons
                     a2.tile_q0 = t * (uint32_t)TILE_COLS;
                     a2.tile_in = t ? buf[(t - 1) & 1] : nullptr;
                     a2.tile_out = t + 1 < n_tiles ? buf[t & 1] : nullptr;
+                    note_launch(ws.launch_log, ZSW_LAUNCH_TILE_W32, TILE_G, TILE_C, 2);
                     e = launch_tile_w32(a2, ws.bucket_items + first, 2, stream);
                     if (e != hipSuccess) return e;
                 }
@@ -948,6 +964,7 @@ hipError_t launch_score_rev(const ScoringDev* d_sc, const ScoringDev& h_sc, cons
         }
     }
     if (!table_ok) {
+        note_launch(ws.launch_log, ZSW_LAUNCH_EXACT32, 0, 0, 2);
         hipLaunchKernelGGL(exact32_kernel, dim3(exact_grid), dim3(64), 0, stream, b, (const uint32_t*)nullptr,
                            (const uint32_t*)nullptr, d_ref, ref_len, d_sc, rule, out, ws.scratch, (uint32_t)ws.slots,
                            ws.scratch_len, d_fwd_ref_end, d_fwd_query_end);
@@ -977,12 +994,15 @@ hipError_t launch_score_rev(const ScoringDev* d_sc, const ScoringDev& h_sc, cons
     }
     if (ref_len) hipLaunchKernelGGL(gtab_kernel, dim3((ref_len + 255) / 256), dim3(256), 0, stream, d_ref, ref_len, d_sc, a, (int)wide, d_gtab);
     if (wide) {
+        if (b.n_items) note_launch(ws.launch_log, ZSW_LAUNCH_WIDE_REV, G, C, 2);
         e = launch_cfg_rev_wide(a, G, C, stream);
         if (e != hipSuccess) return e;
+        note_launch(ws.launch_log, ZSW_LAUNCH_EXACT32_WORKLIST, 0, 0, 2);
         hipLaunchKernelGGL(exact32_kernel, dim3(exact_grid), dim3(64), 0, stream, b, out.fb_list, out.fb_count, d_ref, ref_len, d_sc,
                            rule, out, ws.scratch, (uint32_t)ws.slots, ws.scratch_len, d_fwd_ref_end, d_fwd_query_end);
         return hipGetLastError();
     }
+    if (b.n_items) note_launch(ws.launch_log, fast ? ZSW_LAUNCH_V1_FAST_REV : ZSW_LAUNCH_V1_BIASED_REV, G, C, 2);
     switch (G * 100 + C) {
 #define ZSW_CASE(GV, CV) \
     case GV * 100 + CV: e = launch_cfg_rev<GV, CV>(a, fast, stream); break;
@@ -991,6 +1011,7 @@ hipError_t launch_score_rev(const ScoringDev* d_sc, const ScoringDev& h_sc, cons
         default: e = hipErrorInvalidValue;
     }
     if (e != hipSuccess) return e;
+    note_launch(ws.launch_log, ZSW_LAUNCH_EXACT32_WORKLIST, 0, 0, 2);
     hipLaunchKernelGGL(exact32_kernel, dim3(exact_grid), dim3(64), 0, stream, b, out.fb_list, out.fb_count, d_ref, ref_len, d_sc,
                        rule, out, ws.scratch, (uint32_t)ws.slots, ws.scratch_len, d_fwd_ref_end, d_fwd_query_end);
     return hipGetLastError();

@@ -193,7 +193,8 @@ bool seed_applicable(const SeedIndex& ix, uint32_t max_len, uint32_t ref_len, ui
 
 hipError_t launch_score_seeded(const ScoreArgsV2& a2, int G, int C, uint32_t max_len, const SeedIndex& ix, uint8_t* work, size_t work_bytes,
                                uint2* gtab, uint32_t* fail_list, uint32_t* fail_count, int mode, const ScoreArgsV2* band_tabs, const uint2* gtab_band, int32_t* band_dbg,
-                               uint32_t narrow_min_reads, uint32_t band_grid_cap, hipStream_t stream, KernelTimer* window_timer, bool narrow_only, bool reads_reversed) {
+                               uint32_t narrow_min_reads, uint32_t band_grid_cap, hipStream_t stream, KernelTimer* window_timer, bool narrow_only, bool reads_reversed,
+                               std::vector<uint32_t>* launches) {
     const uint32_t n = a2.b.n_items;
     if (n == 0) return hipSuccess;
     if (!work || !gtab || work_bytes < seed_workspace_bytes(n, max_len, band_grid_cap)) return hipErrorNotSupported;
@@ -309,6 +310,7 @@ hipError_t launch_score_seeded(const ScoreArgsV2& a2, int G, int C, uint32_t max
             b1.retry = narrow_only ? nullptr : retry;  // no second tier: what fails joins the worklist at once
             b1.accepted = narrow_only ? nullptr : accepted;
             b1.next_pair = queue1;
+            note_launch(launches, ZSW_LAUNCH_SEED_BAND, G, C, mode);
             e = launch_seed_band(b1, mode, true, stream);
             if (e != hipSuccess) return e;
             if (narrow_only) {
@@ -329,6 +331,7 @@ hipError_t launch_score_seeded(const ScoreArgsV2& a2, int G, int C, uint32_t max
             b.bail_check = true;
             b.bail_below = band_dbg ? 0u : SEED_BAIL_BELOW;  // (the bounds test wants the second tier's records)
         }
+        note_launch(launches, ZSW_LAUNCH_SEED_BAND, G, C, mode);
         e = launch_seed_band(b, mode, false, stream);
         if (window_timer) window_timer->end(stream);
         return e;
@@ -362,6 +365,7 @@ hipError_t launch_score_seeded(const ScoreArgsV2& a2, int G, int C, uint32_t max
     w.fail_count = fail_count;
     w.reversed = reads_reversed;
     if (window_timer) window_timer->begin(stream);
+    note_launch(launches, ZSW_LAUNCH_SEED_WINDOW, G, C, std::min(mode, 2));
     e = mode == 0 ? launch_seed_window_m0(w, G, C, stream) : mode == 1 ? launch_seed_window_m1(w, G, C, stream) : launch_seed_window_m2(w, G, C, stream);
     if (window_timer) window_timer->end(stream);
     return e;
