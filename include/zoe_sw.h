@@ -429,7 +429,10 @@ typedef enum zsw_debug_flag {
      * exactly one optimal alignment that is a gapless diagonal — both maxima in one cell each, the diagonal's weights add up to the
      * score, the score beyond what any path with an insertion and a deletion between the same corners can reach — gets that
      * alignment without it (tests/models/align_gapless_cert.cpp) */
-    ZSW_DEBUG_ALIGN_NO_CERTIFICATE = 32768
+    ZSW_DEBUG_ALIGN_NO_CERTIFICATE = 32768,
+    /* score: the first of the banded pass's two tiers walks 16-column strips (seed_band_kernel) for every read length. By default
+     * score-only batches of reads of up to 255 bases walk it diagonal by diagonal (seed_diag_kernel, zsw_score_band.hip) */
+    ZSW_DEBUG_SEED_STRIP_FIRST_TIER = 65536
 } zsw_debug_flag;
 zsw_error zsw_debug_set(zsw_context* ctx, uint32_t flags);
 

@@ -30,6 +30,7 @@ DEBUG_SCORE_PRUNE, DEBUG_SCORE_PRUNE_ANY_SIZE, DEBUG_PRUNE_STRIP, DEBUG_ALIGN_LO
 DEBUG_NO_ROW_CHUNKS = 8192
 DEBUG_RANGES_EXACT_REVERSE = 16384
 DEBUG_ALIGN_NO_CERTIFICATE = 32768
+DEBUG_SEED_STRIP_FIRST_TIER = 65536
 # zsw_launch_kind: the first entry of a zsw_debug_score_launches record
 (LAUNCH_V1_FAST, LAUNCH_V1_BIASED, LAUNCH_V2, LAUNCH_WIDE, LAUNCH_V1_FAST_REV, LAUNCH_V1_BIASED_REV, LAUNCH_WIDE_REV, LAUNCH_TILE_V2, LAUNCH_TILE_WIDE,
  LAUNCH_TILE_W32, LAUNCH_EXACT32, LAUNCH_EXACT32_WORKLIST, LAUNCH_SEED_WINDOW, LAUNCH_SEED_BAND, LAUNCH_PRUNED) = range(15)

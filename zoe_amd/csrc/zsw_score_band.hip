@@ -20,6 +20,7 @@
 #include <type_traits>
 
 #include "zsw_score_seed.hpp"
+#include "zsw_seed_diag.hpp"
 #include "zsw_score_v2.hpp"
 #include "zsw_timer.hpp"
 
@@ -131,6 +132,129 @@ __device__ __forceinline__ void pk_events(BandPk* t, uint32_t sm, uint32_t em, u
     t->fr &= ~em;
 }
 
+// ---- what the strip kernel and the diagonal kernel share: the work queue in front of a walk, the decision and the outputs behind it ----
+struct BandPair {
+    uint32_t ridA, ridB, idA, idB, itemA, itemB, lenA, lenB;
+    int dtA, dtB;
+    bool validB;
+};
+struct BandEnds {  // MODE 1-3: where the maximum sits
+    int rowA = 0x7fffffff, rowB = 0x7fffffff, colA = 0x7fffffff, colB = 0x7fffffff;
+    bool multA = false, multB = false;
+};
+
+// Work queue: a wavefront takes the next 64 pairs of the anchor order (one atomic per wavefront), so that no lane waits for
+// a neighbour with one pair more. Every wavefront leaves at the first chunk past the last pair, or at the first chunk that
+// holds nothing but reads without an anchor (sorted: they are the tail of the order, and the seed kernel listed them).
+// Returns 0: the wavefront leaves; 1: this lane has nothing to walk in this chunk; 2: walk *p. slack: the anchors of two reads
+// that share a lane are at most this far apart.
+__device__ __forceinline__ int band_fetch(const SeedBandArgs& a, int tid, uint32_t n_items, uint32_t n_pairs, bool bail, int slack, BandPair* p) {
+    uint32_t base = 0;
+    if ((tid & 63) == 0) base = atomicAdd(a.next_pair, 64u);
+    base = (uint32_t)__shfl((int)base, 0, 64);
+    if (base >= n_pairs) return 0;
+    const uint32_t pair = base + (uint32_t)(tid & 63);
+    const uint32_t itemA = 2 * pair, itemB = itemA + 1;
+    uint32_t ridA = 0, keyA = a.fail_key;
+    if (pair < n_pairs) {
+        ridA = a.order[itemA];
+        keyA = a.keys[ridA];
+    }
+    const bool active = keyA != a.fail_key;
+    if (__ballot(active) == 0) return 0;
+    if (!active) return 1;
+    uint32_t ridB = itemB < n_items ? a.order[itemB] : ridA;
+    uint32_t keyB = itemB < n_items ? a.keys[ridB] : a.fail_key;
+    bool validB = keyB != a.fail_key;
+    const int dtA = (int)keyA - (int)a.key_bias;
+    int dtB = validB ? (int)keyB - (int)a.key_bias : dtA;
+    const uint32_t idA = a.b.items ? a.b.items[ridA] : ridA;
+    uint32_t idB = validB ? (a.b.items ? a.b.items[ridB] : ridB) : idA;
+    if (bail) {  // (launch-uniform)
+        a.fail_list[atomicAdd(a.fail_count, 1u)] = idA;
+        if (validB) a.fail_list[atomicAdd(a.fail_count, 1u)] = idB;
+        return 1;
+    }
+    if (validB && dtB - dtA > slack) {  // anchors too far apart to share a band: B waits for the next tier / takes the full pass
+        if (a.retry) a.retry[itemB] = 1;
+        else a.fail_list[atomicAdd(a.fail_count, 1u)] = idB;
+        validB = false;
+        dtB = dtA;
+    }
+    if (!validB) ridB = ridA;
+    p->ridA = ridA;
+    p->ridB = ridB;
+    p->idA = idA;
+    p->idB = idB;
+    p->itemA = itemA;
+    p->itemB = itemB;
+    p->lenA = a.b.offsets ? (uint32_t)(a.b.offsets[idA + 1] - a.b.offsets[idA]) : a.b.fixed_len;
+    p->lenB = validB ? (a.b.offsets ? (uint32_t)(a.b.offsets[idB + 1] - a.b.offsets[idB]) : a.b.fixed_len) : 0u;
+    p->dtA = dtA;
+    p->dtB = dtB;
+    p->validB = validB;
+    return 2;
+}
+
+// best: the band's maximum of either read (doubled, odd: held by a path that touched a cell outside the band); oa2 / ob2: the most
+// a path that ends above / below the band can score (plain, per half); geom / C: rec[5] and the columns per strip of the debug record
+template <int MODE>
+__device__ __forceinline__ void band_finish(const SeedBandArgs& a, const BandPair& p, uint32_t best, uint32_t oa2, uint32_t ob2, int dtmin, int dtmax, int geom, int C,
+                                            uint32_t infoA, uint32_t infoB, const BandEnds& e, uint32_t* n_accepted) {
+    const uint32_t best2A = best & 0xffffu, best2B = best >> 16;
+    const int tallA = (int)(infoA & 0xffffu), tallB = (int)(infoB & 0xffffu);
+    const int dfaA = (int)((infoA >> 16) & 0xffu), dfaB = (int)((infoB >> 16) & 0xffu);
+#pragma unroll
+    for (int h = 0; h < 2; ++h) {
+        if (h == 1 && !p.validB) break;
+        const uint32_t id = h ? p.idB : p.idA;
+        const uint32_t b2 = h ? best2B : best2A;
+        const int oa = (int)((oa2 >> (h ? 16 : 0)) & 0xffffu), ob = (int)((ob2 >> (h ? 16 : 0)) & 0xffffu);
+        const int S = (int)(b2 >> 1), outside = max(oa, ob);
+        // an odd maximum: a path through a cell outside the band may hold it. Score only: a path that ends outside matters if it
+        // can score MORE than S; with ends also if it can score S (it could end in an earlier row or column)
+        const bool redo = (b2 & 1u) != 0 || (MODE == 0 ? outside > S : outside >= S);
+        if (a.dbg) {  // tests/test_gpu_bounds.py: the kernel's own values against the host model's
+            int* rec = a.dbg + (size_t)id * 8;
+            rec[0] = (int)b2;
+            rec[1] = oa;
+            rec[2] = ob;
+            rec[3] = dtmin;
+            rec[4] = dtmax;
+            rec[5] = geom;
+            rec[6] = h ? p.dtB : p.dtA;
+            rec[7] = (((h ? p.lenB : p.lenA) == 0 || redo) ? 0 : 1) | (C << 8);
+        }
+        if ((h ? p.lenB : p.lenA) == 0 || redo) {
+            if (a.retry) a.retry[h ? p.itemB : p.itemA] = 1;
+            else a.fail_list[atomicAdd(a.fail_count, 1u)] = id;
+        } else {
+            ++*n_accepted;
+            uint32_t score;
+            uint8_t status, tier;
+            apply_rule(a.rule, (uint64_t)S, &score, &status, &tier);
+            a.out.score[id] = score;
+            a.out.status[id] = status;
+            if (a.out.tier) a.out.tier[id] = tier;
+            const bool some = status == ZSW_STATUS_SOME;
+            if (MODE != 0 && a.out.ref_end) a.out.ref_end[id] = some ? (uint32_t)(h ? e.rowB : e.rowA) + 1 : 0;
+            if (MODE >= 2 && a.out.query_end) a.out.query_end[id] = some ? (uint32_t)(h ? e.colB : e.colA) + 1 : 0;
+            if (MODE == 3 && a.out.unique) a.out.unique[id] = (some && !(h ? e.multB : e.multA)) ? 1 : 0;
+            if (MODE != 0 && a.out.safe_row)  // sw_simd_align's second pass may start this late (or 0xffffffff: no certificate)
+                a.out.safe_row[id] = (uint32_t)seed_safe_start(a.sp, h ? tallB : tallA, h ? dfaB : dfaA, h ? p.dtB : p.dtA, S);
+        }
+    }
+}
+
+// first tier: the reads a block accepted, one atomic per wavefront
+__device__ __forceinline__ void band_count_accepted(const SeedBandArgs& a, int tid, uint32_t n_accepted) {
+    if (a.retry && a.accepted) {
+#pragma unroll
+        for (int d = 32; d >= 1; d >>= 1) n_accepted += (uint32_t)__shfl_xor((int)n_accepted, d, 64);
+        if ((tid & 63) == 0 && n_accepted) atomicAdd(a.accepted, n_accepted);
+    }
+}
+
 template <int C, int MINW, int MODE>
 __global__ __launch_bounds__(BLOCK, MINW) void seed_band_kernel(SeedBandArgs a) {
     constexpr int TAG = MODE == 0 ? -1 : 1;
@@ -155,45 +279,14 @@ __global__ __launch_bounds__(BLOCK, MINW) void seed_band_kernel(SeedBandArgs a) 
     const uint32_t maxw2 = (uint32_t)a.sp.maxw * 0x00010001u, go2p = (uint32_t)a.sp.go * 0x00010001u;  // plain (not doubled) scores of the bound programmes
     uint2* bnd = a.bnd + (size_t)blockIdx.x * (size_t)a.nb * BLOCK + tid;  // row j of this lane: bnd[j * BLOCK]
 
-    // Work queue: a wavefront takes the next 64 pairs of the anchor order (one atomic per wavefront), so that no lane waits for
-    // a neighbour with one pair more. Every wavefront leaves at the first chunk past the last pair, or at the first chunk that
-    // holds nothing but reads without an anchor (sorted: they are the tail of the order, and the seed kernel listed them).
     for (;;) {
-        uint32_t base = 0;
-        if ((tid & 63) == 0) base = atomicAdd(a.next_pair, 64u);
-        base = (uint32_t)__shfl((int)base, 0, 64);
-        if (base >= n_pairs) break;
-        const uint32_t pair = base + (uint32_t)(tid & 63);
-        const uint32_t itemA = 2 * pair, itemB = itemA + 1;
-        uint32_t ridA = 0, keyA = a.fail_key;
-        if (pair < n_pairs) {
-            ridA = a.order[itemA];
-            keyA = a.keys[ridA];
-        }
-        const bool active = keyA != a.fail_key;
-        if (__ballot(active) == 0) break;
-        if (active) {
-        uint32_t ridB = itemB < n_items ? a.order[itemB] : ridA;
-        uint32_t keyB = itemB < n_items ? a.keys[ridB] : a.fail_key;
-        bool validB = keyB != a.fail_key;
-        const int dtA = (int)keyA - (int)a.key_bias;
-        int dtB = validB ? (int)keyB - (int)a.key_bias : dtA;
-        const uint32_t idA = a.b.items ? a.b.items[ridA] : ridA;
-        uint32_t idB = validB ? (a.b.items ? a.b.items[ridB] : ridB) : idA;
-        if (bail) {  // (launch-uniform)
-            a.fail_list[atomicAdd(a.fail_count, 1u)] = idA;
-            if (validB) a.fail_list[atomicAdd(a.fail_count, 1u)] = idB;
-            continue;
-        }
-        if (validB && dtB - dtA > SEED_BAND_SLACK) {  // anchors too far apart to share a band: B waits for the next tier / takes the full pass
-            if (a.retry) a.retry[itemB] = 1;
-            else a.fail_list[atomicAdd(a.fail_count, 1u)] = idB;
-            validB = false;
-            dtB = dtA;
-        }
-        if (!validB) ridB = ridA;
-        const uint32_t lenA = a.b.offsets ? (uint32_t)(a.b.offsets[idA + 1] - a.b.offsets[idA]) : a.b.fixed_len;
-        const uint32_t lenB = validB ? (a.b.offsets ? (uint32_t)(a.b.offsets[idB + 1] - a.b.offsets[idB]) : a.b.fixed_len) : 0u;
+        BandPair P;
+        const int fetched = band_fetch(a, tid, n_items, n_pairs, bail, SEED_BAND_SLACK, &P);
+        if (fetched == 0) break;
+        if (fetched == 2) {
+        const uint32_t ridA = P.ridA, ridB = P.ridB, lenA = P.lenA, lenB = P.lenB;
+        const int dtA = P.dtA, dtB = P.dtB;
+        const bool validB = P.validB;
         const int lenmax = (int)max(lenA, lenB);
         const int n_strips = (lenmax + C - 1) / C;
         const int wu = a.wu0 + lenmax * a.wu_per16 / 16, wd = a.wd0 + lenmax * a.wd_per32 / 32;
@@ -452,56 +545,197 @@ __global__ __launch_bounds__(BLOCK, MINW) void seed_band_kernel(SeedBandArgs a) 
             }
             prev_bot = bot;
         }
-        const uint32_t best2A = best & 0xffffu, best2B = best >> 16;
-        const int tallA = (int)(infoA & 0xffffu), tallB = (int)(infoB & 0xffffu);
-        const int dfaA = (int)((infoA >> 16) & 0xffu), dfaB = (int)((infoB >> 16) & 0xffu);
+        BandEnds ends;
+        ends.rowA = rowA;
+        ends.rowB = rowB;
+        ends.colA = colA;
+        ends.colB = colB;
+        ends.multA = multA;
+        ends.multB = multB;
+        band_finish<MODE>(a, P, best, (uint32_t)st[BF_OA * BLOCK], (uint32_t)st[BF_OB * BLOCK], dtmin, dtmax, n_strips | (wu << 8) | (wd << 20), C, infoA, infoB, ends,
+                          &n_accepted);
+        }  // fetched == 2
+    }
+    band_count_accepted(a, tid, n_accepted);
+}
+
+// ---- the first tier along its diagonals (score only) ------------------------------------------------------------------------
+// A strip of ONE column is the band itself: column c of a lane's pair covers the reference rows [dtmin + c - wu, dtmax + c + 1 + wd)
+// and nothing else — no rectangle around the band, no boundary buffer (the model of tests/models/seed_band.cpp with C = 1; it also
+// proves more reads than 16-column strips: a bound that entered at a strip's corner has no rectangle to cross). seed_band_kernel's
+// row loop transposed: the registers hold the band's D diagonals (j = row - column - (dtmin - wu): the diagonal neighbour of a cell
+// is the same register one column earlier), per diagonal H, the outgoing F and — D columns unrolled, so that every index is static
+// — the table entry of the row the diagonal crosses in this column; E runs down the column. The drift of the packed domain
+// advances per COLUMN: F~ needs no decay, E pays its gap_extend explicitly, the table's + ge carries H~ from column to column.
+// A cell outside the reference computes with the neutral table entry: above row 0 it stays the zero it is; below the last row it
+// holds no more than a real cell did. The two bound programmes advance one column per step and stay in registers.
+constexpr int DIAG_D = SEED_NARROW_WU + SEED_NARROW_WD + 1 + SEED_DIAG_SLACK;
+
+// x: one bit per column of a group, read A's in bits 0-15, read B's in bits 16-31 -> 0xffff in the half whose read has bit u set
+__device__ __forceinline__ uint32_t pair_mask(uint32_t x, int u) {
+    return __builtin_amdgcn_perm((uint32_t)__builtin_amdgcn_sbfe((int)x, (uint32_t)(u + 16), 1u), (uint32_t)__builtin_amdgcn_sbfe((int)x, (uint32_t)u, 1u), 0x05040100u);
+}
+__device__ __forceinline__ uint32_t lane_mask(uint32_t x, int u) { return (uint32_t)__builtin_amdgcn_sbfe((int)x, (uint32_t)u, 1u); }
+__device__ __forceinline__ uint32_t pair_bits(uint32_t bitsA, uint32_t bitsB) { return (bitsA & 0xffffu) | (bitsB << 16); }
+
+template <int D>
+__global__ __launch_bounds__(BLOCK, 3) void seed_diag_kernel(SeedBandArgs a) {
+    constexpr int TAG = -1;
+    static_assert(D == 16, "a group of columns is two dwords of residue codes and 16 bits per read in the column masks");
+    static_assert(SEED_NARROW_WU_PER16 == 0 && SEED_NARROW_WD_PER32 == 0, "the window's height is fixed at compile time");
+    __shared__ uint16_t sel_lut[16];
+    __shared__ int sst[BF_N * BLOCK];  // (the layout fields only: the programmes' state lives in registers)
+    const int tid = threadIdx.x;
+    int* const st = sst + tid;
+    if (tid < 16) {
+        const uint32_t k = (uint32_t)tid;
+        sel_lut[tid] = (uint16_t)(k < 4 ? (2 * k + 1) | ((8 + k) << 8) : (k == 15 ? 0x0c00u : (2 * (k - 3)) | 0x0c00u));
+    }
+    __syncthreads();
+    const int R = (int)a.ref_len;
+    const uint32_t n_items = a.n_dev ? min(*a.n_dev, a.n) : a.n;
+    const uint32_t n_pairs = (n_items + 1) / 2;
+    const bool bail = a.bail_check && a.accepted && ((uint64_t)(*a.accepted) * SEED_BAIL_RATIO < (uint64_t)n_items || n_items < a.bail_below);
+    uint32_t n_accepted = 0;
+    const uint32_t ge2 = a.ge2, gd2 = a.gd2;
+    const uint32_t ge1 = ge2 & 0xffffu;
+    const uint32_t maxw2 = (uint32_t)a.sp.maxw * 0x00010001u, go2p = (uint32_t)a.sp.go * 0x00010001u;
+    const int wu = a.wu0, wd = a.wd0;  // (launch_seed_band: wu + wd + 1 + SEED_DIAG_SLACK == D)
+
+    for (;;) {
+        BandPair P;
+        const int fetched = band_fetch(a, tid, n_items, n_pairs, bail, SEED_DIAG_SLACK, &P);
+        if (fetched == 0) break;
+        if (fetched == 2) {
+        const uint32_t ridA = P.ridA, ridB = P.ridB;
+        const int lenA = (int)P.lenA, lenB = (int)P.lenB;
+        const bool validB = P.validB;
+        const int lenmax = max(lenA, lenB);
+        const int dtmin = min(P.dtA, P.dtB), dtmax = max(P.dtA, P.dtB);
+        // the band's last diagonal: D - 1 for a pair with two anchors, D - 2 otherwise (then diagonal D - 1 stands for the cells
+        // below the band: it hands yf to the band's last cell, and its own value counts for nothing)
+        const bool narrow = dtmax - dtmin < SEED_DIAG_SLACK;
+        const uint32_t infoA = a.info[ridA], infoB = a.info[ridB];
+        band_lane_init(a.sp, st, lenA, a.band_masks[ridA], lenB, validB ? a.band_masks[ridB] : 0u);
+        const uint32_t lam2 = (uint32_t)st[BF_LAM2 * BLOCK];
+        const uint32_t lamx = pk_subu_sat(lam2, maxw2);
+        const uint32_t* codeA = a.codes + (size_t)ridA * a.cs;
+        const uint32_t* codeB = a.codes + (size_t)ridB * a.cs;
+        const int base = dtmin - wu;  // diagonal j crosses row base + c + j in column c
+        const uint2* gt = a.gtab + SEED_GTAB_PAD;
+        uint2 w[D];                   // slot (c + j) % D: the table entry of the row diagonal j crosses in column c
+        uint32_t H[D], F[D];          // H of the previous column (drift of that column), outgoing F (drift of this one)
+        uint32_t Dc = (a.floor0 - ge1) * 0x00010001u;
 #pragma unroll
-        for (int h = 0; h < 2; ++h) {
-            if (h == 1 && !validB) break;
-            const uint32_t id = h ? idB : idA;
-            const uint32_t b2 = h ? best2B : best2A;
-            const int oa = (int)(((uint32_t)st[BF_OA * BLOCK] >> (h ? 16 : 0)) & 0xffffu), ob = (int)(((uint32_t)st[BF_OB * BLOCK] >> (h ? 16 : 0)) & 0xffffu);
-            const int S = (int)(b2 >> 1), outside = max(oa, ob);
-            // an odd maximum: a path through a cell outside the band may hold it. Score only: a path that ends outside matters if it
-            // can score MORE than S; with ends also if it can score S (it could end in an earlier row or column)
-            const bool redo = (b2 & 1u) != 0 || (MODE == 0 ? outside > S : outside >= S);
-            if (a.dbg) {  // tests/test_gpu_bounds.py: the kernel's own values against the host model's
-                int* rec = a.dbg + (size_t)id * 8;
-                rec[0] = (int)b2;
-                rec[1] = oa;
-                rec[2] = ob;
-                rec[3] = dtmin;
-                rec[4] = dtmax;
-                rec[5] = n_strips | (wu << 8) | (wd << 20);
-                rec[6] = h ? dtB : dtA;
-                rec[7] = (((h ? lenB : lenA) == 0 || redo) ? 0 : 1) | (C << 8);
+        for (int j = 0; j < D; ++j) {
+            w[j] = gt[max(-1, min(R, base + j))];
+            H[j] = Dc;
+            F[j] = pk_addu(Dc, ge2);
+        }
+        uint32_t Fbelow = pk_addu(Dc, ge2);  // what the cell below the band's last sends right
+        BandPk up, lo;
+        up.ch = lo.ch = PKB2;
+        up.fr = lo.fr = 0;
+        uint32_t oa2 = 0, ob2 = 0, best = 0;
+#pragma unroll 1
+        for (int k0 = 0; k0 < lenmax; k0 += D) {
+            uint32_t sel[D];
+#pragma unroll
+            for (int d = 0; d < D / 8; ++d) {
+                const uint32_t di = (uint32_t)(k0 / 8 + d);
+                const uint32_t wa = di < a.cs ? codeA[di] : 0xffffffffu;
+                const uint32_t wb = (validB && di < a.cs) ? codeB[di] : 0xffffffffu;
+#pragma unroll
+                for (int j = 0; j < 8; ++j)
+                    sel[8 * d + j] = (uint32_t)sel_lut[(wa >> (4 * j)) & 15u] | ((uint32_t)sel_lut[(wb >> (4 * j)) & 15u] << 16);
             }
-            if ((h ? lenB : lenA) == 0 || redo) {
-                if (a.retry) a.retry[h ? itemB : itemA] = 1;
-                else a.fail_list[atomicAdd(a.fail_count, 1u)] = id;
-            } else {
-                ++n_accepted;
-                uint32_t score;
-                uint8_t status, tier;
-                apply_rule(a.rule, (uint64_t)S, &score, &status, &tier);
-                a.out.score[id] = score;
-                a.out.status[id] = status;
-                if (a.out.tier) a.out.tier[id] = tier;
-                const bool some = status == ZSW_STATUS_SOME;
-                if (MODE != 0 && a.out.ref_end) a.out.ref_end[id] = some ? (uint32_t)(h ? rowB : rowA) + 1 : 0;
-                if (MODE >= 2 && a.out.query_end) a.out.query_end[id] = some ? (uint32_t)(h ? colB : colA) + 1 : 0;
-                if (MODE == 3 && a.out.unique) a.out.unique[id] = (some && !(h ? multB : multA)) ? 1 : 0;
-                if (MODE != 0 && a.out.safe_row)  // sw_simd_align's second pass may start this late (or 0xffffffff: no certificate)
-                    a.out.safe_row[id] = (uint32_t)seed_safe_start(a.sp, h ? tallB : tallA, h ? dfaB : dfaA, h ? dtB : dtA, S);
+            // the group's columns as bit masks: the k-mer events of both programmes, and where the band's ends are cells of the matrix
+            uint32_t upS, upE, loS, loE, loI, freeb, anyup, anylo, inj, join, ex, bel, nm, topin;
+            {
+                const BandLayout yA = band_layout(st, false), yB = band_layout(st, true);
+                const SeedStripEvents uA = seed_strip_events(k0, D, yA.m, yA.c0, yA.stride, a.sp.K, yA.magic, yA.fa);
+                const SeedStripEvents uB = seed_strip_events(k0, D, yB.m, yB.c0, yB.stride, a.sp.K, yB.magic, yB.fa);
+                const SeedStripEvents lA = seed_strip_events(k0, D, yA.m, yA.c0, yA.stride, a.sp.K, yA.magic, yA.fb);
+                const SeedStripEvents lB = seed_strip_events(k0, D, yB.m, yB.c0, yB.stride, a.sp.K, yB.magic, yB.fb);
+                upS = pair_bits(uA.start, uB.start);
+                upE = pair_bits(uA.end, uB.end);
+                loS = pair_bits(lA.start, lB.start);
+                loE = pair_bits(lA.end, lB.end);
+                loI = pair_bits(lA.inside, lB.inside);
+                freeb = pair_bits(seed_free_bits(k0, D, yA.m, yA.c0, yA.stride, a.sp.K, a.sp.spacer, yA.magic, yA.fa),
+                                  seed_free_bits(k0, D, yB.m, yB.c0, yB.stride, a.sp.K, a.sp.spacer, yB.magic, yB.fa));
+                anyup = upS | upE;
+                anyup |= anyup >> 16;
+                anylo = loS | loE;
+                anylo |= anylo >> 16;
+                // column c: first row base + c (a cell above it exists if that is > 0), first row below dtmax + c + 1 + wd
+                const int t0 = base + k0, t1 = dtmax + k0 + 1 + wd;
+                const uint32_t above = seed_bits_from(1 - t0), below = seed_bits_below(R - t1);
+                topin = seed_bits_from(-t0) & seed_bits_below(R - t0);                                   // the first row is a row of the reference
+                const uint32_t exits = below & seed_bits_from(1 - t1), yfok = below & seed_bits_from(-t1);  // ... the last row; the next column's last row
+                const uint32_t realA = seed_bits_below(lenA - k0), realB = seed_bits_below(lenB - k0);
+                inj = pair_bits(realA & above, realB & above);
+                join = pair_bits(seed_bits_below(lenA - k0 - 1) & topin, seed_bits_below(lenB - k0 - 1) & topin);  // (not behind the read's last column)
+                ex = pair_bits(realA & exits, realB & exits);
+                bel = pair_bits(realA & below, realB & below);
+                nm = pair_bits(realA & yfok, realB & yfok);
+            }
+#pragma unroll
+            for (int u = 0; u < D; ++u) {
+                if (k0 + u < lenmax) {  // (no break: a loop with two exits around a __ballot is not unrolled)
+                Dc = pk_addu(Dc, ge2);
+                const uint32_t Dn = pk_addu(Dc, ge2);
+                // above the column: a(c); the band's first cell receives it from above (E: less gap_open)
+                up.ch += maxw2;
+                up.fr += maxw2;
+                if (__ballot((anyup >> u) & 1u) != 0) pk_events(&up, pair_mask(upS, u), pair_mask(upE, u), lam2);
+                const uint32_t v = pk_subu_sat(pk_maxu(up.ch, up.fr), PKB2) & pair_mask(inj, u);
+                oa2 = pk_maxu(oa2, v);
+                uint32_t E = pk_addu(Dc, pk_tag<TAG>(pk_subu_sat(v, go2p) & lane_mask(topin, u)));
+                uint32_t rmax = 0x04000400u;
+#pragma unroll
+                for (int j = 0; j < D; ++j) {
+                    const uint2 wr = w[(u + j) % D];
+                    const uint32_t hd = pk_addu(H[j], __builtin_amdgcn_perm(wr.y, wr.x, sel[u]));
+                    const uint32_t Fin = j + 1 < D ? F[j + 1 < D ? j + 1 : j] : Fbelow;
+                    const uint32_t h = pk_max3(hd, E, Fin);
+                    H[j] = h;
+                    const uint32_t hg = h - gd2;
+                    F[j] = pk_max3(Fin, hg, Dn);
+                    E = pk_max3(E, hg, Dn) - ge2;
+                    if (j == D - 1) rmax = pk_max3(rmax, H[j - 1], narrow ? 0u : h);
+                    else if (j & 1) rmax = pk_max3(rmax, H[j - 1], h);
+                    if (j == 0) w[u] = gt[max(-1, min(R, base + k0 + u + D))];  // the row that enters the window in the next column
+                }
+                best = pk_maxu(best, pk_subu(rmax, Dc));
+                // the first cell's value joins the paths above the band behind this column
+                {
+                    const uint32_t ux = pk_addu(pk_untag<TAG>(pk_subu(H[0], Dc)), PKB2) & pair_mask(join, u);
+                    const uint32_t fm = pair_mask(freeb, u);
+                    up.fr = pk_maxu(up.fr, ux & fm);
+                    up.ch = pk_maxu(up.ch, ux & ~fm);
+                }
+                // below the column: b(c), joined by the band's last cell
+                lo.ch += maxw2;
+                lo.fr += maxw2;
+                if (__ballot((anylo >> u) & 1u) != 0) pk_events(&lo, pair_mask(loS, u), pair_mask(loE, u), lam2);
+                const uint32_t he = pk_addu(pk_untag<TAG>(pk_subu(narrow ? H[D - 2] : H[D - 1], Dc)), PKB2) & pair_mask(ex, u);
+                const uint32_t im = pair_mask(loI, u);
+                lo.fr = pk_maxu(lo.fr, he & im);
+                lo.ch = pk_maxu(lo.ch, he & ~im);
+                const uint32_t b2 = pk_subu_sat(pk_maxu(lo.ch, lo.fr), PKB2);
+                ob2 = pk_maxu(ob2, b2 & pair_mask(bel, u));
+                // the next column's last cell: F entering from the left (the bound may have stood lambda - maxw higher just before a
+                // k-mer's last column; a horizontal run opens with gap_open)
+                Fbelow = pk_addu(Dn, pk_tag<TAG>(pk_subu_sat(pk_addu(b2, lamx), go2p) & pair_mask(nm, u)));
+                if (narrow) F[D - 1] = Fbelow;
+                }
             }
         }
-        }  // active
+        band_finish<0>(a, P, best, oa2, ob2, dtmin, dtmax, lenmax | (wu << 8) | (wd << 20), 1, infoA, infoB, BandEnds{}, &n_accepted);
+        }  // fetched == 2
     }
-    if (a.retry && a.accepted) {  // first tier: one atomic per wavefront
-#pragma unroll
-        for (int d = 32; d >= 1; d >>= 1) n_accepted += (uint32_t)__shfl_xor((int)n_accepted, d, 64);
-        if ((tid & 63) == 0 && n_accepted) atomicAdd(a.accepted, n_accepted);
-    }
+    band_count_accepted(a, tid, n_accepted);
 }
 
 }  // namespace
@@ -527,7 +761,17 @@ bool seed_band_applicable(const SeedParams& p, uint32_t max_len, uint32_t rebase
     return (uint32_t)BC + seed_band_rows(p, max_len) + 2 <= rebase_rows;
 }
 
-hipError_t launch_seed_band(const SeedBandArgs& a, int mode, bool narrow_strips, hipStream_t stream) {
+bool seed_diag_applicable(uint32_t max_len, uint32_t rebase_rows) {
+    // the drift advances once per column and is never re-based inside a read; the debug record keeps the column count in 8 bits
+    return max_len <= SEED_DIAG_MAX_LEN && max_len + 2 <= rebase_rows;
+}
+
+hipError_t launch_seed_band(const SeedBandArgs& a, int mode, bool narrow_strips, hipStream_t stream, bool diagonal) {
+    if (diagonal) {  // the first tier along its diagonals (launch_score_seeded decides; score only, the narrow band's width)
+        if (mode != 0 || !narrow_strips || a.wu_per16 != 0 || a.wd_per32 != 0 || a.wu0 + a.wd0 + 1 + SEED_DIAG_SLACK != DIAG_D) return hipErrorInvalidValue;
+        hipLaunchKernelGGL((seed_diag_kernel<DIAG_D>), dim3(a.grid), dim3(BLOCK), 0, stream, a);
+        return hipGetLastError();
+    }
     // H, E and the selectors are 3 * C registers (4 * C with the MODE 2 snapshot of the H row); measured: the 48-column ends kernels at
     // one wavefront per SIMD (AGPRs as spill space) beat two with scratch by 16 %, the score-only kernel at two beats one by 4 %
     if (narrow_strips) {

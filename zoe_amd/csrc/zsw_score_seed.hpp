@@ -27,6 +27,11 @@ constexpr int SEED_SECOND_WU = 16, SEED_SECOND_WU_PER16 = 1, SEED_SECOND_WD = 8,
 constexpr uint32_t SEED_NARROW_MAX_LEN = 640;  // beyond: a read's own indels drift further than the narrow band is wide
 constexpr uint32_t SEED_NARROW_MIN_READS = 200000;  // below: two more launches cost more than the narrower band saves (length classes of a ragged batch)
 constexpr int SEED_BAND_SLACK = 32;           // banded pass: two reads share a lane if their anchors are at most this far apart
+// The first tier of a score-only call walks its band diagonal by diagonal (seed_diag_kernel: a strip of one column, no rectangle
+// around the band): a window of SEED_NARROW_WU + SEED_NARROW_WD + 1 + SEED_DIAG_SLACK = 16 diagonals in registers, so lane partners
+// share a band only if their anchors are at most one diagonal apart (reads are sorted by anchor: next to none differ by more).
+constexpr int SEED_DIAG_SLACK = 1;
+constexpr uint32_t SEED_DIAG_MAX_LEN = 255;   // the debug record counts a walk's strips — here columns — in 8 bits
 constexpr uint32_t SEED_BAND_MAX_GRID = 1024;  // banded pass: persistent blocks (each lane owns a boundary buffer in HBM)
 constexpr uint32_t SEED_KEY_BIAS = 1u << 16;  // sort key = anchor diagonal + bias (reads of up to 65,535 bases)
 constexpr uint32_t SEED_MAX_LEN = 2432;       // the widest strip configuration
@@ -107,8 +112,10 @@ uint32_t seed_band_grid(uint32_t n, uint32_t grid_cap);
 size_t seed_band_buffer_bytes(const SeedParams& p, uint32_t n, uint32_t max_len, uint32_t grid_cap);
 // rebase_rows / limit: of the doubled scoring's drift domain (a strip's rows must fit one drift period, twice the largest score the range)
 bool seed_band_applicable(const SeedParams& p, uint32_t max_len, uint32_t rebase_rows, uint32_t limit);
-// narrow_strips: 16 columns per strip (the first tier) instead of 32
-hipError_t launch_seed_band(const SeedBandArgs& a, int mode, bool narrow_strips, hipStream_t stream);
+// narrow_strips: 16 columns per strip (the first tier) instead of 48; diagonal: the first tier as a band of diagonals
+// (seed_diag_kernel: mode 0, the narrow band, reads for which seed_diag_applicable holds)
+hipError_t launch_seed_band(const SeedBandArgs& a, int mode, bool narrow_strips, hipStream_t stream, bool diagonal = false);
+bool seed_diag_applicable(uint32_t max_len, uint32_t rebase_rows);
 
 struct ScoreArgsV2;
 
@@ -133,7 +140,7 @@ hipError_t seed_build_gtab(const ScoreArgsV2& a2, uint2* gtab, hipStream_t strea
 hipError_t launch_score_seeded(const ScoreArgsV2& a2, int G, int C, uint32_t max_len, const SeedIndex& ix, uint8_t* work, size_t work_bytes,
                                uint2* gtab, uint32_t* fail_list, uint32_t* fail_count, int mode, const ScoreArgsV2* band_tabs, const uint2* gtab_band, int32_t* band_dbg,
                                uint32_t narrow_min_reads, uint32_t band_grid_cap, hipStream_t stream, KernelTimer* window_timer, bool narrow_only = false, bool reads_reversed = false,
-                               std::vector<uint32_t>* launches = nullptr /* zsw_debug_score_launches */);
+                               std::vector<uint32_t>* launches = nullptr /* zsw_debug_score_launches */, bool strip_first_tier = false /* ZSW_DEBUG_SEED_STRIP_FIRST_TIER */);
 // (Re)builds the index for a reference given as residue indices on the host.
 hipError_t seed_index_update(SeedIndex* ix, const ScoringDev& sc, const uint8_t* h_ref, size_t ref_len);
 void seed_index_release(SeedIndex* ix);
