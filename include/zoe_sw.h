@@ -432,7 +432,11 @@ typedef enum zsw_debug_flag {
     ZSW_DEBUG_ALIGN_NO_CERTIFICATE = 32768,
     /* score: the first of the banded pass's two tiers walks 16-column strips (seed_band_kernel) for every read length. By default
      * score-only batches of reads of up to 255 bases walk it diagonal by diagonal (seed_diag_kernel, zsw_score_band.hip) */
-    ZSW_DEBUG_SEED_STRIP_FIRST_TIER = 65536
+    ZSW_DEBUG_SEED_STRIP_FIRST_TIER = 65536,
+    /* score: in the diagonal first tier every lane derives the k-mer column patterns of its own two reads. By default a batch of
+     * reads of one length derives them once per wavefront and group of columns, on scalar registers (a ragged batch always takes
+     * the per-lane form) */
+    ZSW_DEBUG_SEED_DIAG_LANE_EVENTS = 131072
 } zsw_debug_flag;
 zsw_error zsw_debug_set(zsw_context* ctx, uint32_t flags);
 

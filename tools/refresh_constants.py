@@ -3,10 +3,13 @@ a directory written by tools/refresh_constants.sh on the GPU box, and stamps eve
 measured on (zoe_amd/build.py::fatbin_sha256): bench.py marks a figure derived from another library's counts "stale".
 
 usage: python tools/refresh_constants.py gpurun_out/r04_const r04
+       python tools/refresh_constants.py <dir> <tag> --band-only   (the directory holds fatbin_sha256.txt and band/ only: a change
+       to the banded kernels alone; the other sections keep their figures and the hash they were measured on)
 """
 import collections, csv, glob, json, subprocess, sys
 
 src, tag = sys.argv[1], sys.argv[2]
+band_only = "--band-only" in sys.argv[3:]
 lib_hash = open(f"{src}/fatbin_sha256.txt").read().strip()
 KIB = 1024.0
 
@@ -36,11 +39,21 @@ def total(d, name, pick=lambda k: True, small_only=()):
 
 # --- the banded kernel of the headline: tools/try_seed.py 10 M = 4 seeded score calls (mode 0) + 4 seeded ranges calls (other modes)
 N_BAND, CALLS_BAND = 1e7, 4
-band0 = lambda k: "seed_band_kernel<" in k and k.split("seed_band_kernel<")[1].split(">")[0].replace(" ", "").endswith(",0")
+BAND_KERNELS = ("seed_band_kernel<", "seed_diag_kernel<")  # the strip kernel per MODE (the last template argument) and the diagonal first tier (score only)
+
+
+def band_name(k):
+    for base in BAND_KERNELS:
+        if base in k:
+            return base + k.split(base)[1].split(">")[0].replace(" ", "") + ">"
+    return None
+
+
+band0 = lambda k: band_name(k) is not None and (band_name(k).startswith("seed_diag_kernel<") or band_name(k).endswith(",0>"))
 band_valu = total(f"{src}/band/pmc_a", "SQ_INSTS_VALU", band0) / CALLS_BAND / N_BAND
 band_fetch = total(f"{src}/band/pmc_fetch", "FETCH_SIZE", band0) * KIB / CALLS_BAND / N_BAND
 band_write = total(f"{src}/band/pmc_write", "WRITE_SIZE", band0) * KIB / CALLS_BAND / N_BAND
-names = sorted("seed_band_kernel<" + k.split("seed_band_kernel<")[1].split(">")[0].replace(" ", "") + ">" for k in counters(f"{src}/band/pmc_a", "SQ_INSTS_VALU") if band0(k))
+names = sorted(band_name(k) for k in counters(f"{src}/band/pmc_a", "SQ_INSTS_VALU") if band0(k))
 subprocess.check_call([sys.executable, "tools/summarize_seed_prof.py", f"{src}/band", f"{tag}_band_summary", str(int(N_BAND))])
 for f in glob.glob(f"{src}/band/stats/*/*kernel_stats.csv"):  # the rocprofv3 --kernel-trace --stats table itself, kernels above 0.1 %
     rows = list(csv.DictReader(open(f)))
@@ -50,6 +63,17 @@ for f in glob.glob(f"{src}/band/stats/*/*kernel_stats.csv"):  # the rocprofv3 --
         for r in rows:
             if float(r["Percentage"]) >= 0.1:
                 w.writerow([r["Name"][:120], r["Calls"], r["TotalDurationNs"], r["AverageNs"], r["Percentage"], r["MinNs"], r["MaxNs"]])
+
+band = {"source": f"profiles/{tag}_band_summary.txt", "fatbin_sha256": lib_hash, "valu_per_read": round(band_valu),
+        "hbm_bytes_per_read": round(band_fetch + band_write, 1), "kernels": names,
+        "note": f"10 M reads of 150 bp vs 2 kb, every launch of the score-only banded kernels of one call (first tier over every read, second "
+                f"tier over the reads that fail it): {band_valu:.0f} VALU wave-instructions, {band_fetch:.0f} B fetched + {band_write:.0f} B written per read of the batch"}
+if band_only:
+    out = json.load(open("profiles/constants.json"))
+    out["band"] = band
+    json.dump(out, open("profiles/constants.json", "w"), indent=1)
+    print(json.dumps(out, indent=1))
+    sys.exit(0)
 
 # --- secondary entry points: tools/pmc_entry.py, 3 identical calls of 1 M reads
 N_SEC, CALLS_SEC = 1e6, 3
@@ -74,10 +98,7 @@ prot_hbm = (total(f"{src}/protein/pmc_fetch", "FETCH_SIZE", pruned, small_only=(
 subprocess.check_call([sys.executable, "tools/summarize_prune_prof.py", f"{src}/protein", f"{tag}_protein_prune_summary", str(int(N_PROT)), "protein"])
 
 out = {
-    "band": {"source": f"profiles/{tag}_band_summary.txt", "fatbin_sha256": lib_hash, "valu_per_read": round(band_valu),
-             "hbm_bytes_per_read": round(band_fetch + band_write, 1), "kernels": names,
-             "note": f"10 M reads of 150 bp vs 2 kb, every launch of the score-only banded kernels of one call (first tier over every read, second "
-                     f"tier over the reads that fail it): {band_valu:.0f} VALU wave-instructions, {band_fetch:.0f} B fetched + {band_write:.0f} B written per read of the batch"},
+    "band": band,
     "secondary": dict({"source": f"profiles/{tag}_secondary_valu.txt", "fatbin_sha256": lib_hash}, **sec),
     "protein": {"source": f"profiles/{tag}_protein_prune_summary.txt", "fatbin_sha256": lib_hash, "valu_per_read": round(prot_valu), "hbm_per_read": round(prot_hbm)},
 }

@@ -571,22 +571,56 @@ __global__ __launch_bounds__(BLOCK, MINW) void seed_band_kernel(SeedBandArgs a) 
 // holds no more than a real cell did. The two bound programmes advance one column per step and stay in registers.
 constexpr int DIAG_D = SEED_NARROW_WU + SEED_NARROW_WD + 1 + SEED_DIAG_SLACK;
 
-// x: one bit per column of a group, read A's in bits 0-15, read B's in bits 16-31 -> 0xffff in the half whose read has bit u set
-__device__ __forceinline__ uint32_t pair_mask(uint32_t x, int u) {
-    return __builtin_amdgcn_perm((uint32_t)__builtin_amdgcn_sbfe((int)x, (uint32_t)(u + 16), 1u), (uint32_t)__builtin_amdgcn_sbfe((int)x, (uint32_t)u, 1u), 0x05040100u);
+// per half: 0xffff if bit 15 - sh of the half is set (sh: a shift count per half, 0 .. 15) — two packed shifts. (The second one as
+// an asm statement: written as a shift the compiler turns "mask & value" into a compare and a select per half, seven instructions.)
+__device__ __forceinline__ uint32_t pk_bit_mask(uint32_t x, uint32_t sh) {
+    const uint32_t top = __builtin_bit_cast(uint32_t, __builtin_bit_cast(us2, x) << __builtin_bit_cast(us2, sh));
+    uint32_t m;
+    asm("v_pk_ashrrev_i16 %0, 15, %1 op_sel_hi:[0,1]" : "=v"(m) : "v"(top));
+    return m;
 }
+// x: one bit per column of a group, read A's in bits 0-15, read B's in bits 16-31 -> 0xffff in the half whose read has bit u set
+__device__ __forceinline__ uint32_t pair_mask(uint32_t x, int u) { return pk_bit_mask(x, (uint32_t)(15 - u) * 0x00010001u); }
 __device__ __forceinline__ uint32_t lane_mask(uint32_t x, int u) { return (uint32_t)__builtin_amdgcn_sbfe((int)x, (uint32_t)u, 1u); }
 __device__ __forceinline__ uint32_t pair_bits(uint32_t bitsA, uint32_t bitsB) { return (bitsA & 0xffffu) | (bitsB << 16); }
 
-template <int D>
+// The k-mer events of a group's columns for both reads of a lane and both bound programmes (zsw_seed_diag.hpp): the unmasked patterns
+// gA / gB of the three k-mers that can touch the group, picked by the reads' masks (fa2 / fb2: read A's 16 bits below read B's).
+struct DiagGroupEvents {
+    uint32_t upS, upE, freeb, loS, loE, loI;  // pair_bits of what seed_strip_events (fa: up, fb: lo) and seed_free_bits (fa) return
+};
+__device__ __forceinline__ DiagGroupEvents diag_group_events(const SeedGroupPatterns& gA, const SeedGroupPatterns& gB, uint32_t fa2, uint32_t fb2) {
+    DiagGroupEvents e;
+    e.upS = e.upE = e.freeb = e.loS = e.loE = e.loI = 0;
+#pragma unroll
+    for (int t = 0; t < SEED_GROUP_KMERS; ++t) {
+        // bit j0 + t of either mask (beyond the 16th k-mer the count wraps: there the patterns are 0)
+        const uint32_t sh = (uint32_t)((15 - gA.j0 - t) & 15) | ((uint32_t)((15 - gB.j0 - t) & 15) << 16);
+        const uint32_t ma = pk_bit_mask(fa2, sh), mb = pk_bit_mask(fb2, sh);
+        const uint32_t s = pair_bits(gA.start[t], gB.start[t]), en = pair_bits(gA.end[t], gB.end[t]);
+        e.upS |= ma & s;
+        e.upE |= ma & en;
+        e.freeb |= ma & pair_bits(gA.terr[t], gB.terr[t]);
+        e.loS |= mb & s;
+        e.loE |= mb & en;
+        e.loI |= mb & pair_bits(gA.inside[t], gB.inside[t]);
+    }
+    return e;
+}
+
+// UNI: every read of the launch has the same length (a.b.offsets == nullptr: launch_seed_band decides), so the k-mer layout and
+// with it a group's patterns are wave-uniform — scalar registers and scalar instructions; only the picks by the reads' masks are
+// per lane. Otherwise (a ragged batch, or ZSW_DEBUG_SEED_DIAG_LANE_EVENTS) every lane derives the patterns of its two reads.
+template <int D, bool UNI>
 __global__ __launch_bounds__(BLOCK, 3) void seed_diag_kernel(SeedBandArgs a) {
     constexpr int TAG = -1;
     static_assert(D == 16, "a group of columns is two dwords of residue codes and 16 bits per read in the column masks");
+    static_assert(D <= SEED_GROUP_MAX, "three k-mers per group (zsw_seed_diag.hpp)");
     static_assert(SEED_NARROW_WU_PER16 == 0 && SEED_NARROW_WD_PER32 == 0, "the window's height is fixed at compile time");
     __shared__ uint16_t sel_lut[16];
-    __shared__ int sst[BF_N * BLOCK];  // (the layout fields only: the programmes' state lives in registers)
+    __shared__ int sst[UNI ? 1 : BF_N * BLOCK];  // (the layout fields only: the programmes' state lives in registers)
     const int tid = threadIdx.x;
-    int* const st = sst + tid;
+    int* const st = sst + (UNI ? 0 : tid);
     if (tid < 16) {
         const uint32_t k = (uint32_t)tid;
         sel_lut[tid] = (uint16_t)(k < 4 ? (2 * k + 1) | ((8 + k) << 8) : (k == 15 ? 0x0c00u : (2 * (k - 3)) | 0x0c00u));
@@ -601,6 +635,17 @@ __global__ __launch_bounds__(BLOCK, 3) void seed_diag_kernel(SeedBandArgs a) {
     const uint32_t ge1 = ge2 & 0xffffu;
     const uint32_t maxw2 = (uint32_t)a.sp.maxw * 0x00010001u, go2p = (uint32_t)a.sp.go * 0x00010001u;
     const int wu = a.wu0, wd = a.wd0;  // (launch_seed_band: wu + wd + 1 + SEED_DIAG_SLACK == D)
+    // UNI: the one layout of the launch
+    int um = 0, ustride = 0, uc0 = 0;
+    uint32_t umagic = 0, ulam2 = 0;
+    if (UNI) {
+        seed_layout((int)a.b.fixed_len, a.sp.K, a.sp.spacer, &um, &ustride, &uc0);
+        umagic = seed_div_magic(ustride);
+        ulam2 = (uint32_t)seed_lambda(a.sp, ustride) * 0x00010001u;
+    }
+    // the per-row table by byte offset from row 0: the rows outside the reference, above it or below, share the neutral entry of row R
+    const char* const gt = reinterpret_cast<const char*>(a.gtab + SEED_GTAB_PAD);
+    const uint32_t row_end = (uint32_t)R * (uint32_t)sizeof(uint2);
 
     for (;;) {
         BandPair P;
@@ -608,27 +653,33 @@ __global__ __launch_bounds__(BLOCK, 3) void seed_diag_kernel(SeedBandArgs a) {
         if (fetched == 0) break;
         if (fetched == 2) {
         const uint32_t ridA = P.ridA, ridB = P.ridB;
-        const int lenA = (int)P.lenA, lenB = (int)P.lenB;
         const bool validB = P.validB;
-        const int lenmax = max(lenA, lenB);
+        const int lenA = UNI ? (int)a.b.fixed_len : (int)P.lenA, lenB = UNI ? (validB ? (int)a.b.fixed_len : 0) : (int)P.lenB;
+        const int lenmax = UNI ? (int)a.b.fixed_len : max(lenA, lenB);
         const int dtmin = min(P.dtA, P.dtB), dtmax = max(P.dtA, P.dtB);
         // the band's last diagonal: D - 1 for a pair with two anchors, D - 2 otherwise (then diagonal D - 1 stands for the cells
         // below the band: it hands yf to the band's last cell, and its own value counts for nothing)
         const bool narrow = dtmax - dtmin < SEED_DIAG_SLACK;
         const uint32_t infoA = a.info[ridA], infoB = a.info[ridB];
-        band_lane_init(a.sp, st, lenA, a.band_masks[ridA], lenB, validB ? a.band_masks[ridB] : 0u);
-        const uint32_t lam2 = (uint32_t)st[BF_LAM2 * BLOCK];
+        // the k-mer masks of the pair, read A's 16 bits below read B's (a missing partner has none): above the band fa, below it fb
+        const uint32_t masksA = a.band_masks[ridA], masksB = validB ? a.band_masks[ridB] : 0u;
+        const uint32_t fa2 = __builtin_amdgcn_perm(masksB, masksA, 0x05040100u), fb2 = __builtin_amdgcn_perm(masksB, masksA, 0x07060302u);
+        uint32_t lam2 = ulam2;
+        if (!UNI) {
+            band_lane_init(a.sp, st, lenA, masksA, lenB, masksB);
+            lam2 = (uint32_t)st[BF_LAM2 * BLOCK];
+        }
         const uint32_t lamx = pk_subu_sat(lam2, maxw2);
         const uint32_t* codeA = a.codes + (size_t)ridA * a.cs;
         const uint32_t* codeB = a.codes + (size_t)ridB * a.cs;
         const int base = dtmin - wu;  // diagonal j crosses row base + c + j in column c
-        const uint2* gt = a.gtab + SEED_GTAB_PAD;
+        const auto table_row = [&](uint32_t off) { return *reinterpret_cast<const uint2*>(gt + min(off, row_end)); };  // off: 8 * row, as it wraps
         uint2 w[D];                   // slot (c + j) % D: the table entry of the row diagonal j crosses in column c
         uint32_t H[D], F[D];          // H of the previous column (drift of that column), outgoing F (drift of this one)
         uint32_t Dc = (a.floor0 - ge1) * 0x00010001u;
 #pragma unroll
         for (int j = 0; j < D; ++j) {
-            w[j] = gt[max(-1, min(R, base + j))];
+            w[j] = table_row((uint32_t)(base + j) * (uint32_t)sizeof(uint2));
             H[j] = Dc;
             F[j] = pk_addu(Dc, ge2);
         }
@@ -652,18 +703,21 @@ __global__ __launch_bounds__(BLOCK, 3) void seed_diag_kernel(SeedBandArgs a) {
             // the group's columns as bit masks: the k-mer events of both programmes, and where the band's ends are cells of the matrix
             uint32_t upS, upE, loS, loE, loI, freeb, anyup, anylo, inj, join, ex, bel, nm, topin;
             {
-                const BandLayout yA = band_layout(st, false), yB = band_layout(st, true);
-                const SeedStripEvents uA = seed_strip_events(k0, D, yA.m, yA.c0, yA.stride, a.sp.K, yA.magic, yA.fa);
-                const SeedStripEvents uB = seed_strip_events(k0, D, yB.m, yB.c0, yB.stride, a.sp.K, yB.magic, yB.fa);
-                const SeedStripEvents lA = seed_strip_events(k0, D, yA.m, yA.c0, yA.stride, a.sp.K, yA.magic, yA.fb);
-                const SeedStripEvents lB = seed_strip_events(k0, D, yB.m, yB.c0, yB.stride, a.sp.K, yB.magic, yB.fb);
-                upS = pair_bits(uA.start, uB.start);
-                upE = pair_bits(uA.end, uB.end);
-                loS = pair_bits(lA.start, lB.start);
-                loE = pair_bits(lA.end, lB.end);
-                loI = pair_bits(lA.inside, lB.inside);
-                freeb = pair_bits(seed_free_bits(k0, D, yA.m, yA.c0, yA.stride, a.sp.K, a.sp.spacer, yA.magic, yA.fa),
-                                  seed_free_bits(k0, D, yB.m, yB.c0, yB.stride, a.sp.K, a.sp.spacer, yB.magic, yB.fa));
+                DiagGroupEvents ev;
+                if (UNI) {  // (a missing partner shares A's patterns: its masks are 0)
+                    const SeedGroupPatterns g = seed_group_patterns(k0, D, um, uc0, ustride, a.sp.K, a.sp.spacer, umagic);
+                    ev = diag_group_events(g, g, fa2, fb2);
+                } else {
+                    const BandLayout yA = band_layout(st, false), yB = band_layout(st, true);
+                    ev = diag_group_events(seed_group_patterns(k0, D, yA.m, yA.c0, yA.stride, a.sp.K, a.sp.spacer, yA.magic),
+                                           seed_group_patterns(k0, D, yB.m, yB.c0, yB.stride, a.sp.K, a.sp.spacer, yB.magic), fa2, fb2);
+                }
+                upS = ev.upS;
+                upE = ev.upE;
+                loS = ev.loS;
+                loE = ev.loE;
+                loI = ev.loI;
+                freeb = ev.freeb;
                 anyup = upS | upE;
                 anyup |= anyup >> 16;
                 anylo = loS | loE;
@@ -680,6 +734,7 @@ __global__ __launch_bounds__(BLOCK, 3) void seed_diag_kernel(SeedBandArgs a) {
                 bel = pair_bits(realA & below, realB & below);
                 nm = pair_bits(realA & yfok, realB & yfok);
             }
+            const uint32_t enter = (uint32_t)(base + k0 + D) * (uint32_t)sizeof(uint2);  // column k0's entering row, as a byte offset
 #pragma unroll
             for (int u = 0; u < D; ++u) {
                 if (k0 + u < lenmax) {  // (no break: a loop with two exits around a __ballot is not unrolled)
@@ -705,7 +760,7 @@ __global__ __launch_bounds__(BLOCK, 3) void seed_diag_kernel(SeedBandArgs a) {
                     E = pk_max3(E, hg, Dn) - ge2;
                     if (j == D - 1) rmax = pk_max3(rmax, H[j - 1], narrow ? 0u : h);
                     else if (j & 1) rmax = pk_max3(rmax, H[j - 1], h);
-                    if (j == 0) w[u] = gt[max(-1, min(R, base + k0 + u + D))];  // the row that enters the window in the next column
+                    if (j == 0) w[u] = table_row(enter + (uint32_t)u * (uint32_t)sizeof(uint2));  // the row that enters the window in the next column
                 }
                 best = pk_maxu(best, pk_subu(rmax, Dc));
                 // the first cell's value joins the paths above the band behind this column
@@ -769,7 +824,11 @@ bool seed_diag_applicable(uint32_t max_len, uint32_t rebase_rows) {
 hipError_t launch_seed_band(const SeedBandArgs& a, int mode, bool narrow_strips, hipStream_t stream, bool diagonal) {
     if (diagonal) {  // the first tier along its diagonals (launch_score_seeded decides; score only, the narrow band's width)
         if (mode != 0 || !narrow_strips || a.wu_per16 != 0 || a.wd_per32 != 0 || a.wu0 + a.wd0 + 1 + SEED_DIAG_SLACK != DIAG_D) return hipErrorInvalidValue;
-        hipLaunchKernelGGL((seed_diag_kernel<DIAG_D>), dim3(a.grid), dim3(BLOCK), 0, stream, a);
+        // three k-mers per group of columns (zsw_seed_diag.hpp); the table's rows by 32-bit byte offsets that wrap above row 0
+        if (a.sp.K + a.sp.spacer < SEED_GROUP_MIN_STRIDE || a.ref_len >= (1u << 24)) return hipErrorInvalidValue;
+        // reads of one length share one k-mer layout: a group's patterns are wave-uniform
+        if (a.b.offsets == nullptr && !a.diag_lane_events) hipLaunchKernelGGL((seed_diag_kernel<DIAG_D, true>), dim3(a.grid), dim3(BLOCK), 0, stream, a);
+        else hipLaunchKernelGGL((seed_diag_kernel<DIAG_D, false>), dim3(a.grid), dim3(BLOCK), 0, stream, a);
         return hipGetLastError();
     }
     // H, E and the selectors are 3 * C registers (4 * C with the MODE 2 snapshot of the H row); measured: the 48-column ends kernels at

@@ -194,7 +194,7 @@ bool seed_applicable(const SeedIndex& ix, uint32_t max_len, uint32_t ref_len, ui
 hipError_t launch_score_seeded(const ScoreArgsV2& a2, int G, int C, uint32_t max_len, const SeedIndex& ix, uint8_t* work, size_t work_bytes,
                                uint2* gtab, uint32_t* fail_list, uint32_t* fail_count, int mode, const ScoreArgsV2* band_tabs, const uint2* gtab_band, int32_t* band_dbg,
                                uint32_t narrow_min_reads, uint32_t band_grid_cap, hipStream_t stream, KernelTimer* window_timer, bool narrow_only, bool reads_reversed,
-                               std::vector<uint32_t>* launches, bool strip_first_tier) {
+                               std::vector<uint32_t>* launches, bool strip_first_tier, bool diag_lane_events) {
     const uint32_t n = a2.b.n_items;
     if (n == 0) return hipSuccess;
     if (!work || !gtab || work_bytes < seed_workspace_bytes(n, max_len, band_grid_cap)) return hipErrorNotSupported;
@@ -310,6 +310,7 @@ hipError_t launch_score_seeded(const ScoreArgsV2& a2, int G, int C, uint32_t max
             b1.retry = narrow_only ? nullptr : retry;  // no second tier: what fails joins the worklist at once
             b1.accepted = narrow_only ? nullptr : accepted;
             b1.next_pair = queue1;
+            b1.diag_lane_events = diag_lane_events;
             note_launch(launches, ZSW_LAUNCH_SEED_BAND, G, C, mode);
             // score only, as the first of two tiers: the band diagonal by diagonal (seed_diag_kernel) instead of 16-column strips
             const bool diagonal = mode == 0 && !narrow_only && !strip_first_tier && seed_diag_applicable(max_len, band_tabs->K);

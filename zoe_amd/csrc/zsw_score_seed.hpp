@@ -102,6 +102,7 @@ struct SeedBandArgs {
     bool bail_check = false;
     uint32_t bail_below = 0;  // ... or with fewer items than this: a handful of reads costs the second tier one wavefront's whole walk (0.4 ms)
                               // and the full pass 30 ns each
+    bool diag_lane_events = false;     // seed_diag_kernel: every lane derives its reads' k-mer patterns, in a batch of one length too (ZSW_DEBUG_SEED_DIAG_LANE_EVENTS)
     int* dbg;                          // non-null (tests): 8 ints per read — the walk's own values (maximum, oa, ob) and its geometry
     uint32_t key_bias, fail_key;
     uint32_t* fail_list;
@@ -140,7 +141,8 @@ hipError_t seed_build_gtab(const ScoreArgsV2& a2, uint2* gtab, hipStream_t strea
 hipError_t launch_score_seeded(const ScoreArgsV2& a2, int G, int C, uint32_t max_len, const SeedIndex& ix, uint8_t* work, size_t work_bytes,
                                uint2* gtab, uint32_t* fail_list, uint32_t* fail_count, int mode, const ScoreArgsV2* band_tabs, const uint2* gtab_band, int32_t* band_dbg,
                                uint32_t narrow_min_reads, uint32_t band_grid_cap, hipStream_t stream, KernelTimer* window_timer, bool narrow_only = false, bool reads_reversed = false,
-                               std::vector<uint32_t>* launches = nullptr /* zsw_debug_score_launches */, bool strip_first_tier = false /* ZSW_DEBUG_SEED_STRIP_FIRST_TIER */);
+                               std::vector<uint32_t>* launches = nullptr /* zsw_debug_score_launches */, bool strip_first_tier = false /* ZSW_DEBUG_SEED_STRIP_FIRST_TIER */,
+                               bool diag_lane_events = false /* ZSW_DEBUG_SEED_DIAG_LANE_EVENTS */);
 // (Re)builds the index for a reference given as residue indices on the host.
 hipError_t seed_index_update(SeedIndex* ix, const ScoringDev& sc, const uint8_t* h_ref, size_t ref_len);
 void seed_index_release(SeedIndex* ix);
