@@ -29,6 +29,7 @@
 #include "zsw_score_prune.hpp"
 #include "zsw_score_seed.hpp"
 #include "zsw_score_v2.hpp"
+#include "zsw_handback.hpp"
 #include "zsw_timer.hpp"
 
 namespace zsw {
@@ -122,46 +123,20 @@ __global__ __launch_bounds__(64) void exact32_kernel(BatchDev b, const uint32_t*
 }
 
 // ------------------------------------------------------------------------------------------------
-struct Cfg {
-    int G, C;
-};
+using Cfg = StripCfg;
 // strip configurations, ascending capacity G*C
 #define ZSW_CFG_ENTRY(GV, CV) {GV, CV},
 static const Cfg kCfgs[] = {ZSW_FOR_EACH_STRIP_CONFIG(ZSW_CFG_ENTRY)};
 #undef ZSW_CFG_ENTRY
 
 constexpr int N_ASCENDING_CFGS = 20;  // the rest of kCfgs is for small batches only (score_config_for_batch)
+constexpr int N_CFGS = (int)(sizeof(kCfgs) / sizeof(kCfgs[0]));
 
-bool score_config_for(uint32_t max_len, int* G, int* C) {
-    for (int k = 0; k < N_ASCENDING_CFGS; ++k) {
-        const Cfg& c = kCfgs[k];
-        if ((uint32_t)(c.G * c.C) >= max_len) {
-            *G = c.G;
-            *C = c.C;
-            return true;
-        }
-    }
-    return false;
-}
+bool score_config_for(uint32_t max_len, int* G, int* C) { return strip_config_first_fit(kCfgs, N_ASCENDING_CFGS, max_len, G, C); }
 
-// Same, for a batch of n_items reads: a small batch cannot fill 1024 SIMDs with the narrowest strips (10 k reads of 150 bp are
-// 312 wavefronts at G = 4), so it takes more lanes per read and fewer columns per lane. The score does not depend on the choice.
-// Cost model: a step issues about 7.5*C + 25 instructions; a launch is latency-bound up to ~2 waves per SIMD, throughput-bound above.
+// Same, for a batch of n_items reads (zsw_handback.hpp: strip_config_for_batch).
 static bool score_config_for_batch(uint32_t max_len, uint32_t n_items, int* G, int* C) {
-    double best = 0;
-    bool found = false;
-    for (const Cfg& c : kCfgs) {
-        if ((uint32_t)(c.G * c.C) < max_len) continue;
-        const double waves = ((double)((n_items + 1) / 2) * c.G) / 64.0;
-        const double cost = (7.5 * c.C + 25.0) * std::max(2048.0, waves);
-        if (!found || cost < best * 0.97) {  // ties go to the narrower configuration
-            best = cost;
-            *G = c.G;
-            *C = c.C;
-            found = true;
-        }
-    }
-    return found;
+    return strip_config_for_batch(kCfgs, N_CFGS, max_len, n_items, G, C);
 }
 
 template <int G, int C>
@@ -644,29 +619,28 @@ hipError_t launch_score(const ScoringDev* d_sc, const ScoringDev& h_sc, const Ba
                 // stays on the device, so the list is launched in up to three configurations — the ones the cost model picks for
                 // 16 k, 128 k and many reads — and each launch returns at once unless the count lies in its range (measured, 1 M
                 // reads: 21 k handed back 1.27 ms at 8 lanes per pair, 1.1 ms at 16; 110 k: 4.3 ms at 4 lanes, 4.0 ms at 8).
-                const uint32_t cuts[2] = {49152u, 327680u}, probe[2] = {16384u, 131072u};
-                uint32_t lo = 0;
-                for (int k = 0; k < 3 && pe == hipSuccess; ++k) {
-                    const uint32_t hi = k < 2 ? cuts[k] : 0xffffffffu;
-                    int g2 = g, c2 = c;
+                // (zsw_handback.hpp: the plan, and the invariant tests/models/handback_plan.cpp holds it to.)
+                HandbackLaunch plan[HANDBACK_MAX_LAUNCHES];
+                ScoreArgsV2 tabs[HANDBACK_MAX_LAUNCHES];
+                int n_tabs = 0;
+                const int n_plan = handback_plan(kCfgs, N_CFGS, longest, g, c, bb.n_items, [&](int g2) {
+                    tabs[n_tabs] = a2;
+                    if (!build_tables_v2(h_sc, g2, &tabs[n_tabs])) return false;
+                    ++n_tabs;
+                    return true;
+                }, plan);
+                for (int k = 0, t = 0; k < n_plan && pe == hipSuccess; ++k) {
                     ScoreArgsV2 ah = ap;
-                    const bool other = k < 2 && lo < bb.n_items && score_config_for_batch(longest, probe[k], &g2, &c2) && g2 != g;
-                    if (other) {
-                        ah = a2;
-                        if (!build_tables_v2(h_sc, g2, &ah)) continue;  // (the class's configuration serves this range too: lo stays)
+                    if (plan[k].own_tables) {  // (tables_ok succeeded once per such launch, in the plan's order)
+                        ah = tabs[t++];
                         ah.b = ap.b;
-                        ah.b.n_items = std::min(bb.n_items, hi);  // (the grid: a longer list is not this launch's)
                         ah.n_items_dev = counter;
-                    } else if (k < 2) {
-                        continue;
                     }
-                    ah.gate_lo = lo;
-                    ah.gate_hi = hi;
-                    if (lo < bb.n_items) {
-                        note_launch(launches, ZSW_LAUNCH_V2, other ? g2 : g, other ? c2 : c, std::min(mode, 2));
-                        pe = launch_table_cfg_v2(ah, other ? g2 : g, other ? c2 : c, mode, stream);
-                    }
-                    lo = hi;
+                    ah.b.n_items = plan[k].grid_items;
+                    ah.gate_lo = plan[k].lo;
+                    ah.gate_hi = plan[k].hi;
+                    note_launch(launches, ZSW_LAUNCH_V2, plan[k].G, plan[k].C, std::min(mode, 2));
+                    pe = launch_table_cfg_v2(ah, plan[k].G, plan[k].C, mode, stream);
                 }
             }
         }
