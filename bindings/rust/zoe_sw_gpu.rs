@@ -78,6 +78,10 @@ pub const ZSW_STATUS_SOME: u8 = 0;
 pub const ZSW_STATUS_OVERFLOWED: u8 = 1;
 pub const ZSW_STATUS_UNMAPPED: u8 = 2;
 pub const ZSW_STATUS_EMPTY: u8 = 3;
+pub const ZSW_STATUS_BELOW_MIN_SCORE: u8 = 4;
+/// `zsw_option`
+pub const ZSW_OPTION_EXACT_PRUNING: i32 = 1;
+pub const ZSW_OPTION_MIN_SCORE: i32 = 2;
 
 /// `zsw_int_type`: T of `StripedProfile<T, N, S>` (`math/integer.rs:231-238`)
 #[repr(i32)]
@@ -153,6 +157,7 @@ unsafe extern "C" {
     fn zsw_debug_score_launches(ctx: *mut ZswContext, records: *mut u32, capacity: u32, out_n: *mut u32) -> i32;
     fn zsw_prune_rescored(ctx: *mut ZswContext, out_reads: *mut u64) -> i32;
     fn zsw_set_option(ctx: *mut ZswContext, option: i32, value: i64) -> i32;
+    fn zsw_min_score_counts(ctx: *mut ZswContext, out: *mut u64) -> i32;
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -267,6 +272,9 @@ fn maybe<T>(status: u8, value: impl FnOnce() -> T) -> Result<MaybeAligned<T>, Pr
         ZSW_STATUS_SOME => Ok(MaybeAligned::Some(value())),
         ZSW_STATUS_OVERFLOWED => Ok(MaybeAligned::Overflowed),
         ZSW_STATUS_UNMAPPED => Ok(MaybeAligned::Unmapped),
+        // only under `set_min_score(t > 0)`: the read scores less than t. Zoe has no variant for it; the caller that asked for
+        // the minimum was going to drop the read, which is what it does with an unmapped one.
+        ZSW_STATUS_BELOW_MIN_SCORE => Ok(MaybeAligned::Unmapped),
         _ => Err(ProfileError::EmptySequence),
     }
 }
@@ -884,6 +892,25 @@ impl GpuContext {
     pub fn set_exact_pruning(&self, on: bool) -> Result<(), GpuError> {
         // SAFETY: live context
         self.check(unsafe { zsw_set_option(self.raw, 1, i64::from(on)) }, 0, 0)
+    }
+
+    /// `zsw_set_option(ZSW_OPTION_MIN_SCORE, t)`: reads that score less than `t` come back as [`MaybeAligned::Unmapped`]
+    /// without the pass over all their cells where the seeded pass's upper bounds settle them; every other read is what
+    /// `t = 0` (off) returns. Replaces `filter(|a| a.score >= t)` after the call. Covers the score, ends, ranges and 3-pass
+    /// calls with the read as the profile; the alignment, shared-profile and strand-aware calls fail with
+    /// `ZSW_ERR_UNSUPPORTED` while `t > 0`.
+    pub fn set_min_score(&self, t: u32) -> Result<(), GpuError> {
+        // SAFETY: live context
+        self.check(unsafe { zsw_set_option(self.raw, ZSW_OPTION_MIN_SCORE, i64::from(t)) }, 0, 0)
+    }
+
+    /// `zsw_min_score_counts` of the last covered call: reads settled below the minimum by the whole-read bound, by a band
+    /// bound, by their exact score, and in total.
+    pub fn min_score_counts(&self) -> Result<[u64; 4], GpuError> {
+        let mut c = [0u64; 4];
+        // SAFETY: live context, four entries
+        self.check(unsafe { zsw_min_score_counts(self.raw, c.as_mut_ptr()) }, 0, 0)?;
+        Ok(c)
     }
 
     /// `zsw_prune_rescored`: reads the forward seeded (or column-pruned) pass of the last call handed back and that were

@@ -4,10 +4,13 @@
 // POS = ref_range.start + 1, CIGAR = states, AS:i = score.
 //
 //   g++ -O2 -std=c++17 -Iinclude examples/zsw_driver.cpp -o examples/zsw_driver -Lzoe_amd -lzoe_sw_hip -Wl,-rpath,$PWD/zoe_amd
-//   ./examples/zsw_driver reference.txt reads.fastq [--score-only | --3pass | --both-strands]
+//   ./examples/zsw_driver reference.txt reads.fastq [--score-only | --3pass | --both-strands] [--min-score T]
 // --both-strands: every read is aligned on whichever strand scores higher (sw_align_strands_from_i8_3pass); a read answered by
 // its reverse complement gets flag 16, SEQ reverse complemented and QUAL reversed, and POS / CIGAR are those of that sequence.
+// --min-score T (with --3pass or --score-only, the calls ZSW_OPTION_MIN_SCORE covers): a read that scores less than T is written as
+// an unmapped record (flag 4; `*` with --score-only), exactly as a read without any alignment is — and costs the GPU next to nothing.
 #include <algorithm>
+#include <cstdlib>
 #include <cstring>
 #include <fstream>
 #include <iostream>
@@ -34,12 +37,25 @@ static std::string read_reference(const std::string& path, std::string* name) {
 
 int main(int argc, char** argv) {
     if (argc < 3) {
-        std::cerr << "usage: zsw_driver reference.(fa|txt) reads.fastq [--score-only | --3pass | --both-strands]\n";
+        std::cerr << "usage: zsw_driver reference.(fa|txt) reads.fastq [--score-only | --3pass | --both-strands] [--min-score T]\n";
         return 2;
     }
-    const bool score_only = argc > 3 && !std::strcmp(argv[3], "--score-only");
-    const bool three_pass = argc > 3 && !std::strcmp(argv[3], "--3pass");  // sw_align_from_i8_3pass instead of sw_align_from_i8
-    const bool both_strands = argc > 3 && !std::strcmp(argv[3], "--both-strands");  // sw_align_strands_from_i8_3pass
+    bool score_only = false, three_pass = false, both_strands = false;
+    long long min_score = 0;
+    for (int k = 3; k < argc; ++k) {
+        if (!std::strcmp(argv[k], "--score-only")) score_only = true;
+        else if (!std::strcmp(argv[k], "--3pass")) three_pass = true;  // sw_align_from_i8_3pass instead of sw_align_from_i8
+        else if (!std::strcmp(argv[k], "--both-strands")) both_strands = true;  // sw_align_strands_from_i8_3pass
+        else if (!std::strcmp(argv[k], "--min-score") && k + 1 < argc) min_score = std::atoll(argv[++k]);
+        else {
+            std::cerr << "zsw_driver: unknown argument " << argv[k] << '\n';
+            return 2;
+        }
+    }
+    if (min_score < 0 || min_score > 0x7fffffffll || (min_score > 0 && !(score_only || three_pass))) {
+        std::cerr << "zsw_driver: --min-score takes a value in 1 .. 2^31 - 1 and goes with --3pass or --score-only\n";
+        return 2;
+    }
     try {
         std::string ref_name;
         const std::string reference = read_reference(argv[1], &ref_name);
@@ -54,6 +70,7 @@ int main(int argc, char** argv) {
             quals.push_back(q);
         }
         zoe::GpuContext ctx(0);
+        if (min_score > 0) ctx.set_min_score((uint32_t)min_score);
         const zoe::WeightMatrix weights = zoe::WeightMatrix::new_dna_matrix(2, -5, 'N');
         zoe::LocalProfilesBatch profiles(ctx, reads, weights, -10, -1);
         if (score_only) {

@@ -49,12 +49,14 @@ typedef enum zsw_error {
 } zsw_error;
 
 /* MaybeAligned<T> (src/alignment/types/output.rs:18-25), per read. ZSW_STATUS_EMPTY marks a read of
- * length 0, for which StripedProfile::new returns Err(ProfileError::EmptySequence). */
+ * length 0, for which StripedProfile::new returns Err(ProfileError::EmptySequence). ZSW_STATUS_BELOW_MIN_SCORE is reported
+ * only while ZSW_OPTION_MIN_SCORE is set (below): the read scores less than the caller's minimum; every other field of it is 0. */
 typedef enum zsw_status {
     ZSW_STATUS_SOME = 0,
     ZSW_STATUS_OVERFLOWED = 1,
     ZSW_STATUS_UNMAPPED = 2,
-    ZSW_STATUS_EMPTY = 3
+    ZSW_STATUS_EMPTY = 3,
+    ZSW_STATUS_BELOW_MIN_SCORE = 4
 } zsw_status;
 
 /* T of StripedProfile<T,N,S> (AlignableIntWidth, src/math/integer.rs:231-238). Unsigned types run
@@ -388,9 +390,32 @@ zsw_error zsw_timing_read_window(zsw_context* ctx, double* seconds, uint64_t* la
  * add each remaining column's own largest score; reads of 65..400 residues in batches of 98,304 or more, 8 bytes per read pair
  * and reference row of workspace for up to 2 M reads at a time; the first chip-full of a large batch decides whether the rest is
  * worth it (above 70 % handed back the others go straight to the full pass).
+ *
+ * ZSW_OPTION_MIN_SCORE (value T in [0, 2^31 - 1], default 0 = off: not one byte of any result changes). The caller discards
+ * reads that score less than T anyway; with T > 0 the library says so instead of computing their score. Let (status, score, ...)
+ * be what a covered call returns with T = 0 and thr the overflow threshold of the call's last width (255 / 65,535 / 2^32 - 1 for
+ * signed types, T::MAX - bias for unsigned ones). A read that is ZSW_STATUS_UNMAPPED, or ZSW_STATUS_SOME with score <
+ * min(T, thr), reports ZSW_STATUS_BELOW_MIN_SCORE with score 0, tier 0 (no width answered: which one would have is not known
+ * without the score), ends / ranges 0 and, in alignment calls, a zeroed record without ciglets. Every other read — SOME with
+ * score >= T, OVERFLOWED, EMPTY (decided by length before anything else) — is bit for bit what T = 0 returns, whichever kernel
+ * settled it: min(T, thr) keeps a read of true score in [thr, T) OVERFLOWED on every route. Reads are settled below T by the
+ * upper bounds the seeded pass computes anyway (the bound over the whole reference in the seed kernel, the bounds of a band
+ * walk), which spares them the pass over all their cells, or else by their exact score.
+ * Covered (read-as-profile role; host and device batches, fixed and ragged, both encodings): zsw_score_batch(_from),
+ * zsw_score_ends_batch, zsw_score_ranges_batch(_from), zsw_align_3pass_batch(_from); in the ranges and 3-pass calls T applies to
+ * the forward pass, and a read below T takes no reverse pass, bounding box or DP — as an UNMAPPED read. Alphabets of 8..32
+ * letters get the contract from the exact score alone. Not covered: zsw_align_batch(_from) and every *_shared_* and *_strands_*
+ * call return ZSW_ERR_UNSUPPORTED while T > 0 and write nothing. zsw_group_* (no option setter) and zsw_sneaky_snake_batch (no
+ * score) are unaffected.
  * Unknown options or values return ZSW_ERR_INVALID_ARGUMENT. */
-typedef enum zsw_option { ZSW_OPTION_EXACT_PRUNING = 1 } zsw_option;
+typedef enum zsw_option { ZSW_OPTION_EXACT_PRUNING = 1, ZSW_OPTION_MIN_SCORE = 2 } zsw_option;
 zsw_error zsw_set_option(zsw_context* ctx, zsw_option option, int64_t value);
+
+/* ZSW_OPTION_MIN_SCORE: how the context's last covered call settled the reads it reports as ZSW_STATUS_BELOW_MIN_SCORE (the forward
+ * pass of a ranges / 3-pass call): out[0] by the bound over the whole reference in the seed kernel, out[1] by the bounds of a band
+ * walk, out[2] by their exact score, out[3] all of them. All 0 while the option is off. Synchronises the device. With T > 0
+ * zsw_prune_rescored goes down by the reads the bounds settle: it keeps counting the reads scored over all their cells. */
+zsw_error zsw_min_score_counts(zsw_context* ctx, uint64_t* out /* 4 entries */);
 
 /* Kernel-selection overrides for the parity tests (every path below is bit-identical to the default one; the tests
  * prove it by running both). Results never depend on these bits, only which kernel produces them. They are kept apart

@@ -90,7 +90,8 @@ struct WeightMatrix {
     }
 };
 
-enum class Status : uint8_t { Some = 0, Overflowed = 1, Unmapped = 2, Empty = 3 };
+// BelowMinScore: only under GpuContext::set_min_score(t > 0) — the read scores less than t; it has no value, like an Unmapped one
+enum class Status : uint8_t { Some = 0, Overflowed = 1, Unmapped = 2, Empty = 3, BelowMinScore = 4 };
 
 template <typename T> struct MaybeAligned {
     Status status = Status::Unmapped;
@@ -133,6 +134,15 @@ class GpuContext {
     zsw_context* raw() const { return ctx_; }
     // zsw_set_option(ZSW_OPTION_EXACT_PRUNING): the exact column-pruned first pass (same results for every input)
     void set_exact_pruning(bool on) { check(zsw_set_option(ctx_, ZSW_OPTION_EXACT_PRUNING, on ? 1 : 0)); }
+    // zsw_set_option(ZSW_OPTION_MIN_SCORE): reads that score less than t come back as Status::BelowMinScore, settled by the seeded
+    // pass's upper bounds where those suffice; 0 = off. Score, ends, ranges and 3-pass calls (zoe_sw.h); the others throw while t > 0.
+    void set_min_score(uint32_t t) { check(zsw_set_option(ctx_, ZSW_OPTION_MIN_SCORE, (int64_t)t)); }
+    // zsw_min_score_counts of the last covered call: settled below by the whole-read bound, a band bound, the exact score; in total
+    std::vector<uint64_t> min_score_counts() const {
+        std::vector<uint64_t> c(4, 0);
+        check(zsw_min_score_counts(ctx_, c.data()));
+        return c;
+    }
     void check(zsw_error e) const {
         if (e == ZSW_OK) return;
         if (e >= 1 && e <= 4) throw ProfileError(e);

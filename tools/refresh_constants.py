@@ -39,7 +39,7 @@ def total(d, name, pick=lambda k: True, small_only=()):
 
 # --- the banded kernel of the headline: tools/try_seed.py 10 M = 4 seeded score calls (mode 0) + 4 seeded ranges calls (other modes)
 N_BAND, CALLS_BAND = 1e7, 4
-BAND_KERNELS = ("seed_band_kernel<", "seed_diag_kernel<")  # the strip kernel per MODE (the last template argument) and the diagonal first tier (score only)
+BAND_KERNELS = ("seed_band_kernel<", "seed_diag_kernel<")  # the strip kernel per MODE (the third template argument) and the diagonal first tier (score only)
 
 
 def band_name(k):
@@ -49,7 +49,7 @@ def band_name(k):
     return None
 
 
-band0 = lambda k: band_name(k) is not None and (band_name(k).startswith("seed_diag_kernel<") or band_name(k).endswith(",0>"))
+band0 = lambda k: band_name(k) is not None and (band_name(k).startswith("seed_diag_kernel<") or band_name(k).split(",")[2].rstrip(">") == "0")
 band_valu = total(f"{src}/band/pmc_a", "SQ_INSTS_VALU", band0) / CALLS_BAND / N_BAND
 band_fetch = total(f"{src}/band/pmc_fetch", "FETCH_SIZE", band0) * KIB / CALLS_BAND / N_BAND
 band_write = total(f"{src}/band/pmc_write", "WRITE_SIZE", band0) * KIB / CALLS_BAND / N_BAND

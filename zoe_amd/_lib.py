@@ -36,6 +36,7 @@ DEBUG_SEED_DIAG_LANE_EVENTS = 131072
 (LAUNCH_V1_FAST, LAUNCH_V1_BIASED, LAUNCH_V2, LAUNCH_WIDE, LAUNCH_V1_FAST_REV, LAUNCH_V1_BIASED_REV, LAUNCH_WIDE_REV, LAUNCH_TILE_V2, LAUNCH_TILE_WIDE,
  LAUNCH_TILE_W32, LAUNCH_EXACT32, LAUNCH_EXACT32_WORKLIST, LAUNCH_SEED_WINDOW, LAUNCH_SEED_BAND, LAUNCH_PRUNED) = range(15)
 OPTION_EXACT_PRUNING = 1
+OPTION_MIN_SCORE = 2
 INT_TYPES = {"i8": 0, "i16": 1, "i32": 2, "u8": 3, "u16": 4, "u32": 5}
 
 # every symbol include/zoe_sw.h declares (tests/test_capi_symbols.py checks the two lists agree)
@@ -50,6 +51,7 @@ SYMBOLS = [
     "zsw_group_set_reference", "zsw_group_score_batch_from", "zsw_group_score_batch_from_device", "zsw_group_align_batch_from",
     "zsw_group_align_3pass_batch_from",
     "zsw_set_complement", "zsw_score_strands_batch_from", "zsw_orient_batch", "zsw_align_3pass_strands_batch_from", "zsw_strand_counts", "zsw_debug_strand_records", "zsw_debug_score_launches",
+    "zsw_min_score_counts",
 ]
 
 
@@ -170,5 +172,6 @@ def load() -> C.CDLL:
     lib.zsw_strand_counts.argtypes = [vp, C.POINTER(C.c_uint64)]
     lib.zsw_debug_strand_records.argtypes = [vp, vp]
     lib.zsw_debug_score_launches.argtypes = [vp, u32p, C.c_uint32, u32p]
+    lib.zsw_min_score_counts.argtypes = [vp, C.POINTER(C.c_uint64)]
     _lib = lib
     return lib

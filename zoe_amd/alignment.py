@@ -26,6 +26,7 @@ import numpy as np
 from . import _lib
 
 SOME, OVERFLOWED, UNMAPPED, EMPTY = 0, 1, 2, 3
+BELOW_MIN_SCORE = 4  # only while SwContext.set_min_score(T > 0) is in force: the read scores less than T (include/zoe_sw.h)
 
 
 class ProfileError(ValueError):
@@ -330,6 +331,20 @@ class SwContext:
         """zsw_set_option, e.g. set_option(_lib.OPTION_EXACT_PRUNING, 0): every cell of every read instead of the seeded exact pass."""
         self.check(self.lib.zsw_set_option(self.h, int(option), int(value)), profile_errors=False)
 
+    def set_min_score(self, t: int):
+        """zsw_set_option(ZSW_OPTION_MIN_SCORE, t): reads that score less than t (or are Unmapped) come back with status
+        BELOW_MIN_SCORE and every other field 0, settled by the seeded pass's upper bounds where those suffice; every other read is
+        what t = 0 (off) returns. Covers the score, ends, ranges and 3-pass calls of the read-as-profile role; the others raise
+        ZSW_ERR_UNSUPPORTED while t > 0."""
+        self.set_option(_lib.OPTION_MIN_SCORE, int(t))
+
+    def min_score_counts(self):
+        """zsw_min_score_counts of the last covered call: reads settled below the minimum (by the whole-read bound, by a band
+        bound, by their exact score, in total)."""
+        c = (C.c_uint64 * 4)()
+        self.check(self.lib.zsw_min_score_counts(self.h, c))
+        return tuple(int(x) for x in c)
+
     def prune_rescored(self) -> int:
         """zsw_prune_rescored: reads the last call's forward seeded (or column-pruned) pass handed back to the full pass
         (the reversed pass of the ranges and alignment calls is not counted; include/zoe_sw.h)."""
@@ -504,7 +519,8 @@ class ReadBatch:
 
 @dataclass
 class ScoreBatch:
-    """MaybeAligned<u32> per read: status (SOME/OVERFLOWED/UNMAPPED/EMPTY) + score (valid where SOME)."""
+    """MaybeAligned<u32> per read: status (SOME/OVERFLOWED/UNMAPPED/EMPTY, BELOW_MIN_SCORE under SwContext.set_min_score) +
+    score (valid where SOME)."""
 
     score: "object"
     status: "object"
@@ -517,12 +533,13 @@ class ScoreBatch:
 
     def maybe_aligned(self, i: int):
         st = int(self.status[i])
-        return ("Some", int(self.score[i])) if st == SOME else ({1: "Overflowed", 2: "Unmapped", 3: "Empty"}[st], None)
+        return ("Some", int(self.score[i])) if st == SOME else ({1: "Overflowed", 2: "Unmapped", 3: "Empty", 4: "BelowMinScore"}[st], None)
 
 
 @dataclass
 class AlignmentBatch:
-    """MaybeAligned<Alignment<u32>> per read; ciglets flattened (inc, op) with per-read offsets."""
+    """MaybeAligned<Alignment<u32>> per read; ciglets flattened (inc, op) with per-read offsets. A read below the context's
+    minimum score (status BELOW_MIN_SCORE) has a zeroed record and no ciglets, like an UNMAPPED one."""
 
     status: np.ndarray
     records: np.ndarray  # structured: score, ref_start, ref_end, query_start, query_end, ref_len, query_len, n_ciglets, ciglet_offset

@@ -183,6 +183,11 @@ zsw_error stage(zsw_context* ctx, const zsw_batch* reads, hipStream_t stream, bo
         ZSW_HIP(ctx, ctx->d_tile_state.ensure((size_t)n * 16 + 16));
     }
     ZSW_HIP(ctx, ctx->d_bucket_counts.ensure(64 * 4));
+    ctx->min_counts_valid = ctx->min_score != 0;
+    if (ctx->min_score) {  // ZSW_OPTION_MIN_SCORE: the counters of zsw_min_score_counts for this call
+        ZSW_HIP(ctx, ctx->d_min_counts.ensure(4 * 4));
+        ZSW_HIP(ctx, hipMemsetAsync(ctx->d_min_counts.p, 0, 4 * 4, stream));
+    }
     ctx->prune_chunk = 0;
     ctx->seed_ready = false;
     ctx->chunk_ready = false;
@@ -288,6 +293,10 @@ ScoreWorkspace score_ws(zsw_context* ctx) {
     w.side = ctx->side;
     w.debug = ctx->flags();
     w.launch_log = &ctx->score_launches;
+    if (ctx->min_score && ctx->min_counts_valid) {
+        w.min_score = ctx->min_score;
+        w.min_counts = ctx->d_min_counts.as<uint32_t>();
+    }
     if (ctx->seed_ready) {
         w.seed = ctx->shared_call ? &ctx->seed_shared : &ctx->seed;
         w.seed_work = ctx->d_seed_work.as<uint8_t>();
@@ -526,6 +535,8 @@ zsw_error ranges_device(zsw_context* ctx, const Staged& st, const ResultRule& ru
             ScoreWorkspace w = score_ws(ctx);
             w.seed = &ctx->seed_rev;
             w.band_dbg = nullptr;
+            w.min_score = 0;  // ZSW_OPTION_MIN_SCORE applies to the forward pass; a read below it is not SOME and nothing reads its reverse pass
+            w.min_counts = nullptr;
             hipError_t e3 = launch_score(ctx->d_sc.as<ScoringDev>(), ctx->h_sc, brev, st.max_len, ctx->d_ref_rev.as<uint8_t>(), (uint32_t)R, rule, o3, w, stream,
                                          nullptr, 3);
             if (e3 != hipSuccess) return fail(ctx, ZSW_ERR_HIP, "ranges: seeded reverse pass", e3);
@@ -1058,6 +1069,7 @@ extern "C" {
 zsw_error zsw_align_batch(zsw_context* ctx, const zsw_batch* reads, zsw_int_type int_type, int lanes, int invert,
                           zsw_alignment* out_aln, uint8_t* out_status, uint32_t* out_inc, uint8_t* out_op,
                           uint64_t ciglet_cap, uint64_t* out_n_ciglets, void* stream) {
+    if (zsw_error ze = min_score_unsupported(ctx, "zsw_align_batch"); ze != ZSW_OK) return ze;
     ResultRule rule;
     if (zsw_error ze = rule_direct(ctx, int_type, lanes, &rule); ze != ZSW_OK) return ze;
     return run_align(ctx, reads, rule, lanes, lanes, lanes, invert, out_aln, out_status, nullptr, out_inc, out_op, ciglet_cap,
@@ -1067,6 +1079,7 @@ zsw_error zsw_align_batch(zsw_context* ctx, const zsw_batch* reads, zsw_int_type
 zsw_error zsw_align_batch_from(zsw_context* ctx, const zsw_batch* reads, int from_width, int preset_bits, int invert,
                                zsw_alignment* out_aln, uint8_t* out_status, uint8_t* out_tier, uint32_t* out_inc,
                                uint8_t* out_op, uint64_t ciglet_cap, uint64_t* out_n_ciglets, void* stream) {
+    if (zsw_error ze = min_score_unsupported(ctx, "zsw_align_batch_from"); ze != ZSW_OK) return ze;
     ResultRule rule;
     if (zsw_error ze = rule_cascade(ctx, from_width, preset_bits, &rule); ze != ZSW_OK) return ze;
     return run_align(ctx, reads, rule, preset_bits / 8, preset_bits / 16, preset_bits / 32, invert, out_aln, out_status, out_tier,
@@ -1124,7 +1137,7 @@ void zsw_destroy(zsw_context* ctx) {
     DeviceGuard device_guard(ctx);
     if (!ctx) return;
     (void)hipSetDevice(ctx->device);
-    DevBuf* bufs[] = {&ctx->d_sc, &ctx->d_ref, &ctx->d_fb_list, &ctx->d_fb_count, &ctx->d_scratch, &ctx->d_maxlen, &ctx->d_bucket_items, &ctx->d_bucket_counts, &ctx->d_tile_buf, &ctx->d_tile_state, &ctx->d_prune, &ctx->d_prune_list, &ctx->d_prune_count, &ctx->d_seed_work, &ctx->d_seed_gtab, &ctx->d_chunk_keys, &ctx->d_pseq, &ctx->d_pseq_rev, &ctx->d_sc_t,
+    DevBuf* bufs[] = {&ctx->d_sc, &ctx->d_ref, &ctx->d_fb_list, &ctx->d_fb_count, &ctx->d_scratch, &ctx->d_maxlen, &ctx->d_bucket_items, &ctx->d_bucket_counts, &ctx->d_tile_buf, &ctx->d_tile_state, &ctx->d_prune, &ctx->d_prune_list, &ctx->d_prune_count, &ctx->d_seed_work, &ctx->d_seed_gtab, &ctx->d_chunk_keys, &ctx->d_min_counts, &ctx->d_pseq, &ctx->d_pseq_rev, &ctx->d_sc_t,
                       &ctx->s_bases, &ctx->s_packed, &ctx->s_offsets, &ctx->s_score, &ctx->s_status, &ctx->s_tier, &ctx->s_rend, &ctx->s_qend};
     for (DevBuf* b : bufs) b->release();
     for (DevBuf& b : ctx->a_ws) b.release();
@@ -1457,7 +1470,25 @@ zsw_error zsw_set_option(zsw_context* ctx, zsw_option option, int64_t value) {
         }
         return ZSW_OK;
     }
+    if (option == ZSW_OPTION_MIN_SCORE && value >= 0 && value <= 0x7fffffffll) {
+        ctx->min_score = (uint32_t)value;
+        if (!value) ctx->min_counts_valid = false;
+        return ZSW_OK;
+    }
     return fail(ctx, ZSW_ERR_INVALID_ARGUMENT, "unknown option or value");
+}
+
+zsw_error zsw_min_score_counts(zsw_context* ctx, uint64_t* out) {
+    DeviceGuard device_guard(ctx);
+    if (!ctx || !out) return ZSW_ERR_INVALID_ARGUMENT;
+    out[0] = out[1] = out[2] = out[3] = 0;
+    if (!ctx->min_counts_valid || !ctx->d_min_counts.p) return ZSW_OK;
+    uint32_t c[3] = {0, 0, 0};
+    ZSW_HIP(ctx, hipDeviceSynchronize());
+    ZSW_HIP(ctx, hipMemcpy(c, ctx->d_min_counts.p, sizeof(c), hipMemcpyDeviceToHost));
+    for (int k = 0; k < 3; ++k) out[k] = c[k];
+    out[3] = (uint64_t)c[0] + c[1] + c[2];
+    return ZSW_OK;
 }
 
 zsw_error zsw_prune_rescored(zsw_context* ctx, uint64_t* out_reads) {

@@ -506,6 +506,7 @@ zsw_error zsw_set_profile_sequence(zsw_context* ctx, const uint8_t* sequence, si
 
 zsw_error zsw_score_shared_batch(zsw_context* ctx, const zsw_batch* reads, zsw_int_type int_type, int lanes, uint32_t* out_score,
                                  uint8_t* out_status, void* stream) {
+    if (zsw_error ze = min_score_unsupported(ctx, "zsw_score_shared_batch"); ze != ZSW_OK) return ze;
     ResultRule rule;
     if (zsw_error ze = rule_direct(ctx, int_type, lanes, &rule); ze != ZSW_OK) return ze;
     return run_score_shared(ctx, reads, rule, out_score, out_status, nullptr, stream);
@@ -513,6 +514,7 @@ zsw_error zsw_score_shared_batch(zsw_context* ctx, const zsw_batch* reads, zsw_i
 
 zsw_error zsw_score_shared_batch_from(zsw_context* ctx, const zsw_batch* reads, int from_width, int preset_bits, uint32_t* out_score,
                                       uint8_t* out_status, uint8_t* out_tier, void* stream) {
+    if (zsw_error ze = min_score_unsupported(ctx, "zsw_score_shared_batch_from"); ze != ZSW_OK) return ze;
     ResultRule rule;
     if (zsw_error ze = rule_cascade(ctx, from_width, preset_bits, &rule); ze != ZSW_OK) return ze;
     return run_score_shared(ctx, reads, rule, out_score, out_status, out_tier, stream);
@@ -520,6 +522,7 @@ zsw_error zsw_score_shared_batch_from(zsw_context* ctx, const zsw_batch* reads, 
 
 zsw_error zsw_score_ends_shared_batch(zsw_context* ctx, const zsw_batch* reads, zsw_int_type int_type, int lanes, uint32_t* out_score,
                                       uint32_t* out_ref_end, uint32_t* out_query_end, uint8_t* out_status, void* stream) {
+    if (zsw_error ze = min_score_unsupported(ctx, "zsw_score_ends_shared_batch"); ze != ZSW_OK) return ze;
     ResultRule rule;
     if (zsw_error ze = rule_direct(ctx, int_type, lanes, &rule); ze != ZSW_OK) return ze;
     return run_ends_shared(ctx, reads, rule, out_score, out_ref_end, out_query_end, out_status, stream);
@@ -528,6 +531,7 @@ zsw_error zsw_score_ends_shared_batch(zsw_context* ctx, const zsw_batch* reads, 
 zsw_error zsw_score_ranges_shared_batch(zsw_context* ctx, const zsw_batch* reads, zsw_int_type int_type, int lanes, uint32_t* out_score,
                                         uint32_t* out_ref_start, uint32_t* out_ref_end, uint32_t* out_query_start, uint32_t* out_query_end,
                                         uint8_t* out_status, void* stream) {
+    if (zsw_error ze = min_score_unsupported(ctx, "zsw_score_ranges_shared_batch"); ze != ZSW_OK) return ze;
     ResultRule rule;
     if (zsw_error ze = rule_direct(ctx, int_type, lanes, &rule); ze != ZSW_OK) return ze;
     return run_ranges_shared(ctx, reads, rule, out_score, out_ref_start, out_ref_end, out_query_start, out_query_end, out_status, nullptr, stream);
@@ -536,6 +540,7 @@ zsw_error zsw_score_ranges_shared_batch(zsw_context* ctx, const zsw_batch* reads
 zsw_error zsw_score_ranges_shared_batch_from(zsw_context* ctx, const zsw_batch* reads, int from_width, int preset_bits, uint32_t* out_score,
                                              uint32_t* out_ref_start, uint32_t* out_ref_end, uint32_t* out_query_start, uint32_t* out_query_end,
                                              uint8_t* out_status, uint8_t* out_tier, void* stream) {
+    if (zsw_error ze = min_score_unsupported(ctx, "zsw_score_ranges_shared_batch_from"); ze != ZSW_OK) return ze;
     ResultRule rule;
     if (zsw_error ze = rule_cascade(ctx, from_width, preset_bits, &rule); ze != ZSW_OK) return ze;
     return run_ranges_shared(ctx, reads, rule, out_score, out_ref_start, out_ref_end, out_query_start, out_query_end, out_status, out_tier, stream);
@@ -543,6 +548,7 @@ zsw_error zsw_score_ranges_shared_batch_from(zsw_context* ctx, const zsw_batch* 
 
 zsw_error zsw_align_shared_batch(zsw_context* ctx, const zsw_batch* reads, zsw_int_type int_type, int lanes, int invert, zsw_alignment* out_aln,
                                  uint8_t* out_status, uint32_t* out_inc, uint8_t* out_op, uint64_t ciglet_cap, uint64_t* out_n_ciglets, void* stream) {
+    if (zsw_error ze = min_score_unsupported(ctx, "zsw_align_shared_batch"); ze != ZSW_OK) return ze;
     ResultRule rule;
     if (zsw_error ze = rule_direct(ctx, int_type, lanes, &rule); ze != ZSW_OK) return ze;
     return run_align_shared(ctx, reads, rule, lanes, lanes, lanes, invert, out_aln, out_status, nullptr, out_inc, out_op, ciglet_cap, out_n_ciglets,
@@ -552,6 +558,7 @@ zsw_error zsw_align_shared_batch(zsw_context* ctx, const zsw_batch* reads, zsw_i
 zsw_error zsw_align_shared_batch_from(zsw_context* ctx, const zsw_batch* reads, int from_width, int preset_bits, int invert, zsw_alignment* out_aln,
                                       uint8_t* out_status, uint8_t* out_tier, uint32_t* out_inc, uint8_t* out_op, uint64_t ciglet_cap,
                                       uint64_t* out_n_ciglets, void* stream) {
+    if (zsw_error ze = min_score_unsupported(ctx, "zsw_align_shared_batch_from"); ze != ZSW_OK) return ze;
     ResultRule rule;
     if (zsw_error ze = rule_cascade(ctx, from_width, preset_bits, &rule); ze != ZSW_OK) return ze;
     return run_align_shared(ctx, reads, rule, preset_bits / 8, preset_bits / 16, preset_bits / 32, invert, out_aln, out_status, out_tier, out_inc,
@@ -560,6 +567,7 @@ zsw_error zsw_align_shared_batch_from(zsw_context* ctx, const zsw_batch* reads, 
 
 zsw_error zsw_align_3pass_shared_batch(zsw_context* ctx, const zsw_batch* reads, zsw_int_type int_type, int lanes, int invert, zsw_alignment* out_aln,
                                        uint8_t* out_status, uint32_t* out_inc, uint8_t* out_op, uint64_t ciglet_cap, uint64_t* out_n_ciglets, void* stream) {
+    if (zsw_error ze = min_score_unsupported(ctx, "zsw_align_3pass_shared_batch"); ze != ZSW_OK) return ze;
     ResultRule rule;
     if (zsw_error ze = rule_direct(ctx, int_type, lanes, &rule); ze != ZSW_OK) return ze;
     return run_threepass_shared(ctx, reads, rule, invert, out_aln, out_status, nullptr, out_inc, out_op, ciglet_cap, out_n_ciglets, stream);
@@ -568,6 +576,7 @@ zsw_error zsw_align_3pass_shared_batch(zsw_context* ctx, const zsw_batch* reads,
 zsw_error zsw_align_3pass_shared_batch_from(zsw_context* ctx, const zsw_batch* reads, int from_width, int preset_bits, int invert, zsw_alignment* out_aln,
                                             uint8_t* out_status, uint8_t* out_tier, uint32_t* out_inc, uint8_t* out_op, uint64_t ciglet_cap,
                                             uint64_t* out_n_ciglets, void* stream) {
+    if (zsw_error ze = min_score_unsupported(ctx, "zsw_align_3pass_shared_batch_from"); ze != ZSW_OK) return ze;
     ResultRule rule;
     if (zsw_error ze = rule_cascade(ctx, from_width, preset_bits, &rule); ze != ZSW_OK) return ze;
     return run_threepass_shared(ctx, reads, rule, invert, out_aln, out_status, out_tier, out_inc, out_op, ciglet_cap, out_n_ciglets, stream);

@@ -79,6 +79,11 @@ struct zsw_context {
     std::vector<uint32_t> score_launches;  // zsw_debug_score_launches (tests: the score kernels the last call launched, 4 entries each)
     uint32_t options = ZSW_DEBUG_SCORE_PRUNE;  // zsw_set_option, as ZSW_DEBUG_* bits; exact pruning is on by default
     uint32_t flags() const { return debug | options; }
+    // ZSW_OPTION_MIN_SCORE: T (0 = off), and three device counters of the last covered call (ScoreWorkspace::min_counts), zeroed
+    // by stage() while the option is on
+    uint32_t min_score = 0;
+    zsw::DevBuf d_min_counts;
+    bool min_counts_valid = false;
     // host batches: reads of chunk k+1 cross PCIe on this stream while chunk k computes
     hipStream_t copy_stream = nullptr;
     std::vector<hipEvent_t> copy_events;
@@ -189,6 +194,13 @@ inline zsw_error rule_cascade(zsw_context* ctx, int from_width, int preset_bits,
         ++r->n_tiers;
     }
     return ZSW_OK;
+}
+
+// Entry points ZSW_OPTION_MIN_SCORE does not cover refuse to run while it is set (and write nothing)
+inline zsw_error min_score_unsupported(zsw_context* ctx, const char* what) {
+    if (!ctx || !ctx->min_score) return ZSW_OK;
+    ctx->err = std::string(what) + ": not covered by ZSW_OPTION_MIN_SCORE; set the option to 0 for this call";
+    return ZSW_ERR_UNSUPPORTED;
 }
 
 struct Staged {

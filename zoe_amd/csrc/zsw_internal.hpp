@@ -122,7 +122,20 @@ struct ScoreWorkspace {
     unsigned long long* chunk_keys = nullptr;  // one per read: row-chunked full pass over the reads the seeded pass hands back (long references)
     uint32_t debug = 0;           // ZSW_DEBUG_* bits of the context (zsw_debug_set) | its options: kernel-selection overrides
     std::vector<uint32_t>* launch_log = nullptr;  // zsw_debug_score_launches: the context's list, four entries per kernel launch
+    // ZSW_OPTION_MIN_SCORE (0 = off: launch_score launches what it always did). launch_score settles the reads below
+    // min_threshold(rule, min_score): by the seeded pass's bounds where it runs, and by a trailing filter over the results of every
+    // other route (min_filter_kernel), so that the answer does not depend on the route. Passes that must not filter (the reversed
+    // pass of the ranges) clear it. min_counts: three device counters — settled by the whole-read bound, by a band bound, by the score.
+    uint32_t min_score = 0;
+    uint32_t* min_counts = nullptr;
 };
+
+// ZSW_OPTION_MIN_SCORE: a read is below the minimum if it scores less than min(T, overflow threshold of the call's last tier) — a
+// read at or beyond that threshold stays OVERFLOWED, whichever kernel scored it (T <= 2^31 - 1)
+inline uint32_t min_threshold(const ResultRule& r, uint32_t min_score) {
+    const uint64_t thr = r.thr[r.n_tiers - 1];
+    return thr < (uint64_t)min_score ? (uint32_t)thr : min_score;
+}
 
 // zsw_debug_score_launches: one record per kernel launch of the score launchers (host bookkeeping only)
 inline void note_launch(std::vector<uint32_t>* log, uint32_t kind, int G, int C, int mode) {

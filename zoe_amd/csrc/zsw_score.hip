@@ -416,9 +416,46 @@ __global__ void bucket_scatter_kernel(const uint64_t* offsets, uint32_t n, Bucke
 
 __global__ void add_count_kernel(const uint32_t* count, uint32_t* total) { atomicAdd(total, *count); }
 
+// ZSW_OPTION_MIN_SCORE, the exact-score route: behind every kernel of launch_score, whichever scored a read. A read that is
+// UNMAPPED, or SOME with a score below min_thr (= min(T, the last tier's overflow threshold): an OVERFLOWED read never is), becomes
+// BELOW_MIN_SCORE with every other field 0 — what the seed kernel and the band tiers wrote for the reads their bounds settled.
+// Grid-stride, one atomic per wavefront at the end.
+__global__ void min_filter_kernel(BatchDev b, uint32_t min_thr, ScoreOut out, uint32_t* count) {
+    uint32_t mine = 0;
+    for (uint32_t i = blockIdx.x * blockDim.x + threadIdx.x; i < b.n_items; i += gridDim.x * blockDim.x) {
+        const uint32_t id = b.items ? b.items[i] : i;
+        const uint8_t st = out.status[id];
+        if (st == ZSW_STATUS_UNMAPPED || (st == ZSW_STATUS_SOME && out.score[id] < min_thr)) {
+            out.score[id] = 0;
+            out.status[id] = ZSW_STATUS_BELOW_MIN_SCORE;
+            if (out.tier) out.tier[id] = 0;
+            if (out.ref_end) out.ref_end[id] = 0;
+            if (out.query_end) out.query_end[id] = 0;
+            ++mine;
+        }
+    }
+#pragma unroll
+    for (int d = 32; d >= 1; d >>= 1) mine += (uint32_t)__shfl_xor((int)mine, d, 64);
+    if ((threadIdx.x & 63) == 0 && mine) atomicAdd(count, mine);
+}
+
+static hipError_t launch_score_passes(const ScoringDev* d_sc, const ScoringDev& h_sc, const BatchDev& b, uint32_t max_len,
+                                      const uint8_t* d_ref, uint32_t ref_len, const ResultRule& rule, const ScoreOut& out,
+                                      const ScoreWorkspace& ws, hipStream_t stream, KernelTimer* timer, int mode);
+
 hipError_t launch_score(const ScoringDev* d_sc, const ScoringDev& h_sc, const BatchDev& b, uint32_t max_len,
                         const uint8_t* d_ref, uint32_t ref_len, const ResultRule& rule, const ScoreOut& out,
                         const ScoreWorkspace& ws, hipStream_t stream, KernelTimer* timer, int mode) {
+    hipError_t e = launch_score_passes(d_sc, h_sc, b, max_len, d_ref, ref_len, rule, out, ws, stream, timer, mode);
+    if (e != hipSuccess || !ws.min_score || !ws.min_counts || b.n_items == 0) return e;
+    hipLaunchKernelGGL(min_filter_kernel, dim3(std::min<uint32_t>((b.n_items + 255) / 256, 4096u)), dim3(256), 0, stream, b, min_threshold(rule, ws.min_score), out,
+                       ws.min_counts + 2);
+    return hipGetLastError();
+}
+
+static hipError_t launch_score_passes(const ScoringDev* d_sc, const ScoringDev& h_sc, const BatchDev& b, uint32_t max_len,
+                                      const uint8_t* d_ref, uint32_t ref_len, const ResultRule& rule, const ScoreOut& out,
+                                      const ScoreWorkspace& ws, hipStream_t stream, KernelTimer* timer, int mode) {
     hipError_t e = hipMemsetAsync(out.fb_count, 0, sizeof(uint32_t), stream);
     if (e != hipSuccess) return e;
     int G = 0, C = 0;
@@ -587,7 +624,8 @@ hipError_t launch_score(const ScoringDev* d_sc, const ScoringDev& h_sc, const Ba
                                  ws.prune_fail_list + list_off, counter, mode, band_ok ? &ab : nullptr, gtab_band, ws.band_dbg,
                                  (ws.debug & ZSW_DEBUG_SEED_WIDE_BAND) ? 0xffffffffu : (ws.debug & ZSW_DEBUG_SCORE_PRUNE_ANY_SIZE) ? 0u : SEED_NARROW_MIN_READS, band_grid_cap, stream,
                                  ws.window_timer, out.narrow_only, out.reads_reversed && out.skip_handed_back, launches,
-                                 (ws.debug & ZSW_DEBUG_SEED_STRIP_FIRST_TIER) != 0, (ws.debug & ZSW_DEBUG_SEED_DIAG_LANE_EVENTS) != 0);
+                                 (ws.debug & ZSW_DEBUG_SEED_STRIP_FIRST_TIER) != 0, (ws.debug & ZSW_DEBUG_SEED_DIAG_LANE_EVENTS) != 0,
+                                 (ws.min_score && ws.min_counts && !out.skip_handed_back) ? min_threshold(rule, ws.min_score) : 0u, ws.min_counts);
         if (pe != hipSuccess) return pe;
         ap.b.items = ws.prune_fail_list + list_off;
         ap.n_items_dev = counter;

@@ -198,9 +198,13 @@ __device__ __forceinline__ int band_fetch(const SeedBandArgs& a, int tid, uint32
 
 // best: the band's maximum of either read (doubled, odd: held by a path that touched a cell outside the band); oa2 / ob2: the most
 // a path that ends above / below the band can score (plain, per half); geom / C: rec[5] and the columns per strip of the debug record
-template <int MODE>
+// MINS (ZSW_OPTION_MIN_SCORE > 0; instantiations of their own): a read the walk does not accept, but whose matrix holds no cell of
+// a.min_thr or more (seed_band_upper, zsw_seed.hpp: the band's cells are at least their true H, the cells outside at most oa / ob),
+// is settled as BELOW_MIN_SCORE here — in the first tier too: a bound is a bound. It counts as accepted, or a diverged batch that
+// the minimum settles would trip the second tier's bail-out.
+template <int MODE, bool MINS>
 __device__ __forceinline__ void band_finish(const SeedBandArgs& a, const BandPair& p, uint32_t best, uint32_t oa2, uint32_t ob2, int dtmin, int dtmax, int geom, int C,
-                                            uint32_t infoA, uint32_t infoB, const BandEnds& e, uint32_t* n_accepted) {
+                                            uint32_t infoA, uint32_t infoB, const BandEnds& e, uint32_t* n_accepted, uint32_t* n_below) {
     const uint32_t best2A = best & 0xffffu, best2B = best >> 16;
     const int tallA = (int)(infoA & 0xffffu), tallB = (int)(infoB & 0xffffu);
     const int dfaA = (int)((infoA >> 16) & 0xffu), dfaB = (int)((infoB >> 16) & 0xffu);
@@ -225,7 +229,15 @@ __device__ __forceinline__ void band_finish(const SeedBandArgs& a, const BandPai
             rec[6] = h ? p.dtB : p.dtA;
             rec[7] = (((h ? p.lenB : p.lenA) == 0 || redo) ? 0 : 1) | (C << 8);
         }
-        if ((h ? p.lenB : p.lenA) == 0 || redo) {
+        if (MINS && (h ? p.lenB : p.lenA) != 0 && redo && seed_below_min(seed_band_upper(b2, oa, ob), a.min_thr)) {
+            ++*n_accepted;
+            ++*n_below;
+            a.out.score[id] = 0;
+            a.out.status[id] = ZSW_STATUS_BELOW_MIN_SCORE;
+            if (a.out.tier) a.out.tier[id] = 0;
+            if (MODE != 0 && a.out.ref_end) a.out.ref_end[id] = 0;
+            if (MODE >= 2 && a.out.query_end) a.out.query_end[id] = 0;
+        } else if ((h ? p.lenB : p.lenA) == 0 || redo) {
             if (a.retry) a.retry[h ? p.itemB : p.itemA] = 1;
             else a.fail_list[atomicAdd(a.fail_count, 1u)] = id;
         } else {
@@ -254,8 +266,14 @@ __device__ __forceinline__ void band_count_accepted(const SeedBandArgs& a, int t
         if ((tid & 63) == 0 && n_accepted) atomicAdd(a.accepted, n_accepted);
     }
 }
+// MINS: the reads a block settled below the minimum, one atomic per wavefront
+__device__ __forceinline__ void band_count_below(const SeedBandArgs& a, int tid, uint32_t n_below) {
+#pragma unroll
+    for (int d = 32; d >= 1; d >>= 1) n_below += (uint32_t)__shfl_xor((int)n_below, d, 64);
+    if ((tid & 63) == 0 && n_below) atomicAdd(a.min_count, n_below);
+}
 
-template <int C, int MINW, int MODE>
+template <int C, int MINW, int MODE, bool MINS>
 __global__ __launch_bounds__(BLOCK, MINW) void seed_band_kernel(SeedBandArgs a) {
     constexpr int TAG = MODE == 0 ? -1 : 1;
     using M = std::conditional_t<(C > 32), uint64_t, uint32_t>;  // one bit per column of a strip
@@ -274,6 +292,7 @@ __global__ __launch_bounds__(BLOCK, MINW) void seed_band_kernel(SeedBandArgs a) 
     const uint32_t n_pairs = (n_items + 1) / 2;
     const bool bail = a.bail_check && a.accepted && ((uint64_t)(*a.accepted) * SEED_BAIL_RATIO < (uint64_t)n_items || n_items < a.bail_below);
     uint32_t n_accepted = 0;  // (first tier)
+    uint32_t n_below = 0;     // (MINS)
     const uint32_t ge2 = a.ge2, gd2 = a.gd2;  // doubled gap penalties (the tables hold doubled scores)
     const uint32_t ge1 = ge2 & 0xffffu;
     const uint32_t maxw2 = (uint32_t)a.sp.maxw * 0x00010001u, go2p = (uint32_t)a.sp.go * 0x00010001u;  // plain (not doubled) scores of the bound programmes
@@ -552,11 +571,12 @@ __global__ __launch_bounds__(BLOCK, MINW) void seed_band_kernel(SeedBandArgs a) 
         ends.colB = colB;
         ends.multA = multA;
         ends.multB = multB;
-        band_finish<MODE>(a, P, best, (uint32_t)st[BF_OA * BLOCK], (uint32_t)st[BF_OB * BLOCK], dtmin, dtmax, n_strips | (wu << 8) | (wd << 20), C, infoA, infoB, ends,
-                          &n_accepted);
+        band_finish<MODE, MINS>(a, P, best, (uint32_t)st[BF_OA * BLOCK], (uint32_t)st[BF_OB * BLOCK], dtmin, dtmax, n_strips | (wu << 8) | (wd << 20), C, infoA, infoB, ends,
+                                &n_accepted, &n_below);
         }  // fetched == 2
     }
     band_count_accepted(a, tid, n_accepted);
+    if (MINS) band_count_below(a, tid, n_below);
 }
 
 // ---- the first tier along its diagonals (score only) ------------------------------------------------------------------------
@@ -611,7 +631,7 @@ __device__ __forceinline__ DiagGroupEvents diag_group_events(const SeedGroupPatt
 // UNI: every read of the launch has the same length (a.b.offsets == nullptr: launch_seed_band decides), so the k-mer layout and
 // with it a group's patterns are wave-uniform — scalar registers and scalar instructions; only the picks by the reads' masks are
 // per lane. Otherwise (a ragged batch, or ZSW_DEBUG_SEED_DIAG_LANE_EVENTS) every lane derives the patterns of its two reads.
-template <int D, bool UNI>
+template <int D, bool UNI, bool MINS>
 __global__ __launch_bounds__(BLOCK, 3) void seed_diag_kernel(SeedBandArgs a) {
     constexpr int TAG = -1;
     static_assert(D == 16, "a group of columns is two dwords of residue codes and 16 bits per read in the column masks");
@@ -631,6 +651,7 @@ __global__ __launch_bounds__(BLOCK, 3) void seed_diag_kernel(SeedBandArgs a) {
     const uint32_t n_pairs = (n_items + 1) / 2;
     const bool bail = a.bail_check && a.accepted && ((uint64_t)(*a.accepted) * SEED_BAIL_RATIO < (uint64_t)n_items || n_items < a.bail_below);
     uint32_t n_accepted = 0;
+    uint32_t n_below = 0;  // (MINS)
     const uint32_t ge2 = a.ge2, gd2 = a.gd2;
     const uint32_t ge1 = ge2 & 0xffffu;
     const uint32_t maxw2 = (uint32_t)a.sp.maxw * 0x00010001u, go2p = (uint32_t)a.sp.go * 0x00010001u;
@@ -787,10 +808,11 @@ __global__ __launch_bounds__(BLOCK, 3) void seed_diag_kernel(SeedBandArgs a) {
                 }
             }
         }
-        band_finish<0>(a, P, best, oa2, ob2, dtmin, dtmax, lenmax | (wu << 8) | (wd << 20), 1, infoA, infoB, BandEnds{}, &n_accepted);
+        band_finish<0, MINS>(a, P, best, oa2, ob2, dtmin, dtmax, lenmax | (wu << 8) | (wd << 20), 1, infoA, infoB, BandEnds{}, &n_accepted, &n_below);
         }  // fetched == 2
     }
     band_count_accepted(a, tid, n_accepted);
+    if (MINS) band_count_below(a, tid, n_below);
 }
 
 }  // namespace
@@ -821,30 +843,37 @@ bool seed_diag_applicable(uint32_t max_len, uint32_t rebase_rows) {
     return max_len <= SEED_DIAG_MAX_LEN && max_len + 2 <= rebase_rows;
 }
 
-hipError_t launch_seed_band(const SeedBandArgs& a, int mode, bool narrow_strips, hipStream_t stream, bool diagonal) {
+// MINS: the instantiations that also settle reads below a.min_thr (ZSW_OPTION_MIN_SCORE); the others are what they were
+template <bool MINS>
+static hipError_t launch_seed_band_t(const SeedBandArgs& a, int mode, bool narrow_strips, hipStream_t stream, bool diagonal) {
     if (diagonal) {  // the first tier along its diagonals (launch_score_seeded decides; score only, the narrow band's width)
         if (mode != 0 || !narrow_strips || a.wu_per16 != 0 || a.wd_per32 != 0 || a.wu0 + a.wd0 + 1 + SEED_DIAG_SLACK != DIAG_D) return hipErrorInvalidValue;
         // three k-mers per group of columns (zsw_seed_diag.hpp); the table's rows by 32-bit byte offsets that wrap above row 0
         if (a.sp.K + a.sp.spacer < SEED_GROUP_MIN_STRIDE || a.ref_len >= (1u << 24)) return hipErrorInvalidValue;
         // reads of one length share one k-mer layout: a group's patterns are wave-uniform
-        if (a.b.offsets == nullptr && !a.diag_lane_events) hipLaunchKernelGGL((seed_diag_kernel<DIAG_D, true>), dim3(a.grid), dim3(BLOCK), 0, stream, a);
-        else hipLaunchKernelGGL((seed_diag_kernel<DIAG_D, false>), dim3(a.grid), dim3(BLOCK), 0, stream, a);
+        if (a.b.offsets == nullptr && !a.diag_lane_events) hipLaunchKernelGGL((seed_diag_kernel<DIAG_D, true, MINS>), dim3(a.grid), dim3(BLOCK), 0, stream, a);
+        else hipLaunchKernelGGL((seed_diag_kernel<DIAG_D, false, MINS>), dim3(a.grid), dim3(BLOCK), 0, stream, a);
         return hipGetLastError();
     }
     // H, E and the selectors are 3 * C registers (4 * C with the MODE 2 snapshot of the H row); measured: the 48-column ends kernels at
     // one wavefront per SIMD (AGPRs as spill space) beat two with scratch by 16 %, the score-only kernel at two beats one by 4 %
     if (narrow_strips) {
-        if (mode == 0) hipLaunchKernelGGL((seed_band_kernel<BC_NARROW, 4, 0>), dim3(a.grid), dim3(BLOCK), 0, stream, a);
-        else if (mode == 1) hipLaunchKernelGGL((seed_band_kernel<BC_NARROW, 4, 1>), dim3(a.grid), dim3(BLOCK), 0, stream, a);
-        else if (mode == 2) hipLaunchKernelGGL((seed_band_kernel<BC_NARROW, 3, 2>), dim3(a.grid), dim3(BLOCK), 0, stream, a);
-        else hipLaunchKernelGGL((seed_band_kernel<BC_NARROW, 3, 3>), dim3(a.grid), dim3(BLOCK), 0, stream, a);
+        if (mode == 0) hipLaunchKernelGGL((seed_band_kernel<BC_NARROW, 4, 0, MINS>), dim3(a.grid), dim3(BLOCK), 0, stream, a);
+        else if (mode == 1) hipLaunchKernelGGL((seed_band_kernel<BC_NARROW, 4, 1, MINS>), dim3(a.grid), dim3(BLOCK), 0, stream, a);
+        else if (mode == 2) hipLaunchKernelGGL((seed_band_kernel<BC_NARROW, 3, 2, MINS>), dim3(a.grid), dim3(BLOCK), 0, stream, a);
+        else hipLaunchKernelGGL((seed_band_kernel<BC_NARROW, 3, 3, MINS>), dim3(a.grid), dim3(BLOCK), 0, stream, a);
     } else {
-        if (mode == 0) hipLaunchKernelGGL((seed_band_kernel<BC_WIDE, 2, 0>), dim3(a.grid), dim3(BLOCK), 0, stream, a);
-        else if (mode == 1) hipLaunchKernelGGL((seed_band_kernel<BC_WIDE, 1, 1>), dim3(a.grid), dim3(BLOCK), 0, stream, a);
-        else if (mode == 2) hipLaunchKernelGGL((seed_band_kernel<BC_WIDE, 1, 2>), dim3(a.grid), dim3(BLOCK), 0, stream, a);
-        else hipLaunchKernelGGL((seed_band_kernel<BC_WIDE, 1, 3>), dim3(a.grid), dim3(BLOCK), 0, stream, a);
+        if (mode == 0) hipLaunchKernelGGL((seed_band_kernel<BC_WIDE, 2, 0, MINS>), dim3(a.grid), dim3(BLOCK), 0, stream, a);
+        else if (mode == 1) hipLaunchKernelGGL((seed_band_kernel<BC_WIDE, 1, 1, MINS>), dim3(a.grid), dim3(BLOCK), 0, stream, a);
+        else if (mode == 2) hipLaunchKernelGGL((seed_band_kernel<BC_WIDE, 1, 2, MINS>), dim3(a.grid), dim3(BLOCK), 0, stream, a);
+        else hipLaunchKernelGGL((seed_band_kernel<BC_WIDE, 1, 3, MINS>), dim3(a.grid), dim3(BLOCK), 0, stream, a);
     }
     return hipGetLastError();
+}
+
+hipError_t launch_seed_band(const SeedBandArgs& a, int mode, bool narrow_strips, hipStream_t stream, bool diagonal) {
+    if (a.min_thr && a.min_count) return launch_seed_band_t<true>(a, mode, narrow_strips, stream, diagonal);
+    return launch_seed_band_t<false>(a, mode, narrow_strips, stream, diagonal);
 }
 
 }  // namespace zsw

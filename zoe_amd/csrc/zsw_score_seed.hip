@@ -39,6 +39,11 @@ struct SeedArgs {
     uint32_t* fail_list;
     uint32_t* fail_count;
     bool reversed;  // column c of a read is its base len - 1 - c
+    // ZSW_OPTION_MIN_SCORE (seed_kernel<.., true> only; behind the fields above, whose offsets the default instantiations keep):
+    // a read whose whole-read bound is below min_thr is settled here — written through `out`, counted at min_count
+    uint32_t min_thr;
+    ScoreOut out;
+    uint32_t* min_count;
 };
 
 // One thread per read. STAGED (contiguous fixed-length reads of at most SEED_STAGE_LEN bases): the block's reads arrive in LDS
@@ -46,7 +51,11 @@ struct SeedArgs {
 // this kernel's time.
 constexpr uint32_t SEED_STAGE_LEN = 160;
 
-template <bool STAGED>
+// MINS (ZSW_OPTION_MIN_SCORE > 0; an instantiation of its own, so that the default one is what it was): seed_read also returns
+// claim W's bound, the most any local alignment of the read against the whole reference can score (zsw_seed.hpp). A read —
+// anchored or not — whose bound is below a.min_thr is settled here as ZSW_STATUS_BELOW_MIN_SCORE: it gets fail_key, so that no
+// band tier walks it, and does not join fail_list. A read too short to be swept is bounded by the potential of its columns.
+template <bool STAGED, bool MINS>
 __global__ __launch_bounds__(256) void seed_kernel(SeedArgs a) {
     __shared__ uint16_t cell_lut[256];  // read byte -> seed_cell (potential, 2-bit code) of its residue | residue index << 12
     __shared__ __attribute__((aligned(16))) uint8_t sbytes[STAGED ? 256 * SEED_STAGE_LEN + 16 : 16];
@@ -93,7 +102,7 @@ __global__ __launch_bounds__(256) void seed_kernel(SeedArgs a) {
         // seed_read asks for every column exactly once, in order: the cell functor also packs the residue codes for the banded pass
         uint32_t* code_out = a.codes ? a.codes + (size_t)k * a.cs : nullptr;
         uint32_t acc = 0;
-        sr = seed_read(
+        sr = seed_read<MINS>(
             a.sp, (int)len,
             [&](int c) {
                 const uint32_t v = cell_lut[bases[rev ? (int)len - 1 - c : c]];
@@ -112,9 +121,30 @@ __global__ __launch_bounds__(256) void seed_kernel(SeedArgs a) {
                 *l1 = e.y;
             });
     }
-    const bool fail = valid && !sr.ok;
+    bool below = false;
+    if (MINS && valid && len > 0 && len < SEED_KEY_BIAS) {  // (an empty read is EMPTY, decided by its length alone: it goes where it went)
+        int bound = sr.u_whole;
+        if (len < SEED_MIN_LEN) {
+            const uint8_t* bases = STAGED ? sbytes + off : a.b.bases + off;
+            bound = 0;
+            for (uint32_t c = 0; c < len; ++c) bound += (int)(cell_lut[bases[c]] & 0xffu);
+        }
+        below = seed_below_min(bound, a.min_thr);
+        if (below) {
+            a.out.score[id] = 0;
+            a.out.status[id] = ZSW_STATUS_BELOW_MIN_SCORE;
+            if (a.out.tier) a.out.tier[id] = 0;
+            if (a.out.ref_end) a.out.ref_end[id] = 0;
+            if (a.out.query_end) a.out.query_end[id] = 0;
+        }
+    }
+    if (MINS) {  // one atomic per wavefront
+        const unsigned long long mb = __ballot(below);
+        if (mb && (threadIdx.x & 63) == 0) atomicAdd(a.min_count, (uint32_t)__popcll(mb));
+    }
+    const bool fail = valid && !sr.ok && !below;
     if (valid) {
-        a.keys[k] = sr.ok ? (uint32_t)(sr.dt + (int)a.key_bias) : a.fail_key;
+        a.keys[k] = (sr.ok && !below) ? (uint32_t)(sr.dt + (int)a.key_bias) : a.fail_key;
         a.ids[k] = k;
         a.info[k] = (uint32_t)sr.t_all | ((uint32_t)sr.d_fa << 16) | ((uint32_t)sr.d_bl << 24);
         a.masks[k] = sr.bl_mask;
@@ -194,8 +224,9 @@ bool seed_applicable(const SeedIndex& ix, uint32_t max_len, uint32_t ref_len, ui
 hipError_t launch_score_seeded(const ScoreArgsV2& a2, int G, int C, uint32_t max_len, const SeedIndex& ix, uint8_t* work, size_t work_bytes,
                                uint2* gtab, uint32_t* fail_list, uint32_t* fail_count, int mode, const ScoreArgsV2* band_tabs, const uint2* gtab_band, int32_t* band_dbg,
                                uint32_t narrow_min_reads, uint32_t band_grid_cap, hipStream_t stream, KernelTimer* window_timer, bool narrow_only, bool reads_reversed,
-                               std::vector<uint32_t>* launches, bool strip_first_tier, bool diag_lane_events) {
+                               std::vector<uint32_t>* launches, bool strip_first_tier, bool diag_lane_events, uint32_t min_thr, uint32_t* min_counts) {
     const uint32_t n = a2.b.n_items;
+    if (!min_counts) min_thr = 0;
     if (n == 0) return hipSuccess;
     if (!work || !gtab || work_bytes < seed_workspace_bytes(n, max_len, band_grid_cap)) return hipErrorNotSupported;
     // the banded kernel (zsw_score_band.hip) when a strip's rows fit one drift period of the doubled scoring
@@ -243,10 +274,17 @@ hipError_t launch_score_seeded(const ScoreArgsV2& a2, int G, int C, uint32_t max
     s.fail_list = fail_list;
     s.fail_count = fail_count;
     s.reversed = reads_reversed;
-    if (!s.b.offsets && !s.b.items && s.b.fixed_len <= SEED_STAGE_LEN)
-        hipLaunchKernelGGL(seed_kernel<true>, dim3((n + 255) / 256), dim3(256), 0, stream, s);
+    s.min_thr = min_thr;
+    s.out = a2.out;
+    s.min_count = min_counts;  // [0]: settled by the whole-read bound
+    const bool staged = !s.b.offsets && !s.b.items && s.b.fixed_len <= SEED_STAGE_LEN;
+    if (min_thr) {
+        if (staged) hipLaunchKernelGGL((seed_kernel<true, true>), dim3((n + 255) / 256), dim3(256), 0, stream, s);
+        else hipLaunchKernelGGL((seed_kernel<false, true>), dim3((n + 255) / 256), dim3(256), 0, stream, s);
+    } else if (staged)
+        hipLaunchKernelGGL((seed_kernel<true, false>), dim3((n + 255) / 256), dim3(256), 0, stream, s);
     else
-        hipLaunchKernelGGL(seed_kernel<false>, dim3((n + 255) / 256), dim3(256), 0, stream, s);
+        hipLaunchKernelGGL((seed_kernel<false, false>), dim3((n + 255) / 256), dim3(256), 0, stream, s);
     hipError_t e = hipcub::DeviceRadixSort::SortPairs(temp, temp_bytes, (const uint32_t*)keys, keys_out, (const uint32_t*)ids, order, (int)n, 0,
                                                       key_bits, stream);
     if (e != hipSuccess) return e;
@@ -284,6 +322,8 @@ hipError_t launch_score_seeded(const ScoreArgsV2& a2, int G, int C, uint32_t max
         b.wd_per32 = 2 * ix.params.Wd_per16;
         b.n_dev = nullptr;
         b.retry = nullptr;
+        b.min_thr = min_thr;
+        b.min_count = min_counts ? min_counts + 1 : nullptr;  // [1]: settled by a band bound
         // work-queue counters of the (up to) two launches: the spare words behind `order` and `keys`
         uint32_t* queue1 = reinterpret_cast<uint32_t*>(work + 3 * per + (size_t)n * 4) + 1;
         uint32_t* queue2 = reinterpret_cast<uint32_t*>(work + (size_t)n * 4);

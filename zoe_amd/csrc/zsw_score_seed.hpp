@@ -107,6 +107,10 @@ struct SeedBandArgs {
     uint32_t key_bias, fail_key;
     uint32_t* fail_list;
     uint32_t* fail_count;
+    // ZSW_OPTION_MIN_SCORE (the MINS instantiations only; behind the fields above, whose offsets the default instantiations keep): a
+    // read the walk does not accept and whose seed_band_upper is below min_thr is settled as BELOW_MIN_SCORE, counted at min_count
+    uint32_t min_thr = 0;
+    uint32_t* min_count = nullptr;
 };
 uint32_t seed_band_rows(const SeedParams& p, uint32_t max_len);
 uint32_t seed_band_grid(uint32_t n, uint32_t grid_cap);
@@ -142,7 +146,8 @@ hipError_t launch_score_seeded(const ScoreArgsV2& a2, int G, int C, uint32_t max
                                uint2* gtab, uint32_t* fail_list, uint32_t* fail_count, int mode, const ScoreArgsV2* band_tabs, const uint2* gtab_band, int32_t* band_dbg,
                                uint32_t narrow_min_reads, uint32_t band_grid_cap, hipStream_t stream, KernelTimer* window_timer, bool narrow_only = false, bool reads_reversed = false,
                                std::vector<uint32_t>* launches = nullptr /* zsw_debug_score_launches */, bool strip_first_tier = false /* ZSW_DEBUG_SEED_STRIP_FIRST_TIER */,
-                               bool diag_lane_events = false /* ZSW_DEBUG_SEED_DIAG_LANE_EVENTS */);
+                               bool diag_lane_events = false /* ZSW_DEBUG_SEED_DIAG_LANE_EVENTS */,
+                               uint32_t min_thr = 0 /* ZSW_OPTION_MIN_SCORE: min_threshold(), 0 = off */, uint32_t* min_counts = nullptr /* [0] seed, [1] band */);
 // (Re)builds the index for a reference given as residue indices on the host.
 hipError_t seed_index_update(SeedIndex* ix, const ScoringDev& sc, const uint8_t* h_ref, size_t ref_len);
 void seed_index_release(SeedIndex* ix);

@@ -193,13 +193,19 @@ struct SeedRead {
     // diagonal > dt + Dm
     int d_fb;          // t_all - (bound of the paths that stay right of diagonal dt + Dm), capped at 255
     uint32_t fa_mask, fb_mask;
+    // seed_read<true>: claim W's bound (below, "whole-reference bound") — no local alignment of the read against the reference
+    // scores more, whether an anchor was found or not. seed_read<false>: t_all, which bounds it too.
+    int u_whole;
 };
 
 // cell(c): what the seed kernel needs of query column c: potential Wp in bits 0-7, 2-bit code in bits 8-15 (0xff: the residue is
 // not a good one). look(code, &first1, &last1): the index entry of a k-mer.
 ZSW_SEED_HD uint32_t seed_cell(const SeedParams& p, int residue) { return (uint32_t)p.wp[residue & 31] | ((uint32_t)p.code[residue & 31] << 8); }
 
-template <class GetCell, class Lookup>
+// WHOLE: also derive claim W's bound (SeedRead::u_whole) from the entries the sweep has looked up already — set[j] = k-mer j is
+// usable and occurs nowhere in the index, as in seed_whole_finish; no second sweep, no second look-up. The default leaves the
+// instantiations that do not ask for it as they were.
+template <bool WHOLE = false, class GetCell, class Lookup>
 ZSW_SEED_HD SeedRead seed_read(const SeedParams& p, int len, GetCell cell, Lookup look) {
     SeedRead out;
     out.ok = 0;
@@ -268,7 +274,14 @@ ZSW_SEED_HD SeedRead seed_read(const SeedParams& p, int len, GetCell cell, Looku
         }
     }
     out.t_all = pot;
+    out.u_whole = pot;
     if (m == 0) return out;
+    if (WHOLE) {
+        bool nowhere[SEED_MAX_KMERS];
+#pragma unroll
+        for (int j = 0; j < SEED_MAX_KMERS; ++j) nowhere[j] = j < m && usable[j] && !has[j];
+        out.u_whole = seed_span_bound(m, pot_lo, pot_hi, pot, nowhere, lam);
+    }
     int dt = 0;
     const int support = seed_vote(m, has, dlo, dhi, p.tol, &dt);
     if (support < (m >= 3 ? 2 : 1)) return out;
@@ -517,6 +530,23 @@ ZSW_SEED_HD bool seed_exit_is_free(int x, int m, int c0, int stride, int K, int 
 ZSW_SEED_HD uint32_t seed_tag(int v, int tag) { return v > 0 ? (uint32_t)(2 * v + tag) : 0u; }
 // the plain bound a doubled value stands for
 ZSW_SEED_HD int seed_untag(uint32_t v2, int tag) { return (int)((v2 + (tag < 0 ? 1u : 0u)) >> 1); }
+
+// ---- a caller's minimum score (ZSW_OPTION_MIN_SCORE) ------------------------------------------------------------------------
+// The most ANY cell of a read's matrix can hold, given what one band walk left: b2 = the band's maximum (doubled, tagged), oa / ob =
+// the most a path that ends above / below the band can score. Every band cell holds at least its true H (U(cell) >= H(cell)
+// above) and every outside cell at most oa / ob, so max(bound of b2, oa, ob) is an upper bound of the read's score whether the
+// walk was accepted or not. An odd b2 is 2 * bound - 1 (score only) or 2 * bound + 1 (ends): the ceiling of b2 / 2 is the bound
+// itself for the former and one more for the latter — at least the bound under either convention. Host model:
+// tests/models/min_score.cpp, every walk of tests/models/seed_band.cpp against the full Gotoh matrix.
+ZSW_SEED_HD int seed_band_upper(uint32_t b2, int oa, int ob) {
+    const int in = (int)((b2 + 1u) >> 1);
+    const int out = oa > ob ? oa : ob;
+    return in > out ? in : out;
+}
+// The decision: a read whose score is at most `bound` is below the minimum t (the caller passes min(T, thr): the option's value
+// capped by the overflow threshold of the call's last width, so that a read at or beyond the threshold stays OVERFLOWED). Strict:
+// a read that may score exactly t is not below it.
+ZSW_SEED_HD bool seed_below_min(long long bound, long long t) { return bound < t; }
 
 // Certificate for the late start of the alignment's second pass (sw_simd_align's flags, striped.rs:449-598, recomputed for the
 // rows the traceback can visit). Every quantity of the striped recurrence at a cell (H, the E entering it, the F of a lazy-F

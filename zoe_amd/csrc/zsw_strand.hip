@@ -477,6 +477,7 @@ zsw_error zsw_set_complement(zsw_context* ctx, const uint8_t* table) {
 zsw_error zsw_score_strands_batch_from(zsw_context* ctx, const zsw_batch* reads, int from_width, int preset_bits, uint32_t* out_score,
                                        uint8_t* out_status, uint8_t* out_tier, uint8_t* out_strand, void* stream) {
     DeviceGuard device_guard(ctx);
+    if (zsw_error ze = min_score_unsupported(ctx, "zsw_score_strands_batch_from"); ze != ZSW_OK) return ze;
     if (zsw_error ze = check_strand_batch(ctx, reads, true); ze != ZSW_OK) return ze;
     if (!out_score || !out_status || !out_strand) return fail(ctx, ZSW_ERR_INVALID_ARGUMENT, "null argument");
     ResultRule rule;
@@ -512,6 +513,7 @@ zsw_error zsw_align_3pass_strands_batch_from(zsw_context* ctx, const zsw_batch* 
                                              uint8_t* out_op, uint64_t ciglet_cap, uint64_t* out_n_ciglets, void* stream_) {
     DeviceGuard device_guard(ctx);
     hipStream_t stream = (hipStream_t)stream_;
+    if (zsw_error ze = min_score_unsupported(ctx, "zsw_align_3pass_strands_batch_from"); ze != ZSW_OK) return ze;
     if (zsw_error ze = check_strand_batch(ctx, reads, true); ze != ZSW_OK) return ze;
     if (!out_aln || !out_status || !out_strand || !out_n_ciglets || (ciglet_cap && (!out_inc || !out_op))) return fail(ctx, ZSW_ERR_INVALID_ARGUMENT, "null argument");
     ResultRule rule;
