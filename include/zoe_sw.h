@@ -461,7 +461,11 @@ typedef enum zsw_debug_flag {
     /* score: in the diagonal first tier every lane derives the k-mer column patterns of its own two reads. By default a batch of
      * reads of one length derives them once per wavefront and group of columns, on scalar registers (a ragged batch always takes
      * the per-lane form) */
-    ZSW_DEBUG_SEED_DIAG_LANE_EVENTS = 131072
+    ZSW_DEBUG_SEED_DIAG_LANE_EVENTS = 131072,
+    /* score: the full pass over the reads the seed kernel hands back runs as launches of its own behind the band tiers. By default a
+     * score-only call of two band tiers with reads of up to 152 bases (and no ZSW_OPTION_MIN_SCORE) scores them in the first tier's
+     * launch: the hand-back blocks and the tier's persistent blocks share one grid (zsw_score_band.hip: seed_diag_handback_kernel) */
+    ZSW_DEBUG_SEED_NO_COSCHEDULE = 262144
 } zsw_debug_flag;
 zsw_error zsw_debug_set(zsw_context* ctx, uint32_t flags);
 

@@ -79,4 +79,49 @@ inline int handback_plan(const StripCfg* cfgs, int n_cfgs, uint32_t longest, int
     return n;
 }
 
+// ---- the full pass co-scheduled with the first band tier (zsw_score_band.hip: seed_diag_handback_kernel) ----------------------------
+// Nearly all of the hand-back list exists before the band tiers start: the seed kernel lists the reads without an anchor itself. In a
+// two-tier call the first tier appends nothing (what it cannot prove is flagged for the second tier, and it never bails), so the list
+// and its count are frozen while the first tier runs — and the full pass over that part of the list can share the first tier's grid:
+// the first handback_blocks() blocks of the launch score list[0, count), the blocks behind them are the tier's persistent blocks.
+// The gated launches of handback_plan then score list[count at that time, final count) only (ScoreArgsV2::first_item_dev).
+// Host model: tests/models/coschedule_plan.cpp.
+struct CoscheduleCase {
+    int mode;               // 0 score only, 1 / 2 with ends
+    bool two_tiers;         // a narrow first tier with `retry` flags and no bail-out, then the full band
+    bool diagonal;          // ... walked diagonal by diagonal (seed_diag_kernel: it uses no blockIdx)
+    int G;                  // lanes per read pair of the class's strip configuration
+    bool mins;              // ZSW_OPTION_MIN_SCORE: the MINS instantiations
+    bool row_chunks;        // the hand-backs are cut into chunks of rows (their results are folded by a kernel over the whole list)
+    bool skip_handed_back;  // the caller settles the handed-back reads by other means
+    bool disabled;          // ZSW_DEBUG_SEED_NO_COSCHEDULE
+};
+constexpr bool handback_coschedule(const CoscheduleCase& c) {
+    return c.mode == 0 && c.two_tiers && c.diagonal && c.G == 4 && !c.mins && !c.row_chunks && !c.skip_handed_back && !c.disabled;
+}
+
+constexpr uint32_t HANDBACK_BLOCK_THREADS = 256;  // (= BLOCK of zsw_score_v2.hpp)
+// pairs of reads per block of score_kernel_v2 in a configuration of G lanes per pair
+constexpr uint32_t handback_block_pairs(int G) { return HANDBACK_BLOCK_THREADS / (uint32_t)G; }
+// blocks of a grid sized for n_items reads (the count on the device is at most that)
+constexpr uint32_t handback_blocks(uint32_t n_items, int G) { return (n_items + 2 * handback_block_pairs(G) - 1) / (2 * handback_block_pairs(G)); }
+// A block of the co-scheduled grid: hand-back block `index` (its pairs below), or persistent block `index` of the band tier. The
+// hand-back blocks take the low indices: blocks are dispatched in index order, so the long items start first (for speed only).
+struct CoscheduleRole {
+    bool handback;
+    uint32_t index;
+};
+constexpr CoscheduleRole coschedule_role(uint32_t block, uint32_t hb_blocks) {
+    return block < hb_blocks ? CoscheduleRole{true, block} : CoscheduleRole{false, block - hb_blocks};
+}
+// The pairs [first, end) of a list of `count` reads that hand-back block `block` scores (pair p = reads 2p and 2p + 1, the last pair of
+// an odd count has no partner); first == end: the block returns at once.
+struct PairRange {
+    uint32_t first, end;
+};
+constexpr PairRange handback_block_range(uint32_t block, int G, uint32_t count) {
+    const uint64_t pairs = ((uint64_t)count + 1) / 2, lo = (uint64_t)block * handback_block_pairs(G), hi = lo + handback_block_pairs(G);
+    return lo >= pairs ? PairRange{0u, 0u} : PairRange{(uint32_t)lo, (uint32_t)(hi < pairs ? hi : pairs)};
+}
+
 }  // namespace zsw

@@ -620,27 +620,43 @@ static hipError_t launch_score_passes(const ScoringDev* d_sc, const ScoringDev& 
         pe = hipMemsetAsync(counter, 0, 4, stream);
         if (pe != hipSuccess) return pe;
         ap.b = bb;
+        // Against a long reference the few reads handed back are cut into chunks of rows, each an item of its own (a class of
+        // 2,000 reads walking 30,000 rows each is a dozen blocks on 256 CUs): chunks of at least four times the rows a
+        // positive path can span, so that the overlap costs a quarter more cells at most.
+        int maxw = 0;
+        for (int i = 0; i < h_sc.S * h_sc.S; ++i) maxw = std::max(maxw, (int)h_sc.w[i]);
+        const uint64_t overlap = h_sc.gap_extend > 0 ? (uint64_t)longest + (uint64_t)longest * (uint64_t)maxw / (uint64_t)h_sc.gap_extend + 2 : ~0ull;
+        const uint64_t rows = std::max<uint64_t>(4 * overlap, 2048);
+        const bool row_chunks = ws.chunk_keys && !(ws.debug & ZSW_DEBUG_NO_ROW_CHUNKS) && h_sc.gap_extend > 0 && rows * 2 <= ref_len && longest < (1u << CHUNK_COL_BITS) &&
+                                ref_len < (1u << CHUNK_ROW_BITS) - 2;
+        const uint32_t min_thr = (ws.min_score && ws.min_counts && !out.skip_handed_back) ? min_threshold(rule, ws.min_score) : 0u;
+        // The full pass over the reads the seed kernel hands back may run inside the first band tier's launch (zsw_handback.hpp:
+        // handback_coschedule); n0, one word per counter (the length classes of a ragged batch have their own), then holds how
+        // many reads of the list that launch scored, and the launches below score the rest.
+        CoscheduleCase co{};
+        co.mode = mode;
+        co.G = g;
+        co.mins = min_thr != 0;
+        co.row_chunks = row_chunks;
+        co.skip_handed_back = out.skip_handed_back;
+        co.disabled = (ws.debug & ZSW_DEBUG_SEED_NO_COSCHEDULE) != 0;
+        uint32_t* const n0 = counter + 32;  // (ws.prune_fail_count: 64 words, the counters in the first 2 + NCLS)
+        static_assert(2 + NCLS <= 32, "the n0 words sit 32 behind their counters");
+        bool coscheduled = false;
         pe = launch_score_seeded(ap, g, c, longest, *ws.seed, ws.seed_work + work_off, seed_workspace_bytes(bb.n_items, longest, band_grid_cap), ws.seed_gtab,
                                  ws.prune_fail_list + list_off, counter, mode, band_ok ? &ab : nullptr, gtab_band, ws.band_dbg,
                                  (ws.debug & ZSW_DEBUG_SEED_WIDE_BAND) ? 0xffffffffu : (ws.debug & ZSW_DEBUG_SCORE_PRUNE_ANY_SIZE) ? 0u : SEED_NARROW_MIN_READS, band_grid_cap, stream,
                                  ws.window_timer, out.narrow_only, out.reads_reversed && out.skip_handed_back, launches,
                                  (ws.debug & ZSW_DEBUG_SEED_STRIP_FIRST_TIER) != 0, (ws.debug & ZSW_DEBUG_SEED_DIAG_LANE_EVENTS) != 0,
-                                 (ws.min_score && ws.min_counts && !out.skip_handed_back) ? min_threshold(rule, ws.min_score) : 0u, ws.min_counts);
+                                 min_thr, ws.min_counts, &co, n0, &coscheduled);
         if (pe != hipSuccess) return pe;
         ap.b.items = ws.prune_fail_list + list_off;
         ap.n_items_dev = counter;
+        ap.first_item_dev = coscheduled ? n0 : nullptr;  // (not co-scheduled: n0 is not written, and nothing changes)
         // out.skip_handed_back (the shared-profile role's passes, the seeded reverse pass of the ranges): the caller recomputes every
         // read without the `unique` flag by other means, the handed-back reads among them — scoring them here would be thrown away
         if (!out.skip_handed_back) {
-            // Against a long reference the few reads handed back are cut into chunks of rows, each an item of its own (a class of
-            // 2,000 reads walking 30,000 rows each is a dozen blocks on 256 CUs): chunks of at least four times the rows a
-            // positive path can span, so that the overlap costs a quarter more cells at most.
-            int maxw = 0;
-            for (int i = 0; i < h_sc.S * h_sc.S; ++i) maxw = std::max(maxw, (int)h_sc.w[i]);
-            const uint64_t overlap = h_sc.gap_extend > 0 ? (uint64_t)longest + (uint64_t)longest * (uint64_t)maxw / (uint64_t)h_sc.gap_extend + 2 : ~0ull;
-            const uint64_t rows = std::max<uint64_t>(4 * overlap, 2048);
-            if (ws.chunk_keys && !(ws.debug & ZSW_DEBUG_NO_ROW_CHUNKS) && h_sc.gap_extend > 0 && rows * 2 <= ref_len && longest < (1u << CHUNK_COL_BITS) &&
-                ref_len < (1u << CHUNK_ROW_BITS) - 2) {
+            if (row_chunks) {  // (never co-scheduled: chunk_finalize_kernel writes the result of every read of the list)
                 ap.chunk_rows = (uint32_t)rows;
                 ap.chunk_overlap = (uint32_t)overlap;
                 ap.chunk_keys = ws.chunk_keys;
@@ -673,6 +689,7 @@ static hipError_t launch_score_passes(const ScoringDev* d_sc, const ScoringDev& 
                         ah = tabs[t++];
                         ah.b = ap.b;
                         ah.n_items_dev = counter;
+                        ah.first_item_dev = ap.first_item_dev;  // (the gates choose by the remainder)
                     }
                     ah.b.n_items = plan[k].grid_items;
                     ah.gate_lo = plan[k].lo;

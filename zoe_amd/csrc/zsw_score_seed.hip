@@ -224,8 +224,10 @@ bool seed_applicable(const SeedIndex& ix, uint32_t max_len, uint32_t ref_len, ui
 hipError_t launch_score_seeded(const ScoreArgsV2& a2, int G, int C, uint32_t max_len, const SeedIndex& ix, uint8_t* work, size_t work_bytes,
                                uint2* gtab, uint32_t* fail_list, uint32_t* fail_count, int mode, const ScoreArgsV2* band_tabs, const uint2* gtab_band, int32_t* band_dbg,
                                uint32_t narrow_min_reads, uint32_t band_grid_cap, hipStream_t stream, KernelTimer* window_timer, bool narrow_only, bool reads_reversed,
-                               std::vector<uint32_t>* launches, bool strip_first_tier, bool diag_lane_events, uint32_t min_thr, uint32_t* min_counts) {
+                               std::vector<uint32_t>* launches, bool strip_first_tier, bool diag_lane_events, uint32_t min_thr, uint32_t* min_counts,
+                               const CoscheduleCase* co, uint32_t* n0, bool* coscheduled) {
     const uint32_t n = a2.b.n_items;
+    if (coscheduled) *coscheduled = false;
     if (!min_counts) min_thr = 0;
     if (n == 0) return hipSuccess;
     if (!work || !gtab || work_bytes < seed_workspace_bytes(n, max_len, band_grid_cap)) return hipErrorNotSupported;
@@ -354,7 +356,26 @@ hipError_t launch_score_seeded(const ScoreArgsV2& a2, int G, int C, uint32_t max
             note_launch(launches, ZSW_LAUNCH_SEED_BAND, G, C, mode);
             // score only, as the first of two tiers: the band diagonal by diagonal (seed_diag_kernel) instead of 16-column strips
             const bool diagonal = mode == 0 && !narrow_only && !strip_first_tier && seed_diag_applicable(max_len, band_tabs->K);
-            e = launch_seed_band(b1, mode, true, stream, diagonal);
+            CoscheduleCase cc{};
+            if (co) cc = *co;
+            cc.two_tiers = !narrow_only;
+            cc.diagonal = diagonal;
+            if (co && n0 && coscheduled && handback_coschedule(cc) && cc.mode == mode && cc.G == G && cc.mins == (min_thr != 0)) {
+                // The full pass over the reads the seed kernel listed, in the first tier's grid. Invariant: b1.retry != nullptr and
+                // no bail-out (b1.bail_check is false), so the tier appends nothing to fail_list: the list and *fail_count are
+                // frozen for the whole launch, and *n0 — copied here, on the stream, behind the seed kernel — is the count every
+                // block of the launch reads. What the second tier appends behind it is the caller's (first_item_dev = n0).
+                e = hipMemcpyAsync(n0, fail_count, 4, hipMemcpyDeviceToDevice, stream);
+                if (e != hipSuccess) return e;
+                ScoreArgsV2 hb = a2;
+                hb.b.items = fail_list;
+                hb.n_items_dev = fail_count;
+                note_launch(launches, ZSW_LAUNCH_V2, G, C, 0);
+                e = launch_seed_diag_handback(b1, hb, G, C, stream);
+                *coscheduled = true;
+            } else {
+                e = launch_seed_band(b1, mode, true, stream, diagonal);
+            }
             if (e != hipSuccess) return e;
             if (narrow_only) {
                 if (window_timer) window_timer->end(stream);

@@ -1,6 +1,7 @@
 // zsw_score_seed.hpp — the seeded exact score pass: declarations shared by zsw_score_seed.hip (seed kernel, reference index,
 // launcher), zsw_score_seed_m{0,1,2}.hip (the window kernel per MODE) and zsw_score.hip / zsw_capi.hip (callers).
 #pragma once
+#include "zsw_handback.hpp"
 #include "zsw_internal.hpp"
 #include "zsw_seed.hpp"
 
@@ -123,6 +124,9 @@ hipError_t launch_seed_band(const SeedBandArgs& a, int mode, bool narrow_strips,
 bool seed_diag_applicable(uint32_t max_len, uint32_t rebase_rows);
 
 struct ScoreArgsV2;
+// The diagonal first tier and, in the same grid, the full pass (strip configuration G x C of hb's tables, G = 4, mode 0) over the
+// hand-back list as the seed kernel left it: hb.b.items / hb.n_items_dev (zsw_handback.hpp: handback_coschedule).
+hipError_t launch_seed_diag_handback(const SeedBandArgs& a, const ScoreArgsV2& hb, int G, int C, hipStream_t stream);
 
 // bytes of workspace for a range of n items
 // band_grid_cap: most blocks the banded kernel may launch for this range (each owns a boundary buffer). A ragged batch shares
@@ -147,7 +151,12 @@ hipError_t launch_score_seeded(const ScoreArgsV2& a2, int G, int C, uint32_t max
                                uint32_t narrow_min_reads, uint32_t band_grid_cap, hipStream_t stream, KernelTimer* window_timer, bool narrow_only = false, bool reads_reversed = false,
                                std::vector<uint32_t>* launches = nullptr /* zsw_debug_score_launches */, bool strip_first_tier = false /* ZSW_DEBUG_SEED_STRIP_FIRST_TIER */,
                                bool diag_lane_events = false /* ZSW_DEBUG_SEED_DIAG_LANE_EVENTS */,
-                               uint32_t min_thr = 0 /* ZSW_OPTION_MIN_SCORE: min_threshold(), 0 = off */, uint32_t* min_counts = nullptr /* [0] seed, [1] band */);
+                               uint32_t min_thr = 0 /* ZSW_OPTION_MIN_SCORE: min_threshold(), 0 = off */, uint32_t* min_counts = nullptr /* [0] seed, [1] band */,
+                               // co (with n0): the caller's side of handback_coschedule (two_tiers and diagonal are filled in here). If the
+                               // decision holds, *fail_count as the seed kernel left it is copied to the device word n0 and the first tier's
+                               // launch scores fail_list[0, *n0) itself, with a2's tables: the caller's launches start at *n0
+                               // (ScoreArgsV2::first_item_dev). *coscheduled says whether that happened; if not, n0 is not written.
+                               const CoscheduleCase* co = nullptr, uint32_t* n0 = nullptr, bool* coscheduled = nullptr);
 // (Re)builds the index for a reference given as residue indices on the host.
 hipError_t seed_index_update(SeedIndex* ix, const ScoringDev& sc, const uint8_t* h_ref, size_t ref_len);
 void seed_index_release(SeedIndex* ix);

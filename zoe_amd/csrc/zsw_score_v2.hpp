@@ -92,6 +92,11 @@ struct ScoreArgsV2 {
     // ... and the launch does nothing unless that number lies in [gate_lo, gate_hi): the same worklist is launched in several strip
     // configurations (many lanes per read for a short list, few for a long one), and the count picks the one that runs
     uint32_t gate_lo = 0, gate_hi = 0xffffffffu;
+    // non-null (with n_items_dev): the launch scores the items [*first_item_dev, count) of the list only, its gate is tested against
+    // count - *first_item_dev, and blocks past that many items return at once. The seeded pass's first band tier scores the part of
+    // the hand-back list the seed kernel wrote in its own launch (zsw_score_band.hip: seed_diag_handback_kernel); the launches behind
+    // the band tiers then score what those appended. null = 0.
+    const uint32_t* first_item_dev = nullptr;
     // Row-chunked launch (reads handed back by the seeded pass against a long reference: a few thousand reads walking 30,000 rows
     // each fill a fraction of the chip): chunk_rows > 0 = blockIdx.y is a chunk of reference rows, rows [y * chunk_rows -
     // chunk_overlap, (y + 1) * chunk_rows) from a zero state; a path that spans more than chunk_overlap rows cannot be positive
@@ -108,8 +113,11 @@ __host__ __device__ inline unsigned long long chunk_key(uint32_t score, uint32_t
            (unsigned long long)(((1u << CHUNK_COL_BITS) - 1u) - col1);
 }
 
+// The kernel's body. `block`: the block's index within its own part of the grid — blockIdx.x for score_kernel_v2; the co-scheduled
+// launch of zsw_score_band.hip (seed_diag_handback_kernel) runs this body in the first blocks of a grid it shares with the first
+// band tier. Every __syncthreads below is reached by all threads of a block or by none (the early return is block-uniform).
 template <int G, int C, int MODE, bool WIDE = false, bool TILED = false>
-__global__ __launch_bounds__(BLOCK, min_waves(C, MODE)) void score_kernel_v2(ScoreArgsV2 a) {
+__device__ __forceinline__ void score_body_v2(const ScoreArgsV2& a, const uint32_t block) {
     __shared__ uint2 rp[WIDE ? 1 : CH + G];
     __shared__ uint16_t rpw[WIDE ? CH + G : 1];      // WIDE: byte offset of each staged row's table row
     __shared__ uint32_t wt32[WIDE ? 33 * 9 : 1];     // WIDE: the score table
@@ -119,13 +127,17 @@ __global__ __launch_bounds__(BLOCK, min_waves(C, MODE)) void score_kernel_v2(Sco
 
     const int tid = threadIdx.x;
     const int g = tid & (G - 1);
-    const uint32_t group = blockIdx.x * (BLOCK / G) + tid / G;
+    const uint32_t group = block * (BLOCK / G) + tid / G;
     const uint32_t itemA = 2 * group, itemB = 2 * group + 1;
-    const uint32_t n_items = a.n_items_dev ? min(*a.n_items_dev, a.b.n_items) : a.b.n_items;
-    if (2 * blockIdx.x * (BLOCK / G) >= n_items || n_items < a.gate_lo || n_items >= a.gate_hi) return;
+    // the launch's items: [first, n_list) of the list, counted from `first` (first_item_dev: what a co-scheduled launch scored already)
+    // (b.n_items sizes the grid: it caps the launch's items, not the list — a gated launch's grid is sized for its gate's upper end)
+    const uint32_t n_list = a.n_items_dev ? *a.n_items_dev : a.b.n_items;
+    const uint32_t first = (!TILED && a.first_item_dev) ? min(*a.first_item_dev, n_list) : 0u;  // (the tiles' boundary rows are per pair of the whole list)
+    const uint32_t n_items = min(n_list - first, a.b.n_items);
+    if (2 * block * (BLOCK / G) >= n_items || n_items < a.gate_lo || n_items >= a.gate_hi) return;
     const bool validA = itemA < n_items, validB = itemB < n_items;
-    const uint32_t idA = validA ? (a.b.items ? a.b.items[itemA] : itemA) : 0;
-    const uint32_t idB = validB ? (a.b.items ? a.b.items[itemB] : itemB) : 0;
+    const uint32_t idA = validA ? (a.b.items ? a.b.items[first + itemA] : first + itemA) : 0;
+    const uint32_t idB = validB ? (a.b.items ? a.b.items[first + itemB] : first + itemB) : 0;
 
     if (tid < 64) lut32[tid] = reinterpret_cast<const uint32_t*>(a.sc->index_map)[tid];
     if (tid < 9) swt[tid] = make_uint2(a.wtab[tid][0], a.wtab[tid][1]);
@@ -407,6 +419,11 @@ __global__ __launch_bounds__(BLOCK, min_waves(C, MODE)) void score_kernel_v2(Sco
             if (MODE == 2 && a.out.query_end) a.out.query_end[o_id] = some ? o_qe : 0;
         }
     }
+}
+
+template <int G, int C, int MODE, bool WIDE = false, bool TILED = false>
+__global__ __launch_bounds__(BLOCK, min_waves(C, MODE)) void score_kernel_v2(ScoreArgsV2 a) {
+    score_body_v2<G, C, MODE, WIDE, TILED>(a, blockIdx.x);
 }
 
 // zsw_score_wide.hip
