@@ -82,6 +82,8 @@ pub const ZSW_STATUS_BELOW_MIN_SCORE: u8 = 4;
 /// `zsw_option`
 pub const ZSW_OPTION_EXACT_PRUNING: i32 = 1;
 pub const ZSW_OPTION_MIN_SCORE: i32 = 2;
+/// `zsw_launch_kind` of a `debug_score_launches` record that describes the row-chunked launch recorded after it
+pub const ZSW_LAUNCH_ROW_CHUNKS: u32 = 15;
 
 /// `zsw_int_type`: T of `StripedProfile<T, N, S>` (`math/integer.rs:231-238`)
 #[repr(i32)]
@@ -788,7 +790,8 @@ impl GpuContext {
 
     /// `zsw_debug_score_launches`: tests only — the score kernels the last call launched, one `[kind, G, C, mode]` per launch in
     /// launch order (`kind`: `zsw_launch_kind` of the header; `(G, C)`: the strip configuration; `mode`: the MODE the kernel was
-    /// built with). Host bookkeeping: no device work, no synchronisation.
+    /// built with). A record of kind [`ZSW_LAUNCH_ROW_CHUNKS`] is `[kind, rows per chunk, rows of overlap, chunks]` of the
+    /// row-chunked launch whose own record follows it. Host bookkeeping: no device work, no synchronisation.
     pub fn debug_score_launches(&self) -> Result<Vec<[u32; 4]>, GpuError> {
         let mut n = 0u32;
         // SAFETY: live context; capacity 0 writes nothing but the count

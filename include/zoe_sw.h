@@ -507,7 +507,9 @@ zsw_error zsw_debug_strand_records(zsw_context* ctx, int32_t* records);
  * mode 3 of the seeded passes' hand-backs, shows the one that ran; ZSW_LAUNCH_SEED_BAND alone can show 3, seed_band_kernel has
  * that instantiation: ends + "the maximum sits in one cell"). For the two seeded kinds (G, C) is the configuration of the length
  * class the pass ran for. Launches that decide on the device whether they do anything (ScoreArgsV2::gate_lo / gate_hi) are
- * recorded as issued; so is every tile of the tiled kernels. A launcher that finds no item on the host launches and records nothing. A strand-aware call reports the
+ * recorded as issued; so is every tile of the tiled kernels. ZSW_LAUNCH_ROW_CHUNKS alone reads its fields otherwise: (kind, rows a
+ * chunk owns, rows of overlap in front of them, number of chunks = grid rows) of the row-chunked score_kernel_v2 launch
+ * (ScoreArgsV2::chunk_rows) whose ZSW_LAUNCH_V2 record comes next; a launch of whole rows has no such record. A launcher that finds no item on the host launches and records nothing. A strand-aware call reports the
  * launches of the last batch it staged. records: host memory for 4 * capacity uint32, may be NULL when capacity is 0; *out_n is
  * the number of launches. When capacity < *out_n nothing is written (ZSW_OK all the same): call again with that capacity. */
 typedef enum zsw_launch_kind {
@@ -525,7 +527,8 @@ typedef enum zsw_launch_kind {
     ZSW_LAUNCH_EXACT32_WORKLIST = 11, /* exact32_kernel over the device-side worklist (usually empty) */
     ZSW_LAUNCH_SEED_WINDOW = 12,   /* seeded pass: whole rows around the anchor (seed_window_kernel) */
     ZSW_LAUNCH_SEED_BAND = 13,     /* seeded pass: band of diagonals (seed_band_kernel), one record per tier */
-    ZSW_LAUNCH_PRUNED = 14         /* column-pruned pass (strip + window kernels of zsw_score_prune.hip), one record per pass */
+    ZSW_LAUNCH_PRUNED = 14,        /* column-pruned pass (strip + window kernels of zsw_score_prune.hip), one record per pass */
+    ZSW_LAUNCH_ROW_CHUNKS = 15     /* no kernel: the ZSW_LAUNCH_V2 record that follows is a row-chunked launch with these numbers */
 } zsw_launch_kind;
 zsw_error zsw_debug_score_launches(zsw_context* ctx, uint32_t* records, uint32_t capacity, uint32_t* out_n);
 

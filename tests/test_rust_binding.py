@@ -98,7 +98,8 @@ def test_repr_c_structs_match_the_header():
         rfields = [(n, t.strip()) for n, t in re.findall(r"pub (\w+):\s*([^,\n]+),", rbody)]
         assert cfields == rfields, (cname, cfields, rfields)
     # enum values
-    for cname, val in (("ZSW_STATUS_SOME", 0), ("ZSW_STATUS_OVERFLOWED", 1), ("ZSW_STATUS_UNMAPPED", 2), ("ZSW_STATUS_EMPTY", 3), ("ZSW_MEM_HOST", 0), ("ZSW_MEM_DEVICE", 1)):
+    for cname, val in (("ZSW_STATUS_SOME", 0), ("ZSW_STATUS_OVERFLOWED", 1), ("ZSW_STATUS_UNMAPPED", 2), ("ZSW_STATUS_EMPTY", 3), ("ZSW_MEM_HOST", 0), ("ZSW_MEM_DEVICE", 1),
+                       ("ZSW_LAUNCH_ROW_CHUNKS", 15)):
         assert re.search(cname + r"\s*=\s*" + str(val) + r"\b", h) and re.search(r"pub const " + cname + r": \w+ = " + str(val) + ";", rs), cname
     for k, v in (("I8", 0), ("I16", 1), ("I32", 2), ("U8", 3), ("U16", 4), ("U32", 5)):
         assert re.search(r"ZSW_" + k + r"\s*=\s*" + str(v), h) and re.search(k + r"\s*=\s*" + str(v) + ",", rs)

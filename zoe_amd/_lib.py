@@ -35,7 +35,7 @@ DEBUG_SEED_DIAG_LANE_EVENTS = 131072
 DEBUG_SEED_NO_COSCHEDULE = 262144
 # zsw_launch_kind: the first entry of a zsw_debug_score_launches record
 (LAUNCH_V1_FAST, LAUNCH_V1_BIASED, LAUNCH_V2, LAUNCH_WIDE, LAUNCH_V1_FAST_REV, LAUNCH_V1_BIASED_REV, LAUNCH_WIDE_REV, LAUNCH_TILE_V2, LAUNCH_TILE_WIDE,
- LAUNCH_TILE_W32, LAUNCH_EXACT32, LAUNCH_EXACT32_WORKLIST, LAUNCH_SEED_WINDOW, LAUNCH_SEED_BAND, LAUNCH_PRUNED) = range(15)
+ LAUNCH_TILE_W32, LAUNCH_EXACT32, LAUNCH_EXACT32_WORKLIST, LAUNCH_SEED_WINDOW, LAUNCH_SEED_BAND, LAUNCH_PRUNED, LAUNCH_ROW_CHUNKS) = range(16)
 OPTION_EXACT_PRUNING = 1
 OPTION_MIN_SCORE = 2
 INT_TYPES = {"i8": 0, "i16": 1, "i32": 2, "u8": 3, "u16": 4, "u32": 5}

@@ -283,7 +283,8 @@ class SwContext:
 
     def debug_score_launches(self):
         """zsw_debug_score_launches (tests): the score kernels the last call launched, as a list of (kind, G, C, mode) tuples in
-        launch order — kind is a _lib.LAUNCH_* value, (G, C) the strip configuration, mode the MODE the kernel was built with."""
+        launch order — kind is a _lib.LAUNCH_* value, (G, C) the strip configuration, mode the MODE the kernel was built with. A
+        _lib.LAUNCH_ROW_CHUNKS record is (kind, rows per chunk, rows of overlap, chunks) of the row-chunked launch recorded next."""
         n = C.c_uint32(0)
         self.check(self.lib.zsw_debug_score_launches(self.h, None, 0, C.byref(n)))
         rec = np.zeros((n.value, 4), dtype=np.uint32)

@@ -228,7 +228,9 @@ __global__ void chunk_finalize_kernel(BatchDev b, const uint32_t* n_dev, const u
         if (out.tier) out.tier[id] = 0;
         if (mode != 0 && out.ref_end) out.ref_end[id] = 0;
         if (mode == 2 && out.query_end) out.query_end[id] = 0;
-    } else if (s >= limit) {  // near the representable limit: recompute exactly in 32 bits
+    } else if (s >= limit) {  // near the representable limit: recompute exactly in 32 bits (not reached behind seed_applicable, which
+                              // requires maxw * max_len + 8 < limit: no read of a seeded class can score that much; kept as the rule of
+                              // score_kernel_v2's own epilogue, and there is no test for it)
         out.fb_list[atomicAdd(out.fb_count, 1u)] = id;
     } else {
         uint32_t score;
@@ -662,6 +664,7 @@ static hipError_t launch_score_passes(const ScoringDev* d_sc, const ScoringDev& 
                 ap.chunk_keys = ws.chunk_keys;
                 const uint32_t zgrid = (bb.n_items + 255) / 256;
                 hipLaunchKernelGGL(chunk_zero_kernel, dim3(zgrid), dim3(256), 0, stream, ap.b.items, counter, bb.n_items, ws.chunk_keys);
+                note_launch(launches, ZSW_LAUNCH_ROW_CHUNKS, (int)ap.chunk_rows, (int)ap.chunk_overlap, (int)((ref_len + ap.chunk_rows - 1) / ap.chunk_rows));
                 note_launch(launches, ZSW_LAUNCH_V2, g, c, std::min(mode, 2));
                 pe = launch_table_cfg_v2(ap, g, c, mode, stream);
                 if (pe != hipSuccess) return pe;
