@@ -465,7 +465,11 @@ typedef enum zsw_debug_flag {
     /* score: the full pass over the reads the seed kernel hands back runs as launches of its own behind the band tiers. By default a
      * score-only call of two band tiers with reads of up to 152 bases (and no ZSW_OPTION_MIN_SCORE) scores them in the first tier's
      * launch: the hand-back blocks and the tier's persistent blocks share one grid (zsw_score_band.hip: seed_diag_handback_kernel) */
-    ZSW_DEBUG_SEED_NO_COSCHEDULE = 262144
+    ZSW_DEBUG_SEED_NO_COSCHEDULE = 262144,
+    /* score: contiguous reads of one length of up to 160 bases are seeded by the one-pass kernel (seed_kernel<true, .>: every
+     * thread sweeps its read byte by byte from LDS). By default the block converts its reads to packed rows once and every thread
+     * sweeps words (zsw_score_seed.hip: seed_packed_kernel) */
+    ZSW_DEBUG_SEED_PLAIN_KERNEL = 524288
 } zsw_debug_flag;
 zsw_error zsw_debug_set(zsw_context* ctx, uint32_t flags);
 

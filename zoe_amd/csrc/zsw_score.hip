@@ -650,7 +650,7 @@ static hipError_t launch_score_passes(const ScoringDev* d_sc, const ScoringDev& 
                                  (ws.debug & ZSW_DEBUG_SEED_WIDE_BAND) ? 0xffffffffu : (ws.debug & ZSW_DEBUG_SCORE_PRUNE_ANY_SIZE) ? 0u : SEED_NARROW_MIN_READS, band_grid_cap, stream,
                                  ws.window_timer, out.narrow_only, out.reads_reversed && out.skip_handed_back, launches,
                                  (ws.debug & ZSW_DEBUG_SEED_STRIP_FIRST_TIER) != 0, (ws.debug & ZSW_DEBUG_SEED_DIAG_LANE_EVENTS) != 0,
-                                 min_thr, ws.min_counts, &co, n0, &coscheduled);
+                                 min_thr, ws.min_counts, &co, n0, &coscheduled, (ws.debug & ZSW_DEBUG_SEED_PLAIN_KERNEL) != 0);
         if (pe != hipSuccess) return pe;
         ap.b.items = ws.prune_fail_list + list_off;
         ap.n_items_dev = counter;

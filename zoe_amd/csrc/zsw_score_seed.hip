@@ -13,6 +13,7 @@
 #include <vector>
 
 #include "zsw_score_seed.hpp"
+#include "zsw_seed_packed.hpp"
 #include "zsw_score_v2.hpp"
 #include "zsw_timer.hpp"
 
@@ -50,7 +51,12 @@ struct SeedArgs {
 // by 16-byte loads first — 150 single-byte loads per thread, each touching 64 different cache lines per wavefront, were most of
 // this kernel's time.
 constexpr uint32_t SEED_STAGE_LEN = 160;
+static_assert(SEED_STAGE_LEN == (uint32_t)SEED_PACKED_MAX_LEN, "the staged batches are the ones seed_packed_kernel takes");
 
+template <bool MINS>
+__device__ __forceinline__ void seed_emit(const SeedArgs& a, uint32_t k, uint32_t id, uint32_t len, bool valid, const SeedRead& sr, int bound);
+
+// The STAGED instantiations run under ZSW_DEBUG_SEED_PLAIN_KERNEL only: seed_packed_kernel (below) serves those batches.
 // MINS (ZSW_OPTION_MIN_SCORE > 0; an instantiation of its own, so that the default one is what it was): seed_read also returns
 // claim W's bound, the most any local alignment of the read against the whole reference can score (zsw_seed.hpp). A read —
 // anchored or not — whose bound is below a.min_thr is settled here as ZSW_STATUS_BELOW_MIN_SCORE: it gets fail_key, so that no
@@ -95,6 +101,8 @@ __global__ __launch_bounds__(256) void seed_kernel(SeedArgs a) {
     sr.ok = 0;
     sr.t_all = sr.d_fa = sr.d_bl = 0;
     sr.bl_mask = 0;
+    sr.dt = sr.d_fb = sr.u_whole = 0;
+    sr.fa_mask = sr.fb_mask = 0;
     if (valid && len >= SEED_MIN_LEN && len < SEED_KEY_BIAS) {
         const uint8_t* bases = STAGED ? sbytes + off : a.b.bases + off;
         const bool rev = a.reversed;
@@ -121,14 +129,38 @@ __global__ __launch_bounds__(256) void seed_kernel(SeedArgs a) {
                 *l1 = e.y;
             });
     }
+    int bound = sr.u_whole;
+    if (MINS && valid && len > 0 && len < SEED_MIN_LEN) {
+        const uint8_t* bases = STAGED ? sbytes + off : a.b.bases + off;
+        bound = 0;
+        for (uint32_t c = 0; c < len; ++c) bound += (int)(cell_lut[bases[c]] & 0xffu);
+    }
+    seed_emit<MINS>(a, k, id, len, valid, sr, bound);
+    if (valid && a.codes) {
+        // the last, partial dword of the codes and the rest of the row: padding (reads the seed did not sweep are all padding)
+        uint32_t* code_row = a.codes + (size_t)k * a.cs;
+        const bool swept = len >= SEED_MIN_LEN && len < SEED_KEY_BIAS;
+        const uint32_t full = swept ? len >> 3 : 0;
+        if (full < a.cs) {
+            uint32_t tail = 0xffffffffu;
+            if (swept && (len & 7u)) {
+                const uint8_t* bases = STAGED ? sbytes + off : a.b.bases + off;
+                tail = 0;
+                for (uint32_t c = full * 8; c < full * 8 + 8; ++c)
+                    tail |= (c < len ? (uint32_t)(cell_lut[bases[a.reversed ? len - 1 - c : c]] >> 12) : 15u) << (4 * (c & 7));
+            }
+            code_row[full] = tail;
+            for (uint32_t d = full + 1; d < a.cs; ++d) code_row[d] = 0xffffffffu;
+        }
+    }
+}
+
+// What both seed kernels leave per read: the MINS settle, sort key, id, bounds and masks, and the hand-back list. bound: claim W's
+// bound of a swept read, the potential of its columns for a read too short to be swept (MINS only).
+template <bool MINS>
+__device__ __forceinline__ void seed_emit(const SeedArgs& a, uint32_t k, uint32_t id, uint32_t len, bool valid, const SeedRead& sr, int bound) {
     bool below = false;
     if (MINS && valid && len > 0 && len < SEED_KEY_BIAS) {  // (an empty read is EMPTY, decided by its length alone: it goes where it went)
-        int bound = sr.u_whole;
-        if (len < SEED_MIN_LEN) {
-            const uint8_t* bases = STAGED ? sbytes + off : a.b.bases + off;
-            bound = 0;
-            for (uint32_t c = 0; c < len; ++c) bound += (int)(cell_lut[bases[c]] & 0xffu);
-        }
         below = seed_below_min(bound, a.min_thr);
         if (below) {
             a.out.score[id] = 0;
@@ -151,21 +183,6 @@ __global__ __launch_bounds__(256) void seed_kernel(SeedArgs a) {
         if (a.codes) {
             a.band_masks[k] = sr.fa_mask | (sr.fb_mask << 16);
             a.band_dfb[k] = (uint8_t)sr.d_fb;
-            // the last, partial dword of the codes and the rest of the row: padding (reads the seed did not sweep are all padding)
-            uint32_t* code_row = a.codes + (size_t)k * a.cs;
-            const bool swept = len >= SEED_MIN_LEN && len < SEED_KEY_BIAS;
-            const uint32_t full = swept ? len >> 3 : 0;
-            if (full < a.cs) {
-                uint32_t tail = 0xffffffffu;
-                if (swept && (len & 7u)) {
-                    const uint8_t* bases = STAGED ? sbytes + off : a.b.bases + off;
-                    tail = 0;
-                    for (uint32_t c = full * 8; c < full * 8 + 8; ++c)
-                        tail |= (c < len ? (uint32_t)(cell_lut[bases[a.reversed ? len - 1 - c : c]] >> 12) : 15u) << (4 * (c & 7));
-                }
-                code_row[full] = tail;
-                for (uint32_t d = full + 1; d < a.cs; ++d) code_row[d] = 0xffffffffu;
-            }
         }
     }
     // reads without an anchor are scored over all their cells: one atomic per wavefront
@@ -178,6 +195,76 @@ __global__ __launch_bounds__(256) void seed_kernel(SeedArgs a) {
         base = (uint32_t)__shfl((int)base, leader, 64);
         if (fail) a.fail_list[base + (uint32_t)__popcll(m & ((1ull << lane) - 1ull))] = id;
     }
+}
+
+// The seed kernel of contiguous reads of one length L <= SEED_PACKED_MAX_LEN (what seed_kernel<true, .> served), in two phases
+// (zsw_seed_packed.hpp). Phase A: the block converts its reads once. Work item i = (read r, dword d) of the block's code rows —
+// consecutive lanes take consecutive dwords, so the rows go out as whole lines — loads its eight bytes from global memory in one
+// piece (seed_pack_window), turns them into the residue-code dword and leaves it in LDS too. Phase B: one thread per read,
+// seed_read_packed over its row. LDS (seed_packed_lds_bytes): 20,512 bytes per block for reads of 150 bases, 22,560 for 160.
+constexpr uint32_t SEED_PACKED_LUT_WORDS = 64 + 8;  // residue index per read byte, seed_cell (16 bits) per residue index
+size_t seed_packed_lds_bytes(uint32_t L) { return 4 * (size_t)(SEED_PACKED_LUT_WORDS + 256u * (uint32_t)seed_packed_res_words((int)L)); }
+
+template <bool MINS>
+__global__ __launch_bounds__(256) void seed_packed_kernel(SeedArgs a) {
+    extern __shared__ uint32_t seed_lds[];
+    const uint32_t t = threadIdx.x;
+    const uint32_t L = a.b.fixed_len;
+    const uint32_t res_words = (uint32_t)seed_packed_res_words((int)L);
+    uint8_t* entry_lut = reinterpret_cast<uint8_t*>(seed_lds);
+    uint16_t* cell16 = reinterpret_cast<uint16_t*>(seed_lds + 64);
+    uint32_t* res_rows = seed_lds + SEED_PACKED_LUT_WORDS;
+    entry_lut[t] = a.sc->index_map[t];
+    if (t < 16) cell16[t] = (uint16_t)seed_cell(a.sp, (int)t);
+    __syncthreads();
+    const uint32_t r0 = blockIdx.x * 256u;
+    const uint32_t nr = min(256u, a.n - r0);
+    const uint8_t* src = a.b.bases + (uint64_t)(a.first + r0) * L;
+    const int cnt = (int)(nr * L);    // the block's bytes
+    const uint32_t rw = (L + 7) / 8;  // dwords of a row that hold a column (< a.cs)
+    const uint32_t cs = a.cs;
+    const bool swept = L >= SEED_MIN_LEN;  // (the rows of reads the seed does not sweep are all padding)
+    const bool rev = a.reversed;
+    const uint32_t magic = seed_div_magic((int)cs);  // i / cs for i < 256 * cs, cs <= SEED_PACKED_RES_WORDS_MAX
+    uint32_t* codes_out = a.codes ? a.codes + (size_t)r0 * cs : nullptr;
+    for (uint32_t i = t; i < nr * cs; i += 256) {
+        const uint32_t r = (uint32_t)seed_div((int)i, magic), d = i - r * cs;
+        uint32_t res = 0xffffffffu;
+        if (d < rw) {
+            const int ncols = min(8, (int)L - 8 * (int)d);
+            const uint64_t w = seed_pack_window(src, cnt, (int)L, (int)r, (int)d, rev);
+            res = seed_pack8(w, ncols, [&](uint32_t byte) { return (uint32_t)entry_lut[byte]; });
+            res_rows[r * res_words + d] = res;
+        }
+        if (codes_out) codes_out[i] = swept ? res : 0xffffffffu;
+    }
+    __syncthreads();
+    const uint32_t k = r0 + t;
+    const bool valid = t < nr;
+    const uint32_t id = a.first + k;
+    const uint32_t* res_row = res_rows + t * res_words;
+    SeedRead sr;
+    sr.ok = 0;
+    sr.t_all = sr.d_fa = sr.d_bl = 0;
+    sr.bl_mask = 0;
+    sr.dt = sr.d_fb = sr.u_whole = 0;
+    sr.fa_mask = sr.fb_mask = 0;
+    if (valid && swept) {
+        const uint2* table = a.table;
+        sr = seed_read_packed<MINS>(
+            a.sp, (int)L, res_row, [&](uint32_t res) { return (uint32_t)cell16[res]; },
+            [&](uint32_t code, uint32_t* f1, uint32_t* l1) {
+                const uint2 e = table[code];
+                *f1 = e.x;
+                *l1 = e.y;
+            });
+    }
+    int bound = sr.u_whole;
+    if (MINS && valid && L > 0 && !swept) {  // too short to be swept: the potential of its columns
+        bound = 0;
+        for (uint32_t c = 0; c < L; ++c) bound += (int)(cell16[(res_row[c >> 3] >> (4 * (c & 7))) & 15u] & 0xffu);
+    }
+    seed_emit<MINS>(a, k, id, L, valid, sr, bound);
 }
 
 __global__ void seed_gtab_kernel(const uint8_t* ref, uint32_t ref_len, const ScoringDev* sc, ScoreArgsV2 a, uint2* gtab) {
@@ -225,7 +312,7 @@ hipError_t launch_score_seeded(const ScoreArgsV2& a2, int G, int C, uint32_t max
                                uint2* gtab, uint32_t* fail_list, uint32_t* fail_count, int mode, const ScoreArgsV2* band_tabs, const uint2* gtab_band, int32_t* band_dbg,
                                uint32_t narrow_min_reads, uint32_t band_grid_cap, hipStream_t stream, KernelTimer* window_timer, bool narrow_only, bool reads_reversed,
                                std::vector<uint32_t>* launches, bool strip_first_tier, bool diag_lane_events, uint32_t min_thr, uint32_t* min_counts,
-                               const CoscheduleCase* co, uint32_t* n0, bool* coscheduled) {
+                               const CoscheduleCase* co, uint32_t* n0, bool* coscheduled, bool plain_seed_kernel) {
     const uint32_t n = a2.b.n_items;
     if (coscheduled) *coscheduled = false;
     if (!min_counts) min_thr = 0;
@@ -280,10 +367,15 @@ hipError_t launch_score_seeded(const ScoreArgsV2& a2, int G, int C, uint32_t max
     s.out = a2.out;
     s.min_count = min_counts;  // [0]: settled by the whole-read bound
     const bool staged = !s.b.offsets && !s.b.items && s.b.fixed_len <= SEED_STAGE_LEN;
+    // the two-phase kernel for the staged batches (cs: its residue rows hold a read's dwords, and i / cs by seed_div)
+    const bool packed = staged && !plain_seed_kernel && cs <= (uint32_t)SEED_PACKED_RES_WORDS_MAX;
     if (min_thr) {
-        if (staged) hipLaunchKernelGGL((seed_kernel<true, true>), dim3((n + 255) / 256), dim3(256), 0, stream, s);
+        if (packed) hipLaunchKernelGGL((seed_packed_kernel<true>), dim3((n + 255) / 256), dim3(256), seed_packed_lds_bytes(s.b.fixed_len), stream, s);
+        else if (staged) hipLaunchKernelGGL((seed_kernel<true, true>), dim3((n + 255) / 256), dim3(256), 0, stream, s);
         else hipLaunchKernelGGL((seed_kernel<false, true>), dim3((n + 255) / 256), dim3(256), 0, stream, s);
-    } else if (staged)
+    } else if (packed)
+        hipLaunchKernelGGL((seed_packed_kernel<false>), dim3((n + 255) / 256), dim3(256), seed_packed_lds_bytes(s.b.fixed_len), stream, s);
+    else if (staged)
         hipLaunchKernelGGL((seed_kernel<true, false>), dim3((n + 255) / 256), dim3(256), 0, stream, s);
     else
         hipLaunchKernelGGL((seed_kernel<false, false>), dim3((n + 255) / 256), dim3(256), 0, stream, s);

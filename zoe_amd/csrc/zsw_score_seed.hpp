@@ -156,7 +156,8 @@ hipError_t launch_score_seeded(const ScoreArgsV2& a2, int G, int C, uint32_t max
                                // decision holds, *fail_count as the seed kernel left it is copied to the device word n0 and the first tier's
                                // launch scores fail_list[0, *n0) itself, with a2's tables: the caller's launches start at *n0
                                // (ScoreArgsV2::first_item_dev). *coscheduled says whether that happened; if not, n0 is not written.
-                               const CoscheduleCase* co = nullptr, uint32_t* n0 = nullptr, bool* coscheduled = nullptr);
+                               const CoscheduleCase* co = nullptr, uint32_t* n0 = nullptr, bool* coscheduled = nullptr,
+                               bool plain_seed_kernel = false /* ZSW_DEBUG_SEED_PLAIN_KERNEL */);
 // (Re)builds the index for a reference given as residue indices on the host.
 hipError_t seed_index_update(SeedIndex* ix, const ScoringDev& sc, const uint8_t* h_ref, size_t ref_len);
 void seed_index_release(SeedIndex* ix);
