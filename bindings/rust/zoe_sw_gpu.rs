@@ -69,6 +69,42 @@ pub struct ZswAlignment {
     pub ciglet_offset: u64,
 }
 
+/// `zsw_alignment_stats`: what `zsw_annotate_batch` counts along one CIGAR
+#[repr(C)]
+#[derive(Clone, Copy, Default, Debug, PartialEq, Eq)]
+pub struct ZswAlignmentStats {
+    pub matches:     u32,
+    pub mismatches:  u32,
+    pub ins_bases:   u32,
+    pub del_bases:   u32,
+    pub ins_runs:    u32,
+    pub del_runs:    u32,
+    pub path_score:  i32,
+    pub path_status: u32,
+}
+
+impl ZswAlignmentStats {
+    /// The `NM` tag of SAM: mismatches plus inserted and deleted bases
+    pub fn nm(&self) -> u32 {
+        self.mismatches + self.ins_bases + self.del_bases
+    }
+}
+
+/// `zsw_path_status`: `ScoringError` of `sw_score_from_path` (1..=6), then the reads that are not walked
+pub const ZSW_PATH_OK: u32 = 0;
+pub const ZSW_PATH_REFERENCE_ENDED: u32 = 1;
+pub const ZSW_PATH_QUERY_ENDED: u32 = 2;
+pub const ZSW_PATH_FULL_QUERY_NOT_USED: u32 = 3;
+pub const ZSW_PATH_FULL_REFERENCE_NOT_USED: u32 = 4;
+pub const ZSW_PATH_INVALID_CIGAR_OP: u32 = 5;
+pub const ZSW_PATH_NEGATIVE_SCORE: u32 = 6;
+pub const ZSW_PATH_NO_ALIGNMENT: u32 = 7;
+pub const ZSW_PATH_BAD_RECORD: u32 = 8;
+/// flags of `zsw_annotate_batch`
+pub const ZSW_ANNOTATE_READ_IS_REF: i32 = 1;
+pub const ZSW_ANNOTATE_SHARED: i32 = 2;
+pub const ZSW_ANNOTATE_MATCH_RESIDUES: i32 = 4;
+
 pub const ZSW_OK: i32 = 0;
 pub const ZSW_MEM_HOST: i32 = 0;
 pub const ZSW_ENCODING_BYTES: i32 = 0;
@@ -160,6 +196,7 @@ unsafe extern "C" {
     fn zsw_prune_rescored(ctx: *mut ZswContext, out_reads: *mut u64) -> i32;
     fn zsw_set_option(ctx: *mut ZswContext, option: i32, value: i64) -> i32;
     fn zsw_min_score_counts(ctx: *mut ZswContext, out: *mut u64) -> i32;
+    fn zsw_annotate_batch(ctx: *mut ZswContext, reads: *const ZswBatch, flags: i32, aln: *const ZswAlignment, status: *const u8, inc: *const u32, op: *const u8, n_ciglets: u64, out_stats: *mut c_void, out_aln: *mut ZswAlignment, out_inc: *mut u32, out_op: *mut u8, ciglet_cap: u64, out_n_ciglets: *mut u64, stream: *mut c_void) -> i32;
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -749,6 +786,51 @@ impl GpuContext {
         // SAFETY: out holds as many bytes as the batch, strand one entry per read
         self.check(unsafe { zsw_orient_batch(self.raw, &batch.as_c(), strand.as_ptr(), out.as_mut_ptr(), ptr::null_mut()) }, 0, 0)?;
         Ok((0..reads.len()).map(|i| out[batch.offsets[i] as usize..batch.offsets[i + 1] as usize].to_vec()).collect())
+    }
+
+    /// `zsw_annotate_batch` over the raw records of an alignment call on this context (scoring and the sequence the flags name are
+    /// the configured ones): per read the match / mismatch / gap counts and `sw_score_from_path`, and with `verbose` the records
+    /// and ciglets of `Alignment::to_verbose_sequence_matching` (`M` split into `=` / `X`). `flags`: `ZSW_ANNOTATE_*`, by the
+    /// call that produced the records (see the header).
+    #[allow(clippy::type_complexity)]
+    pub fn annotate_batch<Q: AsRef<[u8]>>(
+        &self, reads: &[Q], flags: i32, recs: &[ZswAlignment], status: &[u8], inc: &[u32], op: &[u8], verbose: bool,
+    ) -> Result<(Vec<ZswAlignmentStats>, Option<(Vec<ZswAlignment>, Vec<u32>, Vec<u8>)>), GpuError> {
+        assert!(recs.len() == reads.len() && status.len() == reads.len() && inc.len() == op.len());
+        let batch = HostBatch::new(reads);
+        let c = batch.as_c();
+        let n = reads.len();
+        let mut stats = vec![ZswAlignmentStats::default(); n.max(1)];
+        if !verbose {
+            // SAFETY: stats holds n entries; the optional outputs are absent
+            let code = unsafe {
+                zsw_annotate_batch(self.raw, &c, flags, recs.as_ptr(), status.as_ptr(), inc.as_ptr(), op.as_ptr(), inc.len() as u64, stats.as_mut_ptr().cast::<c_void>(),
+                                   ptr::null_mut(), ptr::null_mut(), ptr::null_mut(), 0, ptr::null_mut(), ptr::null_mut())
+            };
+            self.check(code, 0, 0)?;
+            stats.truncate(n);
+            return Ok((stats, None));
+        }
+        let mut out = vec![ZswAlignment::default(); n.max(1)];
+        let mut cap = (2 * inc.len()).max(16);
+        loop {
+            let (mut oinc, mut oop, mut needed) = (vec![0u32; cap], vec![0u8; cap], 0u64);
+            // SAFETY: every output array holds what the call may write: n records, cap ciglets
+            let code = unsafe {
+                zsw_annotate_batch(self.raw, &c, flags, recs.as_ptr(), status.as_ptr(), inc.as_ptr(), op.as_ptr(), inc.len() as u64, stats.as_mut_ptr().cast::<c_void>(),
+                                   out.as_mut_ptr(), oinc.as_mut_ptr(), oop.as_mut_ptr(), cap as u64, &mut needed, ptr::null_mut())
+            };
+            if code == -1 && needed as usize > cap {
+                cap = needed as usize; // capacity too small: the required size came back
+                continue;
+            }
+            self.check(code, 0, 0)?;
+            stats.truncate(n);
+            out.truncate(n);
+            oinc.truncate(needed as usize);
+            oop.truncate(needed as usize);
+            return Ok((stats, Some((out, oinc, oop))));
+        }
     }
 
     /// Per read: `profiles.sw_align_from_i{from_width}_3pass(seq)` of the read or of its reverse complement, whichever scores

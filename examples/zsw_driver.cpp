@@ -4,11 +4,14 @@
 // POS = ref_range.start + 1, CIGAR = states, AS:i = score.
 //
 //   g++ -O2 -std=c++17 -Iinclude examples/zsw_driver.cpp -o examples/zsw_driver -Lzoe_amd -lzoe_sw_hip -Wl,-rpath,$PWD/zoe_amd
-//   ./examples/zsw_driver reference.txt reads.fastq [--score-only | --3pass | --both-strands] [--min-score T]
+//   ./examples/zsw_driver reference.txt reads.fastq [--score-only | --3pass | --both-strands] [--min-score T] [--nm] [--verbose-cigar]
 // --both-strands: every read is aligned on whichever strand scores higher (sw_align_strands_from_i8_3pass); a read answered by
 // its reverse complement gets flag 16, SEQ reverse complemented and QUAL reversed, and POS / CIGAR are those of that sequence.
 // --min-score T (with --3pass or --score-only, the calls ZSW_OPTION_MIN_SCORE covers): a read that scores less than T is written as
 // an unmapped record (flag 4; `*` with --score-only), exactly as a read without any alignment is — and costs the GPU next to nothing.
+// --nm appends NM:i: (mismatches + inserted + deleted bases) to every mapped record, --verbose-cigar writes the CIGAR with = / X in
+// place of M (Alignment::to_verbose_sequence_matching); both come from one zsw_annotate_batch pass over the alignments. Without them
+// the output is what it always was.
 #include <algorithm>
 #include <cstdlib>
 #include <cstring>
@@ -37,16 +40,18 @@ static std::string read_reference(const std::string& path, std::string* name) {
 
 int main(int argc, char** argv) {
     if (argc < 3) {
-        std::cerr << "usage: zsw_driver reference.(fa|txt) reads.fastq [--score-only | --3pass | --both-strands] [--min-score T]\n";
+        std::cerr << "usage: zsw_driver reference.(fa|txt) reads.fastq [--score-only | --3pass | --both-strands] [--min-score T] [--nm] [--verbose-cigar]\n";
         return 2;
     }
-    bool score_only = false, three_pass = false, both_strands = false;
+    bool score_only = false, three_pass = false, both_strands = false, nm = false, verbose_cigar = false;
     long long min_score = 0;
     for (int k = 3; k < argc; ++k) {
         if (!std::strcmp(argv[k], "--score-only")) score_only = true;
         else if (!std::strcmp(argv[k], "--3pass")) three_pass = true;  // sw_align_from_i8_3pass instead of sw_align_from_i8
         else if (!std::strcmp(argv[k], "--both-strands")) both_strands = true;  // sw_align_strands_from_i8_3pass
         else if (!std::strcmp(argv[k], "--min-score") && k + 1 < argc) min_score = std::atoll(argv[++k]);
+        else if (!std::strcmp(argv[k], "--nm")) nm = true;
+        else if (!std::strcmp(argv[k], "--verbose-cigar")) verbose_cigar = true;
         else {
             std::cerr << "zsw_driver: unknown argument " << argv[k] << '\n';
             return 2;
@@ -82,6 +87,8 @@ int main(int argc, char** argv) {
         auto alns = both_strands ? profiles.sw_align_strands_from_i8_3pass(reference)
                     : three_pass ? profiles.sw_align_from_i8_3pass(reference)
                                  : profiles.sw_align_from_i8(reference);
+        zoe::Annotation ann;  // NM and = / X CIGARs: one pass over the alignments, against the reads as aligned
+        if (nm || verbose_cigar) ann = profiles.annotate(alns, reference, false, false, verbose_cigar, both_strands ? &profiles.last_strands() : nullptr);
         std::vector<uint8_t> strand(reads.size(), 0);
         if (both_strands) {  // SEQ and QUAL as aligned: the reverse complement of a read answered on the reverse strand, its qualities reversed
             strand = profiles.last_strands();
@@ -93,8 +100,10 @@ int main(int argc, char** argv) {
         for (size_t i = 0; i < reads.size(); ++i) {
             if (alns[i].is_some()) {
                 const zoe::Alignment& a = alns[i].value;
-                std::cout << names[i] << '\t' << (strand[i] ? 16 : 0) << '\t' << ref_name << '\t' << a.ref_start + 1 << "\t255\t" << a.cigar() << "\t*\t0\t0\t" << reads[i]
-                          << '\t' << quals[i] << "\tAS:i:" << a.score << '\n';
+                std::cout << names[i] << '\t' << (strand[i] ? 16 : 0) << '\t' << ref_name << '\t' << a.ref_start + 1 << "\t255\t"
+                          << (verbose_cigar ? ann.verbose[i].value.cigar() : a.cigar()) << "\t*\t0\t0\t" << reads[i] << '\t' << quals[i] << "\tAS:i:" << a.score;
+                if (nm) std::cout << "\tNM:i:" << ann.nm(i);
+                std::cout << '\n';
             } else {
                 std::cout << names[i] << "\t4\t*\t0\t0\t*\t*\t0\t0\t" << reads[i] << '\t' << quals[i] << '\n';
             }

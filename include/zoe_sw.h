@@ -284,6 +284,62 @@ zsw_error zsw_align_3pass_shared_batch_from(zsw_context* ctx, const zsw_batch* r
                                             zsw_alignment* out_aln, uint8_t* out_status, uint8_t* out_tier, uint32_t* out_inc, uint8_t* out_op,
                                             uint64_t ciglet_cap, uint64_t* out_n_ciglets, void* stream);
 
+/* ---- annotation of alignments: =/X CIGARs, edit counts, path score ------------------------------- */
+/* One pass over the records an alignment call wrote (or any caller-built records), beside the two sequences each was aligned
+ * between. Per read with status[i] == ZSW_STATUS_SOME the library builds the Alignment of the record, with ref_in_alignment = the
+ * record's reference sequence [ref_start, ref_end), and computes
+ *   path_score / path_status  sw_score_from_path (src/alignment/sw/mod.rs:399-454) statement for statement: ops M = X I D S N H P,
+ *                             gap_open + gap_extend * (inc - 1) per I / D ciglet, the first error in that function's own order
+ *                             (ZSW_PATH_* 1..6 mirror ScoringError);
+ *   the counts                columns under M, = and X are compared and counted as matches or mismatches; I / D ciglets add to the
+ *                             base and run counts; S N H P count nothing (NM = mismatches + ins_bases + del_bases);
+ *   the verbose CIGAR         (if out_aln is given) AlignmentStates::to_verbose_sequence_matching(reference, query, ref_start)
+ *                             (src/alignment/types/state.rs:320-342; Alignment::to_verbose_sequence_matching, types/output.rs:456-479):
+ *                             each M column becomes = or X through add_state, every other ciglet goes through add_ciglet, so equal
+ *                             neighbours merge (3=2M whose M starts with two matches gives 5=) and no ciglet has inc == 0.
+ * flags say which call produced the records:
+ *   zsw_align*_batch(_from), and the *_strands_* 3-pass call on the oriented batch of zsw_orient_batch:
+ *                                      invert == 0: 0                                     invert != 0: ZSW_ANNOTATE_READ_IS_REF
+ *   zsw_align*_shared_batch(_from):    invert == 0: ZSW_ANNOTATE_SHARED | ZSW_ANNOTATE_READ_IS_REF    invert != 0: ZSW_ANNOTATE_SHARED
+ * ZSW_ANNOTATE_READ_IS_REF: ref_* of a record index the read and query_* the context's sequence (without it the other way round).
+ * ZSW_ANNOTATE_SHARED: the other sequence is the one of zsw_set_profile_sequence and the read takes the matrix's row axis
+ * (weights[idx(read) * S + idx(seq)]); without it the other sequence is the one of zsw_set_reference and the read takes the column
+ * axis (weights[idx(ref) * S + idx(read)]): row = non-profile residue, column = profile residue, whatever invert was.
+ * ZSW_ANNOTATE_MATCH_RESIDUES: a column is a match when index_map sends both bytes to the same residue; by default raw bytes are
+ * compared, which is the reference's rule (state.rs:330): `a` against `A` is X.
+ * aln / status: n_reads entries; inc / op: n_ciglets pairs; every array lives where reads->mem says. out_stats: n_reads
+ * zsw_alignment_stats (declared void*: a zsw_alignment_stats array converts without a cast).
+ * out_aln[i] = aln[i] with n_ciglets / ciglet_offset pointing into out_inc / out_op, the reads laid out in read order (no atomics
+ * decide a place: the output is the same on every run). Capacity protocol of the alignment calls: *out_n_ciglets receives the
+ * total; beyond ciglet_cap the call returns ZSW_ERR_INVALID_ARGUMENT with the required size there (the stats are written all the same).
+ * Reads that are not walked — zeroed stats but for path_status, out_aln[i] copied with no ciglets —: status[i] != ZSW_STATUS_SOME
+ * (ZSW_PATH_NO_ALIGNMENT); ciglets that leave [0, n_ciglets), ref_start > ref_end, a range or length that disagrees with the actual
+ * sequences, an inc of 0, a merged inc beyond 32 bits (ZSW_PATH_BAD_RECORD); an op outside MIDNSHP=X (ZSW_PATH_INVALID_CIGAR_OP); and
+ * a path that leaves a sequence (ZSW_PATH_REFERENCE_ENDED, ZSW_PATH_QUERY_ENDED: the reference's conversion would panic there).
+ * ZSW_PATH_FULL_*_NOT_USED and ZSW_PATH_NEGATIVE_SCORE keep counts and verbose CIGAR. Records and ciglets are caller memory: every
+ * index derived from them is checked in 64-bit arithmetic before the load that uses it; a malformed record is a status, never a fault.
+ * Without out_aln the call is asynchronous for device batches; with it, it synchronises once for the total. Host batches are staged
+ * and the call is synchronous. ZSW_ENCODING_PACKED4: ZSW_ERR_UNSUPPORTED. Output arrays must not overlap inputs or each other;
+ * unknown flag bits or a null required pointer: ZSW_ERR_INVALID_ARGUMENT; scoring, or the sequence the flags name, not set:
+ * ZSW_ERR_NOT_CONFIGURED. Lanes per alignment and the LDS threshold of the context's sequence: zoe_amd/csrc/zsw_annotate.hpp. */
+typedef struct zsw_alignment_stats { /* 32 bytes */
+    uint32_t matches, mismatches;    /* columns under M, = or X, by the chosen equality */
+    uint32_t ins_bases, del_bases;   /* sum of inc over I / D ciglets */
+    uint32_t ins_runs, del_runs;     /* number of I / D ciglets */
+    int32_t path_score;              /* sw_score_from_path; the negative sum for ZSW_PATH_NEGATIVE_SCORE; else 0 */
+    uint32_t path_status;            /* zsw_path_status */
+} zsw_alignment_stats;
+typedef enum zsw_path_status {
+    ZSW_PATH_OK = 0, ZSW_PATH_REFERENCE_ENDED = 1, ZSW_PATH_QUERY_ENDED = 2, ZSW_PATH_FULL_QUERY_NOT_USED = 3,
+    ZSW_PATH_FULL_REFERENCE_NOT_USED = 4, ZSW_PATH_INVALID_CIGAR_OP = 5, ZSW_PATH_NEGATIVE_SCORE = 6, ZSW_PATH_NO_ALIGNMENT = 7,
+    ZSW_PATH_BAD_RECORD = 8
+} zsw_path_status;
+enum { ZSW_ANNOTATE_READ_IS_REF = 1, ZSW_ANNOTATE_SHARED = 2, ZSW_ANNOTATE_MATCH_RESIDUES = 4 };
+zsw_error zsw_annotate_batch(zsw_context* ctx, const zsw_batch* reads, int flags, const zsw_alignment* aln, const uint8_t* status,
+                             const uint32_t* inc, const uint8_t* op, uint64_t n_ciglets, void* out_stats,
+                             zsw_alignment* out_aln, uint32_t* out_inc, uint8_t* out_op, uint64_t ciglet_cap, uint64_t* out_n_ciglets,
+                             void* stream);
+
 /* ---- pre-alignment filter ------------------------------------------------------------------ */
 /* out_pass[i] = sneaky_snake(&reference[ref_start[i] .. ref_start[i]+ref_len[i]], read_i, threshold)
  * (src/alignment/sneaky_snake.rs:78-131): the SneakySnake edit-distance filter between a read and a candidate window of the

@@ -120,6 +120,40 @@ struct Alignment {
         }
         return s;
     }
+    // AlignmentStates::add_ciglet (types/state.rs:142-152): equal neighbours merge, an inc of 0 adds nothing
+    static void add_ciglet(std::vector<Ciglet>& states, size_t inc, uint8_t op) {
+        if (!inc) return;
+        if (!states.empty() && states.back().op == op) states.back().inc += inc;
+        else states.push_back({inc, op});
+    }
+    // Alignment::to_verbose_sequence_matching (types/output.rs:456-479) on the host, one alignment at a time: M becomes = where the
+    // bytes are equal and X elsewhere; `reference` is the whole reference. Throws where the reference panics (a path that leaves a
+    // sequence). A batch goes through annotate() of the profile classes, which does this on the GPU.
+    Alignment to_verbose_sequence_matching(const std::string& reference, const std::string& query) const {
+        Alignment out = *this;
+        out.states.clear();
+        size_t r = ref_start, q = 0;
+        for (const Ciglet& c : states) {
+            if (c.op == 'M') {
+                if (r + c.inc > reference.size() || q + c.inc > query.size()) throw std::out_of_range("to_verbose_sequence_matching: the alignment leaves a sequence");
+                for (size_t k = 0; k < c.inc; ++k) add_ciglet(out.states, 1, query[q + k] == reference[r + k] ? '=' : 'X');
+            } else {
+                add_ciglet(out.states, c.inc, c.op);
+            }
+            if (c.op == 'M' || c.op == '=' || c.op == 'X' || c.op == 'I' || c.op == 'S') q += c.inc;
+            if (c.op == 'M' || c.op == '=' || c.op == 'X' || c.op == 'D' || c.op == 'N') r += c.inc;
+        }
+        return out;
+    }
+};
+
+// zsw_alignment_stats per read, and (if asked for) the alignments of Alignment::to_verbose_sequence_matching: what annotate() of the
+// profile classes returns (zsw_annotate_batch)
+struct Annotation {
+    std::vector<zsw_alignment_stats> stats;
+    std::vector<MaybeAligned<Alignment>> verbose;  // empty without `verbose`
+    // the NM tag of SAM: mismatches + inserted + deleted bases
+    uint32_t nm(size_t i) const { return stats[i].mismatches + stats[i].ins_bases + stats[i].del_bases; }
 };
 
 class GpuContext {
@@ -147,6 +181,55 @@ class GpuContext {
         if (e == ZSW_OK) return;
         if (e >= 1 && e <= 4) throw ProfileError(e);
         throw GpuError(e, zsw_last_error_string(ctx_));
+    }
+    // zsw_annotate_batch over alignments that a call on `reads` (a host batch) returned, with scoring and the sequence the flags
+    // name set on this context: the records are flattened again, annotated on the GPU, and rebuilt. flags: ZSW_ANNOTATE_*.
+    Annotation annotate(const zsw_batch& reads, int flags, const std::vector<MaybeAligned<Alignment>>& alns, bool verbose) const {
+        const size_t n = alns.size();
+        if (n != reads.n_reads) throw GpuError(ZSW_ERR_INVALID_ARGUMENT, "one alignment per read");
+        std::vector<zsw_alignment> rec(n);
+        std::vector<uint8_t> status(n);
+        std::vector<uint32_t> inc;
+        std::vector<uint8_t> op;
+        for (size_t i = 0; i < n; ++i) {
+            const Alignment& a = alns[i].value;
+            status[i] = (uint8_t)alns[i].status;
+            rec[i] = zsw_alignment{a.score, (uint32_t)a.ref_start, (uint32_t)a.ref_end, (uint32_t)a.query_start, (uint32_t)a.query_end, (uint32_t)a.ref_len,
+                                   (uint32_t)a.query_len, (uint32_t)a.states.size(), (uint64_t)inc.size()};
+            for (const Ciglet& c : a.states) {
+                if (c.inc > 0xffffffffull) throw GpuError(ZSW_ERR_INVALID_ARGUMENT, "a ciglet beyond 32 bits");
+                inc.push_back((uint32_t)c.inc);
+                op.push_back(c.op);
+            }
+        }
+        Annotation out;
+        out.stats.resize(n);
+        if (!verbose) {
+            check(zsw_annotate_batch(ctx_, &reads, flags, rec.data(), status.data(), inc.data(), op.data(), inc.size(), out.stats.data(), nullptr, nullptr, nullptr,
+                                     0, nullptr, nullptr));
+            return out;
+        }
+        std::vector<zsw_alignment> vrec(n);
+        std::vector<uint32_t> vinc(2 * inc.size() + 64);
+        std::vector<uint8_t> vop(vinc.size());
+        uint64_t total = 0;
+        auto call = [&]() {
+            return zsw_annotate_batch(ctx_, &reads, flags, rec.data(), status.data(), inc.data(), op.data(), inc.size(), out.stats.data(), vrec.data(), vinc.data(),
+                                      vop.data(), (uint64_t)vinc.size(), &total, nullptr);
+        };
+        zsw_error e = call();
+        if (e == ZSW_ERR_INVALID_ARGUMENT && total > vinc.size()) {
+            vinc.resize(total);
+            vop.resize(total);
+            e = call();
+        }
+        check(e);
+        out.verbose = alns;
+        for (size_t i = 0; i < n; ++i) {
+            out.verbose[i].value.states.clear();
+            for (uint32_t k = 0; k < vrec[i].n_ciglets; ++k) out.verbose[i].value.states.push_back({vinc[vrec[i].ciglet_offset + k], vop[vrec[i].ciglet_offset + k]});
+        }
+        return out;
     }
 
   private:
@@ -229,6 +312,25 @@ class ProfileBatchBase {
     GpuContext& ctx_;
     std::vector<uint8_t> bases_;
     std::vector<uint64_t> offsets_;
+
+  public:
+    // zsw_annotate_batch over the alignments `alns` that one of this batch's alignment calls returned for `seq` (with the same
+    // seq_is_query): counts, sw_score_from_path and, with `verbose`, the = / X CIGARs. residues: a column matches when the index map
+    // sends both bytes to one residue (default: equal bytes, as the reference). strand: the strands of a strand-aware call, whose
+    // alignments are annotated against the reads as aligned (zsw_orient_batch).
+    Annotation annotate(const std::vector<MaybeAligned<Alignment>>& alns, const std::string& seq, bool seq_is_query = false, bool residues = false,
+                        bool verbose = true, const std::vector<uint8_t>* strand = nullptr) {
+        set_reference(seq);
+        zsw_batch b = batch();
+        std::vector<uint8_t> oriented;
+        if (strand) {
+            if (strand->size() != size()) throw GpuError(ZSW_ERR_INVALID_ARGUMENT, "one strand per read");
+            oriented.resize(bases_.size());
+            ctx_.check(zsw_orient_batch(ctx_.raw(), &b, strand->data(), oriented.data(), nullptr));
+            b.bases = oriented.data();
+        }
+        return ctx_.annotate(b, (seq_is_query ? ZSW_ANNOTATE_READ_IS_REF : 0) | (residues ? ZSW_ANNOTATE_MATCH_RESIDUES : 0), alns, verbose);
+    }
 };
 
 // `StripedProfile::<T, N, S>::new(read_i, &matrix, gap_open, gap_extend)` for every read of a batch (profile.rs:239-247).
@@ -490,6 +592,15 @@ class SharedProfileBase {
         return out;
     }
     GpuContext& ctx_;
+
+  public:
+    // zsw_annotate_batch over the alignments one of this profile's alignment calls returned for `reads` (with the same seq_is_query);
+    // results as ProfileBatchBase::annotate
+    Annotation annotate(const std::vector<MaybeAligned<Alignment>>& alns, const std::vector<std::string>& reads, bool seq_is_query = true, bool residues = false,
+                        bool verbose = true) {
+        const HostReads h = pack(reads);
+        return ctx_.annotate(h.batch(), ZSW_ANNOTATE_SHARED | (seq_is_query ? 0 : ZSW_ANNOTATE_READ_IS_REF) | (residues ? ZSW_ANNOTATE_MATCH_RESIDUES : 0), alns, verbose);
+    }
 };
 
 // `StripedProfile::<T, N, S>::new(sequence, ..)` once; sw_score / sw_score_ends / sw_score_ranges / sw_align against a batch of reads

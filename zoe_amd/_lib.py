@@ -53,7 +53,7 @@ SYMBOLS = [
     "zsw_group_set_reference", "zsw_group_score_batch_from", "zsw_group_score_batch_from_device", "zsw_group_align_batch_from",
     "zsw_group_align_3pass_batch_from",
     "zsw_set_complement", "zsw_score_strands_batch_from", "zsw_orient_batch", "zsw_align_3pass_strands_batch_from", "zsw_strand_counts", "zsw_debug_strand_records", "zsw_debug_score_launches",
-    "zsw_min_score_counts",
+    "zsw_min_score_counts", "zsw_annotate_batch",
 ]
 
 
@@ -80,6 +80,25 @@ class ZswAlignment(C.Structure):
         ("n_ciglets", C.c_uint32),
         ("ciglet_offset", C.c_uint64),
     ]
+
+
+class ZswAlignmentStats(C.Structure):
+    _fields_ = [
+        ("matches", C.c_uint32),
+        ("mismatches", C.c_uint32),
+        ("ins_bases", C.c_uint32),
+        ("del_bases", C.c_uint32),
+        ("ins_runs", C.c_uint32),
+        ("del_runs", C.c_uint32),
+        ("path_score", C.c_int32),
+        ("path_status", C.c_uint32),
+    ]
+
+
+# zsw_path_status and the flags of zsw_annotate_batch
+(PATH_OK, PATH_REFERENCE_ENDED, PATH_QUERY_ENDED, PATH_FULL_QUERY_NOT_USED, PATH_FULL_REFERENCE_NOT_USED, PATH_INVALID_CIGAR_OP, PATH_NEGATIVE_SCORE,
+ PATH_NO_ALIGNMENT, PATH_BAD_RECORD) = range(9)
+ANNOTATE_READ_IS_REF, ANNOTATE_SHARED, ANNOTATE_MATCH_RESIDUES = 1, 2, 4
 
 
 class ZswError(RuntimeError):
@@ -175,5 +194,6 @@ def load() -> C.CDLL:
     lib.zsw_debug_strand_records.argtypes = [vp, vp]
     lib.zsw_debug_score_launches.argtypes = [vp, u32p, C.c_uint32, u32p]
     lib.zsw_min_score_counts.argtypes = [vp, C.POINTER(C.c_uint64)]
+    lib.zsw_annotate_batch.argtypes = [vp, C.POINTER(ZswBatch), C.c_int, vp, u8p, u32p, u8p, C.c_uint64, vp, vp, u32p, u8p, C.c_uint64, C.POINTER(C.c_uint64), vp]
     _lib = lib
     return lib

@@ -562,11 +562,58 @@ class AlignmentBatch:
         return (st, int(r["score"]), (int(r["ref_start"]), int(r["ref_end"])), (int(r["query_start"]), int(r["query_end"])),
                 self.cigar(i), int(r["ref_len"]), int(r["query_len"]))
 
+    @staticmethod
+    def nm(stats: np.ndarray) -> np.ndarray:
+        """The NM tag of SAM per read, from the stats array of `annotate`: mismatches + inserted + deleted bases."""
+        return stats["mismatches"] + stats["ins_bases"] + stats["del_bases"]
+
 
 ALN_DTYPE = np.dtype(
     [("score", "<u4"), ("ref_start", "<u4"), ("ref_end", "<u4"), ("query_start", "<u4"), ("query_end", "<u4"),
      ("ref_len", "<u4"), ("query_len", "<u4"), ("n_ciglets", "<u4"), ("ciglet_offset", "<u8")]
 )
+
+
+# zsw_alignment_stats: what zsw_annotate_batch counts along one CIGAR (path_status: a _lib.PATH_* value)
+STATS_DTYPE = np.dtype([("matches", "<u4"), ("mismatches", "<u4"), ("ins_bases", "<u4"), ("del_bases", "<u4"), ("ins_runs", "<u4"), ("del_runs", "<u4"),
+                        ("path_score", "<i4"), ("path_status", "<u4")])
+
+
+def _annotate(ctx: "SwContext", rb: "ReadBatch", aln: AlignmentBatch, flags: int, verbose: bool):
+    """zsw_annotate_batch over the records of `aln` (host arrays: they are uploaded), with the context configured by the caller.
+    -> (the verbose AlignmentBatch or None, stats as STATS_DTYPE)"""
+    torch = _torch()
+    n, dev = rb.n_reads, rb.bases.device
+    if len(aln.status) != n:
+        raise ValueError("the alignments are not those of this batch of reads")
+    up = lambda a, dt: torch.from_numpy(np.ascontiguousarray(a).view(dt).reshape(-1).copy() if a.size else np.zeros(1, dtype=dt)).to(dev)
+    d_aln, d_status = up(aln.records, np.uint8), up(aln.status, np.uint8)
+    d_inc, d_op = up(aln.inc, np.int32), up(aln.op, np.uint8)
+    t_in = int(aln.inc.size)
+    stats = torch.zeros(max(n, 1) * STATS_DTYPE.itemsize, dtype=torch.uint8, device=dev)
+    b = rb.c_batch()
+    if not verbose:
+        ctx.check(ctx.lib.zsw_annotate_batch(ctx.h, C.byref(b), flags, d_aln.data_ptr(), d_status.data_ptr(), d_inc.data_ptr(), d_op.data_ptr(), t_in,
+                                             stats.data_ptr(), None, None, None, 0, None, ctx.stream()), profile_errors=False)
+        torch.cuda.synchronize(dev)
+        return None, _to_host(stats[: n * STATS_DTYPE.itemsize])[0].view(STATS_DTYPE)
+    out = torch.zeros(max(n, 1) * ALN_DTYPE.itemsize, dtype=torch.uint8, device=dev)
+    cap = max(2 * t_in, 64)
+    total = C.c_uint64(0)
+    while True:
+        inc = torch.empty(cap, dtype=torch.int32, device=dev)
+        op = torch.empty(cap, dtype=torch.uint8, device=dev)
+        rc = ctx.lib.zsw_annotate_batch(ctx.h, C.byref(b), flags, d_aln.data_ptr(), d_status.data_ptr(), d_inc.data_ptr(), d_op.data_ptr(), t_in,
+                                        stats.data_ptr(), out.data_ptr(), inc.data_ptr(), op.data_ptr(), cap, C.byref(total), ctx.stream())
+        if rc == -1 and total.value > cap:
+            cap = int(total.value)
+            continue
+        ctx.check(rc, profile_errors=False)
+        break
+    torch.cuda.synchronize(dev)
+    t = int(total.value)
+    h_stats, h_out, h_inc, h_op = _to_host(stats[: n * STATS_DTYPE.itemsize], out[: n * ALN_DTYPE.itemsize], inc[:t], op[:t])
+    return AlignmentBatch(aln.status, h_out.view(ALN_DTYPE), h_inc.view(np.uint32), h_op, aln.tier, aln.strand), h_stats.view(STATS_DTYPE)
 
 
 def _to_host(*tensors):
@@ -645,6 +692,20 @@ class _ProfileBatchBase:
         if strands:
             out.strand = _to_host(strand[:n])[0]
         return out
+
+
+    def annotate(self, aln: AlignmentBatch, seq: SeqSrc, residues: bool = False, verbose: bool = True):
+        """zsw_annotate_batch over the alignments `aln` that one of this batch's alignment calls returned for `seq` (the same
+        SeqSrc): -> (the AlignmentBatch of `Alignment::to_verbose_sequence_matching`, M split into = / X, or None without `verbose`;
+        a STATS_DTYPE array: matches, mismatches, gap bases and runs, `sw_score_from_path` and its status per read).
+        residues: a column matches when the index map sends both bytes to one residue (default: equal bytes, as the reference).
+        Alignments of a strand-aware call are annotated against the reads as aligned (strand 1: the reverse complement)."""
+        self._prep(seq.seq)
+        reads = self.reads
+        if aln.strand is not None:
+            reads = self.ctx.orient(reads, _torch().from_numpy(np.ascontiguousarray(aln.strand, dtype=np.uint8)).to(reads.bases.device))
+        flags = (_lib.ANNOTATE_READ_IS_REF if seq.is_query else 0) | (_lib.ANNOTATE_MATCH_RESIDUES if residues else 0)
+        return _annotate(self.ctx, reads, aln, flags, verbose)
 
 
 class StripedProfileBatch(_ProfileBatchBase):
@@ -986,6 +1047,16 @@ class _SharedBase:
         t = int(total.value)
         h_aln, h_status, h_inc, h_op, h_tier = _to_host(aln[: n * ALN_DTYPE.itemsize], status[:n], inc[:t], op[:t], tier[:n])
         return AlignmentBatch(h_status, h_aln.view(ALN_DTYPE), h_inc.view(np.uint32), h_op, h_tier if direct is None else None)
+
+
+    def annotate(self, aln: AlignmentBatch, seq, residues: bool = False, verbose: bool = True):
+        """zsw_annotate_batch over the alignments `aln` that one of this profile's alignment calls returned for `seq` (the same reads,
+        or the same SeqBatchSrc); results as `_ProfileBatchBase.annotate`."""
+        reads, is_query = self._reads_of(seq)
+        rb = _as_batch(reads, self.device)
+        self._prep()
+        flags = _lib.ANNOTATE_SHARED | (0 if is_query else _lib.ANNOTATE_READ_IS_REF) | (_lib.ANNOTATE_MATCH_RESIDUES if residues else 0)
+        return _annotate(self.ctx, rb, aln, flags, verbose)
 
 
 @dataclass

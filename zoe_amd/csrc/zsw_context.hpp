@@ -111,6 +111,8 @@ struct zsw_context {
     zsw::DevBuf st_ws[24];
     std::vector<uint8_t> h_orient;
     int32_t* strand_dbg = nullptr;  // zsw_debug_strand_records
+    // zsw_annotate_batch (zsw_annotate.hip): the staged arrays of a host call, the verbose ciglet counts and their exclusive sum
+    zsw::DevBuf an_ws[16];
 };
 
 namespace zsw {

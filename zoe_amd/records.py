@@ -2,7 +2,8 @@
 
 Mirrors, for exactly what the path needs:
     FastQReader            src/data/records/fastq/reader.rs:17-187 (single-line FASTQ; same validation and messages)
-    SamData::from_alignment src/data/records/sam/mod.rs:223-245   (POS = ref_range.start + 1, CIGAR = states, AS:i = score)
+    SamData::from_alignment src/data/records/sam/mod.rs:223-245   (POS = ref_range.start + 1, CIGAR = states, AS:i = score;
+                            with the stats of `annotate` also NM:i = mismatches + inserted + deleted bases)
     Display for SamData     src/data/records/sam/std_traits.rs:3-44 (tab-separated, optional fields appended)
 """
 from __future__ import annotations
@@ -110,10 +111,14 @@ class SamData:
     opt_fields: List[str] = field(default_factory=list)
 
     @staticmethod
-    def from_alignment(aln: AlignmentBatch, i: int, qname: str, flag: int, rname: str, mapq: int, seq: bytes, qual: bytes) -> "SamData":
-        """sam/mod.rs:223-245: both SAM and Alignment exclude clipped bases from positions; only the 1-based shift remains."""
+    def from_alignment(aln: AlignmentBatch, i: int, qname: str, flag: int, rname: str, mapq: int, seq: bytes, qual: bytes, stats=None) -> "SamData":
+        """sam/mod.rs:223-245: both SAM and Alignment exclude clipped bases from positions; only the 1-based shift remains.
+        stats: the stats array of `annotate` for this batch; appends NM:i:."""
         r = aln.records[i]
-        return SamData(qname, flag, rname, int(r["ref_start"]) + 1, mapq, aln.cigar(i), "*", 0, 0, seq, qual, [f"AS:i:{int(r['score'])}"])
+        opt = [f"AS:i:{int(r['score'])}"]
+        if stats is not None:
+            opt.append(f"NM:i:{int(AlignmentBatch.nm(stats[i:i + 1])[0])}")
+        return SamData(qname, flag, rname, int(r["ref_start"]) + 1, mapq, aln.cigar(i), "*", 0, 0, seq, qual, opt)
 
     @staticmethod
     def unmapped(qname: str, seq: bytes, qual: bytes) -> "SamData":
@@ -127,16 +132,25 @@ class SamData:
 
 
 def align_fastq_to_sam(records: List[FastQ], reference: bytes, rname: str, matrix, gap_open: int, gap_extend: int,
-                       device: int = 0) -> List[SamData]:
-    """FASTQ records -> `into_local_profile(..).sw_align_from_i8(SeqSrc::Reference(reference))` on the GPU -> SAM records."""
+                       device: int = 0, nm: bool = False, verbose_cigar: bool = False, three_pass: bool = False) -> List[SamData]:
+    """FASTQ records -> `into_local_profile(..).sw_align_from_i8(SeqSrc::Reference(reference))` on the GPU -> SAM records
+    (three_pass: `sw_align_from_i8_3pass`). nm: NM:i: on every mapped record; verbose_cigar: = / X in place of M — both from one
+    `annotate` pass over the alignments."""
     from .alignment import SeqSrc, into_local_profile
 
     qnames = [r.header.split()[0] if r.header.split() else r.header for r in records]
-    aln = into_local_profile(batch_from_fastq(records, device), matrix, gap_open, gap_extend, device).sw_align_from_i8(SeqSrc.Reference(reference))
+    profiles = into_local_profile(batch_from_fastq(records, device), matrix, gap_open, gap_extend, device)
+    src = SeqSrc.Reference(reference)
+    aln = profiles.sw_align_from_i8_3pass(src) if three_pass else profiles.sw_align_from_i8(src)
+    stats = None
+    if nm or verbose_cigar:
+        verbose, stats = profiles.annotate(aln, src, verbose=verbose_cigar)
+        aln = verbose if verbose_cigar else aln
+        stats = stats if nm else None
     out = []
     for i, r in enumerate(records):
         if int(aln.status[i]) == SOME:
-            out.append(SamData.from_alignment(aln, i, qnames[i], 0, rname, 255, r.sequence, r.quality))
+            out.append(SamData.from_alignment(aln, i, qnames[i], 0, rname, 255, r.sequence, r.quality, stats))
         else:
             out.append(SamData.unmapped(qnames[i], r.sequence, r.quality))
     return out
