@@ -105,6 +105,22 @@ pub const ZSW_ANNOTATE_READ_IS_REF: i32 = 1;
 pub const ZSW_ANNOTATE_SHARED: i32 = 2;
 pub const ZSW_ANNOTATE_MATCH_RESIDUES: i32 = 4;
 
+/// `zsw_sam_fields`: what a SAM line holds beside the record (`zsw_sam_batch`); every array lives where the batch does, but `rname`
+#[repr(C)]
+#[derive(Clone, Copy, Debug)]
+pub struct ZswSamFields {
+    pub qnames:        *const u8,
+    pub qname_offsets: *const u64,
+    pub quals:         *const u8,
+    pub strand:        *const u8,
+    pub stats:         *const c_void,
+    pub rname:         *const c_char,
+    pub rname_len:     u32,
+    pub mapq:          u32,
+}
+/// flag of `zsw_sam_batch`: SEQ `*` on every line
+pub const ZSW_SAM_OMIT_SEQ: i32 = 1;
+
 pub const ZSW_OK: i32 = 0;
 pub const ZSW_MEM_HOST: i32 = 0;
 pub const ZSW_ENCODING_BYTES: i32 = 0;
@@ -197,6 +213,7 @@ unsafe extern "C" {
     fn zsw_set_option(ctx: *mut ZswContext, option: i32, value: i64) -> i32;
     fn zsw_min_score_counts(ctx: *mut ZswContext, out: *mut u64) -> i32;
     fn zsw_annotate_batch(ctx: *mut ZswContext, reads: *const ZswBatch, flags: i32, aln: *const ZswAlignment, status: *const u8, inc: *const u32, op: *const u8, n_ciglets: u64, out_stats: *mut c_void, out_aln: *mut ZswAlignment, out_inc: *mut u32, out_op: *mut u8, ciglet_cap: u64, out_n_ciglets: *mut u64, stream: *mut c_void) -> i32;
+    fn zsw_sam_batch(ctx: *mut ZswContext, reads: *const ZswBatch, fields: *const c_void, flags: i32, aln: *const ZswAlignment, status: *const u8, inc: *const u32, op: *const u8, n_ciglets: u64, out_text: *mut u8, text_cap: u64, out_n_bytes: *mut u64, out_line_offsets: *mut u64, out_n_bad: *mut u64, stream: *mut c_void) -> i32;
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -831,6 +848,57 @@ impl GpuContext {
             oop.truncate(needed as usize);
             return Ok((stats, Some((out, oinc, oop))));
         }
+    }
+
+    /// `zsw_sam_batch`: the SAM body for the raw records of an alignment call (or of `annotate_batch`), one line per read — what
+    /// `SamData::from_alignment(..)` / `SamData::unmapped(..)` followed by `Display` print — formatted on the GPU. `reads`: the
+    /// reads as aligned (for a strand-aware call: `orient_batch`); `quals`: one slice per read, of the read's length; `strand` and
+    /// `stats` (for `NM:i:`) are optional. -> (the text, the number of malformed records, which were written as unmapped lines).
+    #[allow(clippy::too_many_arguments)]
+    pub fn sam_batch<Q: AsRef<[u8]>, N: AsRef<[u8]>>(
+        &self, reads: &[Q], qnames: &[N], quals: Option<&[Q]>, rname: &str, mapq: u8, strand: Option<&[u8]>, stats: Option<&[ZswAlignmentStats]>, omit_seq: bool,
+        recs: &[ZswAlignment], status: &[u8], inc: &[u32], op: &[u8],
+    ) -> Result<(Vec<u8>, u64), GpuError> {
+        let n = reads.len();
+        assert!(qnames.len() == n && recs.len() == n && status.len() == n && inc.len() == op.len());
+        assert!(strand.map_or(true, |s| s.len() == n) && stats.map_or(true, |s| s.len() == n));
+        assert!(!rname.is_empty() && rname.len() <= 255);
+        let batch = HostBatch::new(reads);
+        let names = HostBatch::new(qnames);
+        let qual_batch = quals.map(|q| {
+            assert!(q.len() == n && q.iter().zip(reads).all(|(q, r)| q.as_ref().len() == r.as_ref().len()));
+            HostBatch::new(q)
+        });
+        let fields = ZswSamFields {
+            qnames:        names.bases.as_ptr(),
+            qname_offsets: names.offsets.as_ptr(),
+            quals:         qual_batch.as_ref().map_or(ptr::null(), |q| q.bases.as_ptr()),
+            strand:        strand.map_or(ptr::null(), |s| s.as_ptr()),
+            stats:         stats.map_or(ptr::null(), |s| s.as_ptr().cast::<c_void>()),
+            rname:         rname.as_ptr().cast::<c_char>(),
+            rname_len:     rname.len() as u32,
+            mapq:          u32::from(mapq),
+        };
+        let c = batch.as_c();
+        let flags = if omit_seq { ZSW_SAM_OMIT_SEQ } else { 0 };
+        let fields_ptr = (&fields as *const ZswSamFields).cast::<c_void>();
+        let (mut total, mut n_bad) = (0u64, 0u64);
+        // SAFETY: the sizing call writes the two counters only
+        let code = unsafe {
+            zsw_sam_batch(self.raw, &c, fields_ptr, flags, recs.as_ptr(), status.as_ptr(), inc.as_ptr(), op.as_ptr(), inc.len() as u64, ptr::null_mut(), 0, &mut total,
+                          ptr::null_mut(), &mut n_bad, ptr::null_mut())
+        };
+        self.check(code, 0, 0)?;
+        let mut text = vec![0u8; total as usize];
+        if total > 0 {
+            // SAFETY: text holds the bytes the sizing call asked for
+            let code = unsafe {
+                zsw_sam_batch(self.raw, &c, fields_ptr, flags, recs.as_ptr(), status.as_ptr(), inc.as_ptr(), op.as_ptr(), inc.len() as u64, text.as_mut_ptr(), total,
+                              &mut total, ptr::null_mut(), &mut n_bad, ptr::null_mut())
+            };
+            self.check(code, 0, 0)?;
+        }
+        Ok((text, n_bad))
     }
 
     /// Per read: `profiles.sw_align_from_i{from_width}_3pass(seq)` of the read or of its reverse complement, whichever scores

@@ -4,7 +4,7 @@
 // POS = ref_range.start + 1, CIGAR = states, AS:i = score.
 //
 //   g++ -O2 -std=c++17 -Iinclude examples/zsw_driver.cpp -o examples/zsw_driver -Lzoe_amd -lzoe_sw_hip -Wl,-rpath,$PWD/zoe_amd
-//   ./examples/zsw_driver reference.txt reads.fastq [--score-only | --3pass | --both-strands] [--min-score T] [--nm] [--verbose-cigar]
+//   ./examples/zsw_driver reference.txt reads.fastq [--score-only | --3pass | --both-strands] [--min-score T] [--nm] [--verbose-cigar] [--device-sam]
 // --both-strands: every read is aligned on whichever strand scores higher (sw_align_strands_from_i8_3pass); a read answered by
 // its reverse complement gets flag 16, SEQ reverse complemented and QUAL reversed, and POS / CIGAR are those of that sequence.
 // --min-score T (with --3pass or --score-only, the calls ZSW_OPTION_MIN_SCORE covers): a read that scores less than T is written as
@@ -12,7 +12,10 @@
 // --nm appends NM:i: (mismatches + inserted + deleted bases) to every mapped record, --verbose-cigar writes the CIGAR with = / X in
 // place of M (Alignment::to_verbose_sequence_matching); both come from one zsw_annotate_batch pass over the alignments. Without them
 // the output is what it always was.
+// --device-sam: the records are formatted on the GPU (zsw_sam_batch) and the body is written with one fwrite; the same bytes as
+// without it, under every option above. Without the flag neither the output nor the code path changes.
 #include <algorithm>
+#include <cstdio>
 #include <cstdlib>
 #include <cstring>
 #include <fstream>
@@ -40,10 +43,10 @@ static std::string read_reference(const std::string& path, std::string* name) {
 
 int main(int argc, char** argv) {
     if (argc < 3) {
-        std::cerr << "usage: zsw_driver reference.(fa|txt) reads.fastq [--score-only | --3pass | --both-strands] [--min-score T] [--nm] [--verbose-cigar]\n";
+        std::cerr << "usage: zsw_driver reference.(fa|txt) reads.fastq [--score-only | --3pass | --both-strands] [--min-score T] [--nm] [--verbose-cigar] [--device-sam]\n";
         return 2;
     }
-    bool score_only = false, three_pass = false, both_strands = false, nm = false, verbose_cigar = false;
+    bool score_only = false, three_pass = false, both_strands = false, nm = false, verbose_cigar = false, device_sam = false;
     long long min_score = 0;
     for (int k = 3; k < argc; ++k) {
         if (!std::strcmp(argv[k], "--score-only")) score_only = true;
@@ -52,6 +55,7 @@ int main(int argc, char** argv) {
         else if (!std::strcmp(argv[k], "--min-score") && k + 1 < argc) min_score = std::atoll(argv[++k]);
         else if (!std::strcmp(argv[k], "--nm")) nm = true;
         else if (!std::strcmp(argv[k], "--verbose-cigar")) verbose_cigar = true;
+        else if (!std::strcmp(argv[k], "--device-sam")) device_sam = true;
         else {
             std::cerr << "zsw_driver: unknown argument " << argv[k] << '\n';
             return 2;
@@ -89,6 +93,13 @@ int main(int argc, char** argv) {
                                  : profiles.sw_align_from_i8(reference);
         zoe::Annotation ann;  // NM and = / X CIGARs: one pass over the alignments, against the reads as aligned
         if (nm || verbose_cigar) ann = profiles.annotate(alns, reference, false, false, verbose_cigar, both_strands ? &profiles.last_strands() : nullptr);
+        if (device_sam) {  // the body from zsw_sam_batch: SEQ oriented, QUAL reversed and the decimals written on the device
+            std::cout << "@HD\tVN:1.6\n@SQ\tSN:" << ref_name << "\tLN:" << reference.size() << '\n' << std::flush;
+            const std::string text = profiles.sam_text(verbose_cigar ? ann.verbose : alns, names, quals, ref_name, 255, both_strands ? &profiles.last_strands() : nullptr,
+                                                       nm ? &ann : nullptr);
+            std::fwrite(text.data(), 1, text.size(), stdout);
+            return 0;
+        }
         std::vector<uint8_t> strand(reads.size(), 0);
         if (both_strands) {  // SEQ and QUAL as aligned: the reverse complement of a read answered on the reverse strand, its qualities reversed
             strand = profiles.last_strands();

@@ -340,6 +340,53 @@ zsw_error zsw_annotate_batch(zsw_context* ctx, const zsw_batch* reads, int flags
                              zsw_alignment* out_aln, uint32_t* out_inc, uint8_t* out_op, uint64_t ciglet_cap, uint64_t* out_n_ciglets,
                              void* stream);
 
+/* ---- SAM records formatted on the device ------------------------------------------------------------ */
+/* The text SamData::from_alignment (src/data/records/sam/mod.rs:223-245) followed by Display for SamData
+ * (records/sam/std_traits.rs:3-44) print for every read of a batch, in read order, one line per read, each closed by '\n':
+ *   status[i] == ZSW_STATUS_SOME:  QNAME FLAG RNAME POS MAPQ CIGAR * 0 0 SEQ QUAL AS:i:score [NM:i:nm]
+ *   any other status:              QNAME 4    *     0   0    *     * 0 0 SEQ QUAL
+ * tab-separated. FLAG is 0, or 16 where strand[i] != 0; POS = ref_start + 1; CIGAR is the decimal inc and the op byte of each of the
+ * record's ciglets in order, `*` for a record without ciglets (Display for Cigar, cigar/mod.rs:146-158); NM = mismatches + ins_bases
+ * + del_bases of stats[i], appended where `stats` is given. POS and NM are 64-bit sums. SEQ is the read's bytes as they stand in
+ * `reads` — for the records of a strand-aware call that is the oriented batch of zsw_orient_batch, as for zsw_annotate_batch —, QUAL
+ * its quality bytes, back to front where strand[i] != 0; a read of length 0 has `*` for both (is_missing_sam_field, sam/mod.rs:425-428).
+ * No byte of a name, a base or a quality is looked at or escaped. The @HD / @SQ header is the caller's.
+ * The call formats whatever records it is given — those of an alignment call, or out_aln / out_inc / out_op of zsw_annotate_batch (the
+ * = / X CIGAR) — and reads neither reference nor scoring: a context is all it needs (ctx == NULL: ZSW_ERR_NOT_CONFIGURED). Records
+ * are caller memory. A ZSW_STATUS_SOME record whose ciglets leave [0, n_ciglets) (64-bit, checked before any ciglet load), or with an
+ * inc of 0 or an op outside MIDNSHP=X, is written as an unmapped line and counted in *out_n_bad: a count, never a fault. For device
+ * arrays a name (or a read) whose end offset lies in front of its start has length 0; host offsets, of the reads or of the names,
+ * that go backwards are ZSW_ERR_INVALID_ARGUMENT.
+ * Capacity protocol of the alignment calls: *out_n_bytes always receives the total; beyond text_cap the call returns
+ * ZSW_ERR_INVALID_ARGUMENT having written out_line_offsets and no byte of out_text; out_text == NULL with text_cap == 0 is the
+ * sizing call (ZSW_OK; the length launch and the scan only). No byte at or beyond out_text[total] is written. out_line_offsets
+ * (optional, n_reads + 1 entries): line i = out_text[off[i], off[i + 1]). Every array lives where reads->mem says, but for
+ * fields->rname, out_n_bytes and out_n_bad (host). Three steps — a length launch, an exclusive sum, a write launch — with no atomic
+ * deciding a place: the text is the same on every run. Host batches are staged and the call is synchronous; device batches
+ * synchronise the stream once, for the total and the count. Workspace, kept by the context until zsw_destroy: 17 bytes per read, and
+ * the staged arrays and the text of a host batch.
+ * Unknown flag bits, mapq > 255, rname_len outside 1..255, a null required pointer (reads, fields, rname, aln, status, out_n_bytes,
+ * out_n_bad; bases unless ZSW_SAM_OMIT_SEQ with quals == NULL; inc / op with n_ciglets; qname_offsets with qnames), or an output array
+ * that overlaps an input or the other output: ZSW_ERR_INVALID_ARGUMENT, nothing written. ZSW_ENCODING_PACKED4: ZSW_ERR_UNSUPPORTED.
+ * ZSW_OPTION_MIN_SCORE and ZSW_OPTION_EXACT_PRUNING do not matter here (a ZSW_STATUS_BELOW_MIN_SCORE read is an unmapped line);
+ * zsw_group_* does not cover the call. Lanes per line, lines per block and the LDS cap of a line: zoe_amd/csrc/zsw_sam.hpp. */
+typedef struct zsw_sam_fields {        /* zero-initialise; every device/host array lives where reads->mem says */
+    const uint8_t*  qnames;            /* QNAME bytes of all reads, back to back; NULL: every QNAME is "*" */
+    const uint64_t* qname_offsets;     /* n_reads + 1 entries; name i = qnames[off[i], off[i+1]) */
+    const uint8_t*  quals;             /* laid out exactly as reads->bases (fixed_len or reads->offsets); NULL: QUAL "*" */
+    const uint8_t*  strand;            /* optional, n_reads: != 0 -> FLAG 16 and QUAL written back to front */
+    const void*     stats;             /* optional, n_reads zsw_alignment_stats: appends NM:i: to mapped lines */
+    const char*     rname;             /* HOST memory always; rname_len bytes, 1..255 */
+    uint32_t        rname_len;
+    uint32_t        mapq;              /* 0..255, written on mapped lines (the driver uses 255) */
+} zsw_sam_fields;
+enum { ZSW_SAM_OMIT_SEQ = 1 };         /* SEQ "*" on every line (with quals == NULL the text carries no per-base bytes) */
+/* fields: a zsw_sam_fields (declared const void*, as out_stats above: a zsw_sam_fields* converts without a cast) */
+zsw_error zsw_sam_batch(zsw_context* ctx, const zsw_batch* reads, const void* fields, int flags, const zsw_alignment* aln,
+                        const uint8_t* status, const uint32_t* inc, const uint8_t* op, uint64_t n_ciglets, uint8_t* out_text,
+                        uint64_t text_cap, uint64_t* out_n_bytes, uint64_t* out_line_offsets /* optional, n_reads + 1 */,
+                        uint64_t* out_n_bad, void* stream);
+
 /* ---- pre-alignment filter ------------------------------------------------------------------ */
 /* out_pass[i] = sneaky_snake(&reference[ref_start[i] .. ref_start[i]+ref_len[i]], read_i, threshold)
  * (src/alignment/sneaky_snake.rs:78-131): the SneakySnake edit-distance filter between a read and a candidate window of the

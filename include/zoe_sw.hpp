@@ -187,21 +187,11 @@ class GpuContext {
     Annotation annotate(const zsw_batch& reads, int flags, const std::vector<MaybeAligned<Alignment>>& alns, bool verbose) const {
         const size_t n = alns.size();
         if (n != reads.n_reads) throw GpuError(ZSW_ERR_INVALID_ARGUMENT, "one alignment per read");
-        std::vector<zsw_alignment> rec(n);
-        std::vector<uint8_t> status(n);
+        std::vector<zsw_alignment> rec;
+        std::vector<uint8_t> status;
         std::vector<uint32_t> inc;
         std::vector<uint8_t> op;
-        for (size_t i = 0; i < n; ++i) {
-            const Alignment& a = alns[i].value;
-            status[i] = (uint8_t)alns[i].status;
-            rec[i] = zsw_alignment{a.score, (uint32_t)a.ref_start, (uint32_t)a.ref_end, (uint32_t)a.query_start, (uint32_t)a.query_end, (uint32_t)a.ref_len,
-                                   (uint32_t)a.query_len, (uint32_t)a.states.size(), (uint64_t)inc.size()};
-            for (const Ciglet& c : a.states) {
-                if (c.inc > 0xffffffffull) throw GpuError(ZSW_ERR_INVALID_ARGUMENT, "a ciglet beyond 32 bits");
-                inc.push_back((uint32_t)c.inc);
-                op.push_back(c.op);
-            }
-        }
+        flatten(alns, rec, status, inc, op);
         Annotation out;
         out.stats.resize(n);
         if (!verbose) {
@@ -231,8 +221,43 @@ class GpuContext {
         }
         return out;
     }
+    // zsw_sam_batch over alignments that a call on `reads` (a host batch: the reads as aligned) returned: the SAM body, one line per
+    // read, formatted on the GPU. fields: names, qualities, strands, stats, RNAME and MAPQ as the C ABI takes them (host arrays).
+    std::string sam_text(const zsw_batch& reads, const zsw_sam_fields& fields, int flags, const std::vector<MaybeAligned<Alignment>>& alns) const {
+        if (alns.size() != reads.n_reads) throw GpuError(ZSW_ERR_INVALID_ARGUMENT, "one alignment per read");
+        std::vector<zsw_alignment> rec;
+        std::vector<uint8_t> status;
+        std::vector<uint32_t> inc;
+        std::vector<uint8_t> op;
+        flatten(alns, rec, status, inc, op);
+        uint64_t total = 0, n_bad = 0;
+        check(zsw_sam_batch(ctx_, &reads, &fields, flags, rec.data(), status.data(), inc.data(), op.data(), inc.size(), nullptr, 0, &total, nullptr, &n_bad, nullptr));
+        std::string text(total, '\0');
+        if (total)
+            check(zsw_sam_batch(ctx_, &reads, &fields, flags, rec.data(), status.data(), inc.data(), op.data(), inc.size(), (uint8_t*)&text[0], total, &total, nullptr,
+                                &n_bad, nullptr));
+        return text;
+    }
 
   private:
+    // Alignments -> the records and ciglet arrays of the C ABI
+    static void flatten(const std::vector<MaybeAligned<Alignment>>& alns, std::vector<zsw_alignment>& rec, std::vector<uint8_t>& status, std::vector<uint32_t>& inc,
+                        std::vector<uint8_t>& op) {
+        const size_t n = alns.size();
+        rec.resize(n);
+        status.resize(n);
+        for (size_t i = 0; i < n; ++i) {
+            const Alignment& a = alns[i].value;
+            status[i] = (uint8_t)alns[i].status;
+            rec[i] = zsw_alignment{a.score, (uint32_t)a.ref_start, (uint32_t)a.ref_end, (uint32_t)a.query_start, (uint32_t)a.query_end, (uint32_t)a.ref_len,
+                                   (uint32_t)a.query_len, (uint32_t)a.states.size(), (uint64_t)inc.size()};
+            for (const Ciglet& c : a.states) {
+                if (c.inc > 0xffffffffull) throw GpuError(ZSW_ERR_INVALID_ARGUMENT, "a ciglet beyond 32 bits");
+                inc.push_back((uint32_t)c.inc);
+                op.push_back(c.op);
+            }
+        }
+    }
     zsw_context* ctx_ = nullptr;
 };
 
@@ -330,6 +355,52 @@ class ProfileBatchBase {
             b.bases = oriented.data();
         }
         return ctx_.annotate(b, (seq_is_query ? ZSW_ANNOTATE_READ_IS_REF : 0) | (residues ? ZSW_ANNOTATE_MATCH_RESIDUES : 0), alns, verbose);
+    }
+    // zsw_sam_batch: the SAM body for the alignments `alns` of this batch (those of an alignment call, or Annotation::verbose for
+    // = / X CIGARs), one line per read in read order, as `SamData::from_alignment(..)` / `SamData::unmapped(..)` print them — without
+    // the @HD / @SQ header. names: QNAME per read (empty vector: "*"); quals: the qualities as read, one string of the read's length
+    // per read (empty vector: "*"); strands: of a strand-aware call — FLAG 16, SEQ reverse complemented (zsw_orient_batch) and QUAL
+    // reversed for strand 1; annotation: its stats give NM:i: on mapped lines; omit_seq: SEQ "*".
+    std::string sam_text(const std::vector<MaybeAligned<Alignment>>& alns, const std::vector<std::string>& names, const std::vector<std::string>& quals,
+                         const std::string& rname, uint32_t mapq = 255, const std::vector<uint8_t>* strands = nullptr, const Annotation* annotation = nullptr,
+                         bool omit_seq = false) {
+        const size_t n = size();
+        if ((!names.empty() && names.size() != n) || (!quals.empty() && quals.size() != n) || (strands && strands->size() != n) ||
+            (annotation && annotation->stats.size() != n))
+            throw GpuError(ZSW_ERR_INVALID_ARGUMENT, "one name, quality string, strand and stats entry per read");
+        zsw_batch b = batch();
+        std::vector<uint8_t> oriented, name_bytes, qual_bytes;
+        std::vector<uint64_t> name_offsets;
+        if (strands) {
+            oriented.resize(bases_.size());
+            ctx_.check(zsw_orient_batch(ctx_.raw(), &b, strands->data(), oriented.data(), nullptr));
+            b.bases = oriented.data();
+        }
+        zsw_sam_fields f{};
+        if (!names.empty()) {
+            name_offsets.push_back(0);
+            for (auto& s : names) {
+                name_bytes.insert(name_bytes.end(), s.begin(), s.end());
+                name_offsets.push_back(name_bytes.size());
+            }
+            name_bytes.push_back(0);  // a valid pointer when every name is empty
+            f.qnames = name_bytes.data();
+            f.qname_offsets = name_offsets.data();
+        }
+        if (!quals.empty()) {
+            qual_bytes.reserve(bases_.size());
+            for (size_t i = 0; i < n; ++i) {
+                if (quals[i].size() != offsets_[i + 1] - offsets_[i]) throw GpuError(ZSW_ERR_INVALID_ARGUMENT, "a quality string is as long as its read");
+                qual_bytes.insert(qual_bytes.end(), quals[i].begin(), quals[i].end());
+            }
+            f.quals = qual_bytes.data();
+        }
+        f.strand = strands ? strands->data() : nullptr;
+        f.stats = annotation ? annotation->stats.data() : nullptr;
+        f.rname = rname.data();
+        f.rname_len = (uint32_t)rname.size();
+        f.mapq = mapq;
+        return ctx_.sam_text(b, f, omit_seq ? ZSW_SAM_OMIT_SEQ : 0, alns);
     }
 };
 

@@ -53,7 +53,7 @@ SYMBOLS = [
     "zsw_group_set_reference", "zsw_group_score_batch_from", "zsw_group_score_batch_from_device", "zsw_group_align_batch_from",
     "zsw_group_align_3pass_batch_from",
     "zsw_set_complement", "zsw_score_strands_batch_from", "zsw_orient_batch", "zsw_align_3pass_strands_batch_from", "zsw_strand_counts", "zsw_debug_strand_records", "zsw_debug_score_launches",
-    "zsw_min_score_counts", "zsw_annotate_batch",
+    "zsw_min_score_counts", "zsw_annotate_batch", "zsw_sam_batch",
 ]
 
 
@@ -99,6 +99,23 @@ class ZswAlignmentStats(C.Structure):
 (PATH_OK, PATH_REFERENCE_ENDED, PATH_QUERY_ENDED, PATH_FULL_QUERY_NOT_USED, PATH_FULL_REFERENCE_NOT_USED, PATH_INVALID_CIGAR_OP, PATH_NEGATIVE_SCORE,
  PATH_NO_ALIGNMENT, PATH_BAD_RECORD) = range(9)
 ANNOTATE_READ_IS_REF, ANNOTATE_SHARED, ANNOTATE_MATCH_RESIDUES = 1, 2, 4
+
+
+class ZswSamFields(C.Structure):
+    """zsw_sam_fields: what a SAM line holds beside the record; every array lives where the batch does, but rname (host)"""
+    _fields_ = [
+        ("qnames", C.c_void_p),
+        ("qname_offsets", C.c_void_p),
+        ("quals", C.c_void_p),
+        ("strand", C.c_void_p),
+        ("stats", C.c_void_p),
+        ("rname", C.c_char_p),
+        ("rname_len", C.c_uint32),
+        ("mapq", C.c_uint32),
+    ]
+
+
+SAM_OMIT_SEQ = 1
 
 
 class ZswError(RuntimeError):
@@ -195,5 +212,7 @@ def load() -> C.CDLL:
     lib.zsw_debug_score_launches.argtypes = [vp, u32p, C.c_uint32, u32p]
     lib.zsw_min_score_counts.argtypes = [vp, C.POINTER(C.c_uint64)]
     lib.zsw_annotate_batch.argtypes = [vp, C.POINTER(ZswBatch), C.c_int, vp, u8p, u32p, u8p, C.c_uint64, vp, vp, u32p, u8p, C.c_uint64, C.POINTER(C.c_uint64), vp]
+    lib.zsw_sam_batch.argtypes = [vp, C.POINTER(ZswBatch), C.POINTER(ZswSamFields), C.c_int, vp, u8p, u32p, u8p, C.c_uint64, u8p, C.c_uint64, C.POINTER(C.c_uint64),
+                                  u64p, C.POINTER(C.c_uint64), vp]
     _lib = lib
     return lib

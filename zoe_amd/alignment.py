@@ -616,6 +616,72 @@ def _annotate(ctx: "SwContext", rb: "ReadBatch", aln: AlignmentBatch, flags: int
     return AlignmentBatch(aln.status, h_out.view(ALN_DTYPE), h_inc.view(np.uint32), h_op, aln.tier, aln.strand), h_stats.view(STATS_DTYPE)
 
 
+def _sam_text(ctx: "SwContext", rb: "ReadBatch", aln: AlignmentBatch, qnames, quals, rname, mapq: int, strands, stats, omit_seq: bool, device_out: bool):
+    """zsw_sam_batch over the records of `aln` (host arrays: they are uploaded) beside the reads `rb` as aligned.
+    -> bytes, or with device_out (a CUDA uint8 tensor with the text, a CUDA int64 tensor with the n + 1 line offsets)"""
+    torch = _torch()
+    n, dev = rb.n_reads, rb.bases.device
+    if len(aln.status) != n:
+        raise ValueError("the alignments are not those of this batch of reads")
+    up = lambda a, dt: torch.from_numpy(np.ascontiguousarray(a).view(dt).reshape(-1).copy() if a.size else np.zeros(1, dtype=dt)).to(dev)
+    d_aln, d_status = up(aln.records, np.uint8), up(aln.status, np.uint8)
+    d_inc, d_op = up(aln.inc, np.int32), up(aln.op, np.uint8)
+    keep = [d_aln, d_status, d_inc, d_op]
+    f = _lib.ZswSamFields()
+    if qnames is not None:
+        names = [q.encode() if isinstance(q, str) else bytes(q) for q in qnames]
+        if len(names) != n:
+            raise ValueError("one QNAME per read")
+        off = np.zeros(n + 1, dtype=np.int64)
+        np.cumsum([len(q) for q in names], out=off[1:])
+        d_names, d_noff = up(np.frombuffer(b"".join(names), dtype=np.uint8), np.uint8), up(off, np.int64)
+        keep += [d_names, d_noff]
+        f.qnames, f.qname_offsets = d_names.data_ptr(), d_noff.data_ptr()
+    if quals is not None:
+        if isinstance(quals, torch.Tensor):  # laid out as the reads' bases
+            d_quals = quals.contiguous()
+            if not d_quals.is_cuda or d_quals.dtype != torch.uint8 or d_quals.numel() < rb.bases.numel():
+                raise ValueError("quals: a CUDA uint8 tensor laid out as the reads' bases")
+        else:
+            q = b"".join(bytes(x) for x in quals)
+            lens = np.fromiter((len(x) for x in quals), dtype=np.int64, count=len(quals))
+            want = np.full(n, rb.fixed_len, dtype=np.int64) if rb.offsets is None else np.diff(_to_host(rb.offsets)[0][: n + 1])
+            if len(lens) != n or not np.array_equal(lens, want):
+                raise ValueError("one quality string per read, as long as the read")
+            d_quals = up(np.frombuffer(q, dtype=np.uint8), np.uint8)
+        keep.append(d_quals)
+        f.quals = d_quals.data_ptr()
+    if strands is not None:
+        d_strand = up(np.asarray(strands, dtype=np.uint8), np.uint8)
+        if d_strand.numel() < n:
+            raise ValueError("one strand per read")
+        keep.append(d_strand)
+        f.strand = d_strand.data_ptr()
+    if stats is not None:
+        if stats.dtype != STATS_DTYPE or len(stats) != n:
+            raise ValueError("stats: the STATS_DTYPE array of `annotate` for this batch")
+        d_stats = up(stats, np.uint8)
+        keep.append(d_stats)
+        f.stats = d_stats.data_ptr()
+    rname_b = rname.encode() if isinstance(rname, str) else bytes(rname)
+    f.rname, f.rname_len, f.mapq = rname_b, len(rname_b), int(mapq)
+    flags = _lib.SAM_OMIT_SEQ if omit_seq else 0
+    b = rb.c_batch()
+    total, n_bad = C.c_uint64(0), C.c_uint64(0)
+    t_in = int(aln.inc.size)
+    args = (ctx.h, C.byref(b), C.byref(f), flags, d_aln.data_ptr(), d_status.data_ptr(), d_inc.data_ptr(), d_op.data_ptr(), t_in)
+    ctx.check(ctx.lib.zsw_sam_batch(*args, None, 0, C.byref(total), None, C.byref(n_bad), ctx.stream()), profile_errors=False)
+    text = torch.empty(max(int(total.value), 1), dtype=torch.uint8, device=dev)
+    offsets = torch.empty(n + 1, dtype=torch.int64, device=dev)
+    ctx.check(ctx.lib.zsw_sam_batch(*args, text.data_ptr(), int(total.value), C.byref(total), offsets.data_ptr(), C.byref(n_bad), ctx.stream()), profile_errors=False)
+    torch.cuda.synchronize(dev)
+    del keep
+    text = text[: int(total.value)]
+    if device_out:
+        return text, offsets
+    return _to_host(text)[0].tobytes() if text.numel() else b""
+
+
 def _to_host(*tensors):
     """Device tensors -> numpy arrays through page-locked buffers (torch caches them between calls), all copies in flight together:
     a 10 M-read alignment hands back half a gigabyte of records and ciglets, which pageable copies move at a fifth of the PCIe rate."""
@@ -706,6 +772,21 @@ class _ProfileBatchBase:
             reads = self.ctx.orient(reads, _torch().from_numpy(np.ascontiguousarray(aln.strand, dtype=np.uint8)).to(reads.bases.device))
         flags = (_lib.ANNOTATE_READ_IS_REF if seq.is_query else 0) | (_lib.ANNOTATE_MATCH_RESIDUES if residues else 0)
         return _annotate(self.ctx, reads, aln, flags, verbose)
+
+    def to_sam_text(self, aln: AlignmentBatch, qnames, quals=None, rname="ref", mapq: int = 255, strands=None, stats=None, omit_seq: bool = False,
+                    device: bool = False):
+        """zsw_sam_batch: the SAM body for the alignments `aln` of this batch (those of an alignment call, or the verbose ones of
+        `annotate`), one line per read — what `str(SamData.from_alignment(..))` / `str(SamData.unmapped(..))` of zoe_amd/records.py give,
+        each closed by a newline — formatted on the GPU. qnames: one name per read, or None ("*"); quals: the qualities as read, one
+        byte string per read or a CUDA uint8 tensor laid out as the reads, or None ("*"); strands: default `aln.strand` — strand 1:
+        FLAG 16, SEQ the reverse complement (the reads are oriented as for `annotate`), QUAL reversed; stats: the stats array of
+        `annotate`, for NM:i:; omit_seq: SEQ "*". -> bytes, or with `device` (a CUDA uint8 tensor, a CUDA int64 tensor of n + 1 line
+        offsets). A read of length 0 has "*" for SEQ and QUAL."""
+        strands = aln.strand if strands is None else strands
+        reads = self.reads
+        if strands is not None:
+            reads = self.ctx.orient(reads, _torch().from_numpy(np.ascontiguousarray(strands, dtype=np.uint8)).to(reads.bases.device))
+        return _sam_text(self.ctx, reads, aln, qnames, quals, rname, mapq, strands, stats, omit_seq, device)
 
 
 class StripedProfileBatch(_ProfileBatchBase):
@@ -1057,6 +1138,14 @@ class _SharedBase:
         self._prep()
         flags = _lib.ANNOTATE_SHARED | (0 if is_query else _lib.ANNOTATE_READ_IS_REF) | (_lib.ANNOTATE_MATCH_RESIDUES if residues else 0)
         return _annotate(self.ctx, rb, aln, flags, verbose)
+
+    def to_sam_text(self, aln: AlignmentBatch, seq, qnames, quals=None, rname="ref", mapq: int = 255, strands=None, stats=None, omit_seq: bool = False,
+                    device: bool = False):
+        """zsw_sam_batch over the alignments `aln` that one of this profile's alignment calls returned for `seq` (the same reads, or
+        the same SeqBatchSrc): as `_ProfileBatchBase.to_sam_text`, POS being the record's ref_start + 1 in whichever sequence the call
+        gave the reference's role. The reads are taken as they are (no strand-aware call exists in this role)."""
+        reads, _ = self._reads_of(seq)
+        return _sam_text(self.ctx, _as_batch(reads, self.device), aln, qnames, quals, rname, mapq, strands, stats, omit_seq, device)
 
 
 @dataclass

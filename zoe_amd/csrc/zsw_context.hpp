@@ -113,6 +113,8 @@ struct zsw_context {
     int32_t* strand_dbg = nullptr;  // zsw_debug_strand_records
     // zsw_annotate_batch (zsw_annotate.hip): the staged arrays of a host call, the verbose ciglet counts and their exclusive sum
     zsw::DevBuf an_ws[16];
+    // zsw_sam_batch (zsw_sam.hip): the staged arrays of a host call, RNAME, the line lengths / starts, the lines' shapes, the text
+    zsw::DevBuf sam_ws[20];
 };
 
 namespace zsw {

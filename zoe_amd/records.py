@@ -154,3 +154,23 @@ def align_fastq_to_sam(records: List[FastQ], reference: bytes, rname: str, matri
         else:
             out.append(SamData.unmapped(qnames[i], r.sequence, r.quality))
     return out
+
+
+def align_fastq_to_sam_text(records: List[FastQ], reference: bytes, rname: str, matrix, gap_open: int, gap_extend: int,
+                            device: int = 0, nm: bool = False, verbose_cigar: bool = False, three_pass: bool = False) -> bytes:
+    """The twin of `align_fastq_to_sam` that formats on the GPU (zsw_sam_batch): the same alignments, and the text
+    `"\\n".join(str(r) for r in align_fastq_to_sam(..)) + "\\n"` as bytes, without a SamData per read on the host."""
+    from .alignment import SeqSrc, into_local_profile
+
+    if not records:
+        return b""
+    qnames = [r.header.split()[0] if r.header.split() else r.header for r in records]
+    profiles = into_local_profile(batch_from_fastq(records, device), matrix, gap_open, gap_extend, device)
+    src = SeqSrc.Reference(reference)
+    aln = profiles.sw_align_from_i8_3pass(src) if three_pass else profiles.sw_align_from_i8(src)
+    stats = None
+    if nm or verbose_cigar:
+        verbose, stats = profiles.annotate(aln, src, verbose=verbose_cigar)
+        aln = verbose if verbose_cigar else aln
+        stats = stats if nm else None
+    return profiles.to_sam_text(aln, qnames, [r.quality for r in records], rname, 255, stats=stats)
