@@ -207,6 +207,7 @@ unsafe extern "C" {
     fn zsw_debug_set(ctx: *mut ZswContext, flags: u32) -> i32;
     fn zsw_debug_band_records(ctx: *mut ZswContext, records: *mut i32) -> i32;
     fn zsw_debug_cert_records(ctx: *mut ZswContext, records: *mut i32) -> i32;
+    fn zsw_debug_threepass_records(ctx: *mut ZswContext, records: *mut i32) -> i32;
     fn zsw_debug_strand_records(ctx: *mut ZswContext, records: *mut i32) -> i32;
     fn zsw_debug_score_launches(ctx: *mut ZswContext, records: *mut u32, capacity: u32, out_n: *mut u32) -> i32;
     fn zsw_prune_rescored(ctx: *mut ZswContext, out_reads: *mut u64) -> i32;
@@ -1038,6 +1039,16 @@ impl GpuContext {
     /// `records` must be null or device memory for `4 * n_reads` `i32` that outlives the following calls.
     pub unsafe fn debug_cert_records(&self, records: *mut i32) -> Result<(), GpuError> {
         self.check(zsw_debug_cert_records(self.raw, records), 0, 0)
+    }
+
+    /// `zsw_debug_threepass_records`: tests only — the third pass of the 3-pass alignment calls reports, per read, the route it
+    /// took (8 `i32` per read in device memory: route, accepted band, banded attempts, launch, why the first DP launch handed the
+    /// read to the rerun, the band that did not fit, slot bytes, ciglets; null = off).
+    ///
+    /// # Safety
+    /// `records` must be null or device memory for `8 * n_reads` `i32` that outlives the following calls.
+    pub unsafe fn debug_threepass_records(&self, records: *mut i32) -> Result<(), GpuError> {
+        self.check(zsw_debug_threepass_records(self.raw, records), 0, 0)
     }
 
     /// `zsw_set_option(ZSW_OPTION_EXACT_PRUNING)`: the exact column-pruned first pass (same results for every input,

@@ -597,6 +597,18 @@ zsw_error zsw_debug_band_records(zsw_context* ctx, int32_t* records);
  * records: device memory for 4 int32 per read of the following calls, NULL = off (the default). Results do not change. */
 zsw_error zsw_debug_cert_records(zsw_context* ctx, int32_t* records);
 
+/* Tests only (tests/test_gpu_threepass_edges.py): the third pass of the 3-pass alignment calls of both roles (zsw_threepass.hip)
+ * writes, for every read with an alignment, eight int32 into records[8 * read]: [0] the route — 1 the no-gaps shortcut, 2 a banded
+ * attempt was accepted, 3 the scalar alignment of the whole box —; [1] the band width of the accepted attempt, else 0; [2] the banded
+ * attempts made by the launch that finished the read; [3] that launch — 0 classify, 1 the first DP launch, 2 the rerun with
+ * full-size resources —; [4] why the first DP launch handed the read to the rerun — 0 it did not, 1 the two DP rows alone exceed
+ * its slot, 2 a banded attempt did not fit, 3 the scalar alignment of the box did not fit, 4 more ciglets than that launch keeps
+ * per read —; [5] reason 2: the band that did not fit, else 0; [6] the bytes of a slot of the launch that finished the read, 0 for
+ * classify; [7] the ciglets written in traceback order. Reads without an alignment and the certificate mode of the zsw_align calls
+ * leave their records alone. records: device memory for 8 int32 per read of the following calls, NULL = off (the default).
+ * Results do not change. */
+zsw_error zsw_debug_threepass_records(zsw_context* ctx, int32_t* records);
+
 /* Tests only (tests/test_gpu_strands.py): the strand-aware calls (zsw_strand.hip) write, for every read, eight int32 into
  * records[8 * read]: [0] / [1] the support of the anchor vote on the forward / reverse strand, [2] / [3] the whole-reference bound
  * of the forward / reverse strand (no local alignment of that orientation scores more; -1: no bound), [4] the strand that ran

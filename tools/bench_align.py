@@ -21,5 +21,5 @@ for r in range(reps + 1):
     torch.cuda.synchronize()
     dt = time.perf_counter() - t0
     ks, kl = ctx.timing_read()
-    print(f"rep {r}: {n/dt/1e6:.2f} M reads/s end-to-end ({dt*1e3:.0f} ms), pass-2 kernels {ks*1e3:.0f} ms over {kl} timed regions, "
+    print(f"rep {r}: {n/dt/1e6:.2f} M reads/s end-to-end ({dt*1e3:.0f} ms), pass-2 kernels {ks*1e3:.3f} ms over {kl} timed regions, "
           f"ciglets {len(a.inc)}, tiers {dict(zip(*__import__('numpy').unique(a.tier, return_counts=True)))}", flush=True)

@@ -272,6 +272,16 @@ class SwContext:
         self._cert_records = records
         self.check(self.lib.zsw_debug_cert_records(self.h, C.c_void_p(records.data_ptr() if records is not None else None)))
 
+    def debug_threepass_records(self, records=None):
+        """zsw_debug_threepass_records (tests): the third pass of the 3-pass alignment calls writes 8 int32 per read — route,
+        accepted band, banded attempts, launch, why the first DP launch handed the read to the rerun, the band that did not fit,
+        slot bytes, ciglets — into `records` (a CUDA int32 tensor of 8 * n_reads elements that the caller keeps alive); None
+        switches it off."""
+        if records is not None:
+            assert records.is_cuda and records.dtype == _torch().int32 and records.is_contiguous()
+        self._threepass_records = records
+        self.check(self.lib.zsw_debug_threepass_records(self.h, C.c_void_p(records.data_ptr() if records is not None else None)))
+
     def debug_strand_records(self, records=None):
         """zsw_debug_strand_records (tests): the strand-aware calls write 8 int32 per read — support of the anchor vote forward /
         reverse, whole-reference bound forward / reverse (-1: none), the strand that ran first, 1 = settled by proof, 0, 0 — into

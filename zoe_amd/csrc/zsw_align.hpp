@@ -37,6 +37,12 @@ hipError_t group_reads(const BatchDev& b, const uint8_t* d_status, const uint8_t
 
 // Third pass of sw_align_3pass (zsw_threepass.hip). list == null: classify pass over all reads (resolves the no-gaps
 // shortcut, queues the rest in dp_list); otherwise the DP pass over `list`.
+// The resources of its launches (threepass_third_pass, zsw_capi.hip; tests/test_gpu_threepass_edges.py reads these lines):
+constexpr uint64_t THREEPASS_SLOT_CAP = 98304;             // bytes: the most a slot of the first DP launch holds (96 KiB)
+constexpr uint32_t THREEPASS_MAXC = 32;                    // ciglets per read of the classify and first DP launches
+constexpr uint64_t THREEPASS_SCRATCH_BUDGET = 2147483648;  // bytes of slot scratch a DP launch may ask for (2 GiB)
+constexpr uint32_t THREEPASS_MAX_SLOTS = 131072;           // slots of a DP launch at most (at least 64: one block)
+constexpr int THREEPASS_RECORD_INTS = 8;                   // zsw_debug_threepass_records
 struct ThreePassArgs {
     BatchDev b{};
     const uint8_t* ref = nullptr;
@@ -84,6 +90,10 @@ struct ThreePassArgs {
     uint32_t* sweep_list = nullptr;
     uint32_t* sweep_count = nullptr;
     bool sweep_pass = false;
+    // zsw_debug_threepass_records: THREEPASS_RECORD_INTS per read (route, accepted band, attempts, launch, why the first DP launch
+    // handed the read to the rerun, the band that did not fit, slot bytes, ciglets); tp_launch: 0 classify, 1 first DP launch, 2 rerun
+    int32_t* tp_rec = nullptr;
+    int tp_launch = 0;
 };
 
 hipError_t launch_threepass(const ThreePassArgs& a, uint32_t grid, hipStream_t stream);

@@ -625,7 +625,7 @@ static zsw_error threepass_args(zsw_context* ctx, const Staged& st, const Ranges
                                 ThreePassArgs* a) {
     const uint32_t n = st.b.n_reads;
     DevBuf* ws = ctx->a_ws;
-    a->maxc = 32;
+    a->maxc = THREEPASS_MAXC;
     ZSW_HIP(ctx, ws[WS_ALN].ensure((size_t)n * sizeof(zsw_alignment)));
     ZSW_HIP(ctx, ws[WS_CIGSTART].ensure((size_t)n * 8));
     ZSW_HIP(ctx, ws[WS_CIGRAW].ensure((size_t)n * 4));
@@ -984,6 +984,7 @@ zsw_error threepass_third_pass(zsw_context* ctx, const Staged& st, const RangesD
     ThreePassArgs a;
     zsw_error ze = threepass_args(ctx, st, rd, pseq, pseq_len, invert, &a);
     if (ze != ZSW_OK) return ze;
+    a.tp_rec = ctx->tp_dbg;
     ZSW_HIP(ctx, hipMemsetAsync(ws[WS_FBCOUNT].p, 0, 16, stream));
     uint32_t* counters = ws[WS_FBCOUNT].as<uint32_t>();  // [0] rerun count, [1] dp count, [2] largest slot need
     a.dp_list = ws[WS_ITEMS].as<uint32_t>();
@@ -998,8 +999,7 @@ zsw_error threepass_third_pass(zsw_context* ctx, const Staged& st, const RangesD
                        DevBuf& cigbuf, DevBuf& scratchbuf) -> zsw_error {
         if (!count) return ZSW_OK;
         slot_bytes = (slot_bytes + 63) & ~63ull;
-        uint64_t budget = 2ull << 30;
-        uint32_t slots = (uint32_t)std::min<uint64_t>(std::max<uint64_t>(budget / slot_bytes, 64), 131072);
+        uint32_t slots = (uint32_t)std::min<uint64_t>(std::max<uint64_t>(THREEPASS_SCRATCH_BUDGET / slot_bytes, 64), THREEPASS_MAX_SLOTS);
         slots = std::min<uint32_t>(slots, (count + 63) / 64 * 64);
         slots = std::max<uint32_t>(64, slots / 64 * 64);
         ZSW_HIP(ctx, scratchbuf.ensure((uint64_t)slots * slot_bytes + 64));
@@ -1013,12 +1013,12 @@ zsw_error threepass_third_pass(zsw_context* ctx, const Staged& st, const RangesD
         d.cig = cigbuf.as<uint32_t>();
         d.maxc = maxc;
         d.by_item = by_item;
+        d.tp_launch = by_item ? 2 : 1;  // the rerun is the launch that packs its ciglets by list item
         hipError_t he = launch_threepass(d, slots / 64, stream);
         if (he != hipSuccess) return fail(ctx, ZSW_ERR_HIP, "3-pass DP", he);
         return ZSW_OK;
     };
-    const uint64_t SLOT_CAP = 96 * 1024;
-    ze = dp_pass(ws[WS_ITEMS].as<uint32_t>(), counters + 1, h_cnt[1], std::min<uint64_t>(std::max<uint32_t>(h_cnt[2], 64), SLOT_CAP), a.maxc, 0,
+    ze = dp_pass(ws[WS_ITEMS].as<uint32_t>(), counters + 1, h_cnt[1], std::min<uint64_t>(std::max<uint32_t>(h_cnt[2], 64), THREEPASS_SLOT_CAP), a.maxc, 0,
                  ws[WS_CIG], ws[WS_RING]);
     if (ze != ZSW_OK) return ze;
     ZSW_HIP(ctx, hipMemcpyAsync(h_cnt, counters, 4, hipMemcpyDeviceToHost, stream));
@@ -1447,6 +1447,12 @@ zsw_error zsw_debug_band_records(zsw_context* ctx, int32_t* records) {
 zsw_error zsw_debug_cert_records(zsw_context* ctx, int32_t* records) {
     if (!ctx) return ZSW_ERR_INVALID_ARGUMENT;
     ctx->cert_dbg = records;
+    return ZSW_OK;
+}
+
+zsw_error zsw_debug_threepass_records(zsw_context* ctx, int32_t* records) {
+    if (!ctx) return ZSW_ERR_INVALID_ARGUMENT;
+    ctx->tp_dbg = records;
     return ZSW_OK;
 }
 

@@ -76,6 +76,7 @@ struct zsw_context {
     uint32_t debug = 0;    // zsw_debug_set (kernel-selection overrides for tests)
     int32_t* band_dbg = nullptr;  // zsw_debug_band_records (tests: the banded seeded pass reports the values it decides with)
     int32_t* cert_dbg = nullptr;  // zsw_debug_cert_records (tests: the certificate pass reports its verdict per read)
+    int32_t* tp_dbg = nullptr;    // zsw_debug_threepass_records (tests: the third pass of the 3-pass calls reports each read's route)
     std::vector<uint32_t> score_launches;  // zsw_debug_score_launches (tests: the score kernels the last call launched, 4 entries each)
     uint32_t options = ZSW_DEBUG_SCORE_PRUNE;  // zsw_set_option, as ZSW_DEBUG_* bits; exact pruning is on by default
     uint32_t flags() const { return debug | options; }

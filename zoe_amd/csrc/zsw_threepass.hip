@@ -127,6 +127,16 @@ __global__ __launch_bounds__(64) void threepass_kernel(ThreePassArgs a) {
         out.query_len = query_len;
         out.ciglet_offset = 0;
         bool done = false;
+        uint32_t route = 1, band_ok = 0, attempts = 0;  // zsw_debug_threepass_records
+        // a read this launch cannot finish goes to the rerun with full-size resources; why: the record's [4], with [5] = why_band
+        auto to_rerun = [&](int32_t why, uint32_t why_band) {
+            if (a.tp_rec) {
+                int32_t* rec = a.tp_rec + (uint64_t)id * THREEPASS_RECORD_INTS;
+                rec[4] = why;
+                rec[5] = (int32_t)why_band;
+            }
+            a.fb_list[atomicAdd(a.fb_count, 1u)] = id;
+        };
         if (!a.list || a.sweep_pass) {
             // classify pass: the no-gaps shortcut (three_pass.rs:37-58) is resolved here, the rest is queued for the DP pass
             // (certificate mode: only reads with one optimal alignment, which must be this diagonal; the rest is not touched)
@@ -198,12 +208,12 @@ __global__ __launch_bounds__(64) void threepass_kernel(ThreePassArgs a) {
             // full-size slots (which starts over and takes the same decisions), so long reads with few indels — a narrow
             // band — are served by this launch's many small slots instead of a handful of box-sized ones.
             const uint64_t rows_bytes = ((8ull * qlen + 15) & ~15ull) + 32;
-            bool too_big = rows_bytes > a.slot_bytes;
-            if (too_big) {
-                const uint32_t k = atomicAdd(a.fb_count, 1u);
-                a.fb_list[k] = id;
+            if (rows_bytes > a.slot_bytes) {
+                to_rerun(1, 0);
                 continue;
             }
+            int32_t too_big = 0;  // the reason, as to_rerun takes it
+            uint32_t big_band = 0;
             // The 64 slots of a block are interleaved word by word (word i of lane l at word i * 64 + l of the block's region): the
             // lanes walk their rows and flag bytes in step, so a wavefront's accesses to "its i-th word" fall into four cache lines
             // instead of sixty-four.
@@ -223,9 +233,11 @@ __global__ __launch_bounds__(64) void threepass_kernel(ThreePassArgs a) {
                 // sw_banded_align (banded.rs:40-133)
                 const uint32_t full = 2 * band + 1;
                 if (rows_bytes + (uint64_t)rlen * full > a.slot_bytes) {
-                    too_big = true;
+                    too_big = 2;
+                    big_band = band;
                     break;
                 }
+                ++attempts;
                 for (uint32_t c = 0; c < qlen; ++c) {
                     h_row(c) = 0;
                     e_row(c) = go;
@@ -284,16 +296,17 @@ __global__ __launch_bounds__(64) void threepass_kernel(ThreePassArgs a) {
                     if (tp_traceback(cell, r_end, c_end, qlen, qs, query_len, trial, &r_fin, &c_fin)) {
                         w = trial;
                         have = true;
+                        band_ok = band;
                     }
                 }
                 if (!have) band *= 2;
             }
-            if (!have && !too_big && rows_bytes + (uint64_t)rlen * qlen > a.slot_bytes) too_big = true;
+            if (!have && !too_big && rows_bytes + (uint64_t)rlen * qlen > a.slot_bytes) too_big = 3;
             if (too_big) {
-                const uint32_t k = atomicAdd(a.fb_count, 1u);
-                a.fb_list[k] = id;
+                to_rerun(too_big, big_band);
                 continue;
             }
+            route = have ? 2 : 3;
             if (!have) {
                 // sw_scalar_align on the box (scalar.rs:173-271)
                 for (uint32_t c = 0; c < qlen; ++c) {
@@ -339,9 +352,18 @@ __global__ __launch_bounds__(64) void threepass_kernel(ThreePassArgs a) {
             out.query_end = (uint32_t)(c_end + 1) + qs;
         }
         if (w.overflow) {
-            const uint32_t k = atomicAdd(a.fb_count, 1u);
-            a.fb_list[k] = id;
+            to_rerun(4, 0);
             continue;
+        }
+        if (a.tp_rec) {
+            int32_t* rec = a.tp_rec + (uint64_t)id * THREEPASS_RECORD_INTS;
+            rec[0] = (int32_t)route;
+            rec[1] = (int32_t)band_ok;
+            rec[2] = (int32_t)attempts;
+            rec[3] = a.tp_launch;
+            if (a.tp_launch < 2) rec[4] = rec[5] = 0;  // the rerun keeps what the first DP launch wrote there
+            rec[6] = (int32_t)a.slot_bytes;
+            rec[7] = (int32_t)w.ncig;
         }
         out.n_ciglets = a.invert ? w.n_nons + (out.ref_start > 0 ? 1u : 0u) + (reference_len > out.ref_end ? 1u : 0u) : w.ncig;
         a.aln[id] = out;
