@@ -71,6 +71,7 @@ struct ScoreOut {
     // then do not depend on the tie rule (zsw_capi_shared.hip; the reverse pass of sw_simd_score_ranges as a second seeded pass).
     // The caller presets 0; kernels that do not know leave it.
     uint8_t* unique = nullptr;
+    // (the three flags below are host policy; they stay in this struct because the kernels take it by value: moving them changes device code)
     // the seeded pass does not score the reads it hands back (the caller computes every read without `unique` by other means)
     bool skip_handed_back = false;
     // the banded seeded pass stops after its first (narrow) tier: what fails there is handed back at once — for a caller whose own

@@ -168,6 +168,13 @@ static bool fast_ok(const ScoringDev& s) {
     return true;
 }
 
+// the largest weight of the matrix (0 if none is positive)
+static int max_weight(const ScoringDev& s) {
+    int maxw = 0;
+    for (int i = 0; i < s.S * s.S; ++i) maxw = std::max(maxw, (int)s.w[i]);
+    return maxw;
+}
+
 static void build_tables(const ScoringDev& s, bool fast, ScoreArgs* a) {
     int bias = 0;
     for (int i = 0; i < s.S * s.S; ++i) bias = s.w[i] < -bias ? -s.w[i] : bias;
@@ -337,13 +344,11 @@ static bool build_tables_wide(const ScoringDev& s, int G, ScoreArgsV2* a) {
 // drifted values stay inside an i32 for this reference and read length.
 static bool w32_ok(const ScoringDev& s, uint32_t ref_len, uint32_t max_len, uint32_t debug) {
     if ((debug & ZSW_DEBUG_NO_W32) || s.S > 32) return false;
-    int maxw = 0;
     for (int i = 0; i < s.S * s.S; ++i) {
         const int t = s.w[i] + s.gap_extend;
         if (t < -128 || t > 127) return false;
-        maxw = std::max(maxw, (int)s.w[i]);
     }
-    const uint64_t top = ((uint64_t)ref_len + TILE_G + 4) * (uint64_t)s.gap_extend + (uint64_t)max_len * (uint64_t)maxw;
+    const uint64_t top = ((uint64_t)ref_len + TILE_G + 4) * (uint64_t)s.gap_extend + (uint64_t)max_len * (uint64_t)max_weight(s);
     return top < 0x7f000000ull;
 }
 
@@ -441,9 +446,517 @@ __global__ void min_filter_kernel(BatchDev b, uint32_t min_thr, ScoreOut out, ui
     if ((threadIdx.x & 63) == 0 && mine) atomicAdd(count, mine);
 }
 
+// ---- the score dispatcher ------------------------------------------------------------------------------------------------------
+// What one call of launch_score / launch_score_rev is about: filled once, const from then on. Every step below builds the ScoreArgs
+// or ScoreArgsV2 it launches as a copy of v1 / v2 — no table set is shared scratch — and takes the stream it launches on as a
+// parameter: no step decides a stream for another.
+struct ScoreCall {
+    const ScoringDev* d_sc;
+    const ScoringDev& h_sc;
+    const BatchDev& b;
+    uint32_t max_len;
+    const uint8_t* d_ref;
+    uint32_t ref_len;
+    const ResultRule& rule;
+    const ScoreOut& out;
+    const ScoreWorkspace& ws;
+    int mode, maxw;
+    bool wide, fast, table_ok, use_v2;
+    uint32_t exact_grid;
+    // (value-initialised: the reverse pass's pointers, the tile fields and whatever else a step does not set are null)
+    ScoreArgs v1;    // the fields every launch shares, and score_kernel's tables where it can serve the call
+    ScoreArgsV2 v2;  // the fields every launch shares; each step adds the tables of its strip width
+
+    ScoreCall(const ScoringDev* d_sc, const ScoringDev& h_sc, const BatchDev& b, uint32_t max_len, const uint8_t* d_ref, uint32_t ref_len,
+              const ResultRule& rule, const ScoreOut& out, const ScoreWorkspace& ws, int mode)
+        : d_sc(d_sc), h_sc(h_sc), b(b), max_len(max_len), d_ref(d_ref), ref_len(ref_len), rule(rule), out(out), ws(ws), mode(mode), v1{}, v2{} {
+        wide = wide_ok(h_sc, ws.debug);
+        fast = fast_ok(h_sc);
+        table_ok = h_sc.S <= 7 || fast || wide;
+        use_v2 = table_ok && !wide && v2_ok(h_sc, ws.debug);
+        exact_grid = (uint32_t)(ws.slots / 64);
+        maxw = max_weight(h_sc);
+        common(&v1);
+        if (table_ok && !wide) build_tables(h_sc, fast, &v1);
+        common(&v2);
+    }
+
+  private:
+    template <class Args>
+    void common(Args* a) const {
+        a->b = b;
+        a->ref = d_ref;
+        a->ref_len = ref_len;
+        a->sc = d_sc;
+        a->rule = rule;
+        a->out = out;
+    }
+};
+
+// What a call leaves behind from one step to the next.
+struct ScoreDispatch {
+    const ScoreCall call;
+    bool seed_gtabs_built = false;  // ws.seed_gtab holds the call's per-row tables (build_seed_gtabs)
+};
+
+// The exact 32-bit kernel over the items of `bb`, or over those of them that `list` names (the worklist); rev_*: the reverse pass.
+static hipError_t launch_exact32(const ScoreCall& c, const BatchDev& bb, const uint32_t* list, const uint32_t* list_count, const uint32_t* rev_ref_end,
+                                 const uint32_t* rev_query_end, hipStream_t stream) {
+    note_launch(c.ws.launch_log, list ? ZSW_LAUNCH_EXACT32_WORKLIST : ZSW_LAUNCH_EXACT32, 0, 0, std::min(c.mode, 2));
+    hipLaunchKernelGGL(exact32_kernel, dim3(c.exact_grid), dim3(64), 0, stream, bb, list, list_count, c.d_ref, c.ref_len, c.d_sc, c.rule, c.out,
+                       c.ws.scratch, (uint32_t)c.ws.slots, c.ws.scratch_len, rev_ref_end, rev_query_end);
+    return hipGetLastError();
+}
+
+static hipError_t launch_one(const ScoreCall& c, const BatchDev& bb, int g, int cc, hipStream_t stream) {
+    std::vector<uint32_t>* const launches = c.ws.launch_log;  // zsw_debug_score_launches
+    if (c.wide || c.use_v2) {
+        ScoreArgsV2 a2 = c.v2;
+        a2.b = bb;
+        if (c.wide) {
+            if (!build_tables_wide(c.h_sc, g, &a2)) return launch_exact32(c, bb, nullptr, nullptr, nullptr, nullptr, stream);
+            if (bb.n_items) note_launch(launches, ZSW_LAUNCH_WIDE, g, cc, c.mode == 0 ? 0 : 2);
+            return launch_table_cfg_v2_wide(a2, g, cc, c.mode, stream);
+        }
+        if (build_tables_v2(c.h_sc, g, &a2)) {
+            if (bb.n_items) note_launch(launches, ZSW_LAUNCH_V2, g, cc, std::min(c.mode, 2));
+            return launch_table_cfg_v2(a2, g, cc, c.mode, stream);
+        }
+    }
+    ScoreArgs a = c.v1;
+    a.b = bb;
+    if (bb.n_items) note_launch(launches, c.fast ? ZSW_LAUNCH_V1_FAST : ZSW_LAUNCH_V1_BIASED, g, cc, std::min(c.mode, 2));
+    return launch_table_cfg(a, g, cc, c.fast, c.mode, stream);
+}
+
+// The tile kernels hand the strip boundary of every reference row from tile to tile through the two halves of ws.tile_buf: the
+// items a round can take, with one boundary per pair (the packed tiles: per_entry 2) or per read (the 32-bit ones: 1). 0: none fits.
+static uint32_t tile_round_items(const ScoreCall& c, uint32_t per_entry, uint32_t n_items) {
+    const size_t per = (size_t)c.ref_len * sizeof(uint2);
+    const size_t fit = per ? c.ws.tile_bytes / 2 / per : (size_t)n_items;
+    return (uint32_t)std::min<size_t>(per_entry * fit, per_entry == 2 ? 0x7ffffffeu : 0x7fffffffu);
+}
+
+// n_items items in rounds of per_round, each round tile by tile over `longest` columns, ping-pong between the halves of tile_buf.
+// launch_tile(a, first) launches one tile of the round that begins at item `first`: `a` holds the round's item count and the tile's
+// columns and buffers; where the items come from is the caller's (a.b.items, or the list it passes to launch_tile_w32).
+template <class LaunchTile>
+static hipError_t tile_rounds(const ScoreCall& c, ScoreArgsV2 a, uint32_t n_items, uint32_t per_round, uint32_t longest, uint32_t kind, LaunchTile launch_tile) {
+    uint2* buf[2] = {c.ws.tile_buf, reinterpret_cast<uint2*>(reinterpret_cast<uint8_t*>(c.ws.tile_buf) + c.ws.tile_bytes / 2)};
+    const uint32_t n_tiles = (longest + TILE_COLS - 1) / TILE_COLS;
+    a.tile_state = c.ws.tile_state;
+    for (uint32_t first = 0; first < n_items; first += per_round) {
+        a.b.n_items = std::min<uint32_t>(per_round, n_items - first);
+        for (uint32_t t = 0; t < n_tiles; ++t) {
+            a.tile_q0 = t * (uint32_t)TILE_COLS;
+            a.tile_in = t ? buf[(t - 1) & 1] : nullptr;
+            a.tile_out = t + 1 < n_tiles ? buf[t & 1] : nullptr;
+            note_launch(c.ws.launch_log, kind, TILE_G, TILE_C, c.mode == 0 ? 0 : 2);
+            hipError_t e = launch_tile(a, first);
+            if (e != hipSuccess) return e;
+        }
+    }
+    return hipSuccess;
+}
+
+// Reads longer than the widest strip configuration: TILE_COLS query columns per launch, the strip boundary of every
+// reference row handed from tile to tile through HBM, as many reads per round as the boundary buffers hold.
+// Returns hipErrorNotSupported when the packed kernels cannot take the batch (the caller then uses the exact kernel).
+static hipError_t launch_tiled(const ScoreCall& c, const BatchDev& bb, uint32_t longest, hipStream_t stream) {
+    const ScoreWorkspace& ws = c.ws;
+    if (!ws.tile_buf || !ws.tile_state || !bb.items || (ws.debug & ZSW_DEBUG_NO_TILES)) return hipErrorNotSupported;
+    if (!(c.wide || c.use_v2)) return hipErrorNotSupported;
+    ScoreArgsV2 a2 = c.v2;
+    if (!(c.wide ? build_tables_wide(c.h_sc, TILE_G, &a2) : build_tables_v2(c.h_sc, TILE_G, &a2))) return hipErrorNotSupported;
+    const uint32_t per_round = tile_round_items(c, 2, bb.n_items);
+    if (per_round == 0) return hipErrorNotSupported;
+    a2.b = bb;
+    return tile_rounds(c, a2, bb.n_items, per_round, longest, c.wide ? ZSW_LAUNCH_TILE_WIDE : ZSW_LAUNCH_TILE_V2, [&](ScoreArgsV2& a, uint32_t first) {
+        a.b.items = bb.items + first;
+        return launch_tile_v2(a, c.wide, c.mode, stream);
+    });
+}
+
+// The arguments of the 32-bit tile kernel (before the tile fields): any alphabet w32_ok admits, in the WIDE table
+static ScoreArgsV2 w32_args(const ScoreCall& c) {
+    ScoreArgsV2 a2 = c.v2;
+    fill_wide_table(c.h_sc, &a2);
+    a2.ge2 = (uint32_t)c.h_sc.gap_extend * 0x00010001u;
+    a2.gd2 = (uint32_t)(c.h_sc.gap_open - c.h_sc.gap_extend) * 0x00010001u;
+    return a2;
+}
+
+// Reads whose score is beyond the packed range sit in the device-side worklist (usually empty). Batches that can hold such
+// scores at all (long reads) read the count back and run the 32-bit tile kernel over the list; everything else launches the
+// exact kernel on the worklist unconditionally, which keeps short-read calls asynchronous.
+static hipError_t finish_worklist(const ScoreCall& c, hipStream_t stream) {
+    const ScoreWorkspace& ws = c.ws;
+    if ((uint64_t)c.max_len * (uint64_t)std::max(c.maxw, 1) >= 16384 && ws.tile_buf && ws.tile_state && w32_ok(c.h_sc, c.ref_len, c.max_len, ws.debug)) {
+        uint32_t cnt = 0;
+        hipError_t we = hipMemcpyAsync(&cnt, c.out.fb_count, sizeof(cnt), hipMemcpyDeviceToHost, stream);
+        if (we == hipSuccess) we = hipStreamSynchronize(stream);
+        if (we != hipSuccess) return we;
+        if (cnt == 0) return hipSuccess;
+        const uint32_t per_round = tile_round_items(c, 1, cnt);
+        if (per_round)
+            return tile_rounds(c, w32_args(c), cnt, per_round, c.max_len, ZSW_LAUNCH_TILE_W32,
+                               [&](const ScoreArgsV2& a, uint32_t first) { return launch_tile_w32(a, c.out.fb_list + first, c.mode, stream); });
+    }
+    return launch_exact32(c, c.b, c.out.fb_list, c.out.fb_count, nullptr, nullptr, stream);
+}
+
+// The seeded pass's per-row score tables, for blocks whose windows do not fit one LDS table (same bytes for every strip width),
+// once per call: `plain` from the call's tables, `band` (null: no banded kernel) from the doubled ones.
+static hipError_t build_seed_gtabs(ScoreDispatch& d, const ScoreArgsV2& plain, const ScoreArgsV2* band, hipStream_t stream) {
+    if (d.seed_gtabs_built) return hipSuccess;
+    hipError_t e = seed_build_gtab(plain, d.call.ws.seed_gtab, stream);
+    if (e == hipSuccess && band) e = seed_build_gtab(*band, seed_gtab_band(d.call.ws, d.call.ref_len), stream);
+    d.seed_gtabs_built = e == hipSuccess;
+    return e;
+}
+
+// Against a long reference the few reads handed back are cut into chunks of rows, each an item of its own (a class of
+// 2,000 reads walking 30,000 rows each is a dozen blocks on 256 CUs): chunks of at least four times the rows a
+// positive path can span, so that the overlap costs a quarter more cells at most. (tests/chunk_edge_reads.py restates the rule.)
+struct RowChunks {
+    uint64_t rows, overlap;
+    bool enabled;
+};
+static RowChunks row_chunks_for(const ScoreCall& c, uint32_t longest) {
+    const ScoringDev& s = c.h_sc;
+    RowChunks r;
+    r.overlap = s.gap_extend > 0 ? (uint64_t)longest + (uint64_t)longest * (uint64_t)c.maxw / (uint64_t)s.gap_extend + 2 : ~0ull;
+    r.rows = std::max<uint64_t>(4 * r.overlap, 2048);
+    r.enabled = c.ws.chunk_keys && !(c.ws.debug & ZSW_DEBUG_NO_ROW_CHUNKS) && s.gap_extend > 0 && r.rows * 2 <= c.ref_len && longest < (1u << CHUNK_COL_BITS) &&
+                c.ref_len < (1u << CHUNK_ROW_BITS) - 2;
+    return r;
+}
+
+// The full pass over the hand-back list of a seeded range (ap: the range's tables, its list and count), in chunks of rows.
+// (never co-scheduled: chunk_finalize_kernel writes the result of every read of the list)
+static hipError_t score_handed_back_chunked(const ScoreCall& c, ScoreArgsV2 ap, const RowChunks& rc, int g, int cc, uint32_t n_items, hipStream_t stream) {
+    ap.chunk_rows = (uint32_t)rc.rows;
+    ap.chunk_overlap = (uint32_t)rc.overlap;
+    ap.chunk_keys = c.ws.chunk_keys;
+    const uint32_t zgrid = (n_items + 255) / 256;
+    hipLaunchKernelGGL(chunk_zero_kernel, dim3(zgrid), dim3(256), 0, stream, ap.b.items, ap.n_items_dev, n_items, c.ws.chunk_keys);
+    note_launch(c.ws.launch_log, ZSW_LAUNCH_ROW_CHUNKS, (int)ap.chunk_rows, (int)ap.chunk_overlap, (int)((c.ref_len + ap.chunk_rows - 1) / ap.chunk_rows));
+    note_launch(c.ws.launch_log, ZSW_LAUNCH_V2, g, cc, std::min(c.mode, 2));
+    hipError_t pe = launch_table_cfg_v2(ap, g, cc, c.mode, stream);
+    if (pe != hipSuccess) return pe;
+    hipLaunchKernelGGL(chunk_finalize_kernel, dim3(zgrid), dim3(256), 0, stream, ap.b, ap.n_items_dev, c.ws.chunk_keys, ap.limit, c.rule, c.out, std::min(c.mode, 2));
+    return hipGetLastError();
+}
+
+// ... or over whole rows. A short list is latency-bound in the class's configuration (10,000 reads hand back a few hundred: one
+// wavefront per 32 reads walking all R rows is 1.3 ms whatever the count), a long one throughput-bound in any other. The count
+// stays on the device, so the list is launched in up to three configurations — the ones the cost model picks for
+// 16 k, 128 k and many reads — and each launch returns at once unless the count lies in its range (measured, 1 M
+// reads: 21 k handed back 1.27 ms at 8 lanes per pair, 1.1 ms at 16; 110 k: 4.3 ms at 4 lanes, 4.0 ms at 8).
+// (zsw_handback.hpp: the plan, and the invariant tests/models/handback_plan.cpp holds it to.)
+static hipError_t score_handed_back_gated(const ScoreCall& c, const ScoreArgsV2& ap, int g, int cc, uint32_t longest, uint32_t n_items, hipStream_t stream) {
+    HandbackLaunch plan[HANDBACK_MAX_LAUNCHES];
+    ScoreArgsV2 tabs[HANDBACK_MAX_LAUNCHES];
+    int n_tabs = 0;
+    const int n_plan = handback_plan(kCfgs, N_CFGS, longest, g, cc, n_items, [&](int g2) {
+        tabs[n_tabs] = c.v2;
+        if (!build_tables_v2(c.h_sc, g2, &tabs[n_tabs])) return false;
+        ++n_tabs;
+        return true;
+    }, plan);
+    hipError_t pe = hipSuccess;
+    for (int k = 0, t = 0; k < n_plan && pe == hipSuccess; ++k) {
+        ScoreArgsV2 ah = ap;
+        if (plan[k].own_tables) {  // (tables_ok succeeded once per such launch, in the plan's order)
+            ah = tabs[t++];
+            ah.b = ap.b;
+            ah.n_items_dev = ap.n_items_dev;
+            ah.first_item_dev = ap.first_item_dev;  // (the gates choose by the remainder)
+        }
+        ah.b.n_items = plan[k].grid_items;
+        ah.gate_lo = plan[k].lo;
+        ah.gate_hi = plan[k].hi;
+        note_launch(c.ws.launch_log, ZSW_LAUNCH_V2, plan[k].G, plan[k].C, std::min(c.mode, 2));
+        pe = launch_table_cfg_v2(ah, plan[k].G, plan[k].C, c.mode, stream);
+    }
+    return pe;
+}
+
+// Seeded exact pass (zsw_score_seed.hip) over the items of `bb` in strip configuration (g, cc): seed + sort + band or window kernel,
+// then score_kernel_v2 over the reads it hands back (device-side list; `counter` = its count, zeroed here). The workspace region
+// [work_off, work_off + seed_workspace_bytes(n_items)) and fail_list + list_off belong to this call alone.
+// hipErrorNotSupported: not switched on, or the batch does not qualify.
+static hipError_t seed_items(ScoreDispatch& d, const BatchDev& bb, int g, int cc, uint32_t longest, size_t work_off, uint32_t list_off, uint32_t* counter,
+                             uint32_t band_grid_cap, hipStream_t stream) {
+    const ScoreCall& c = d.call;
+    const ScoreWorkspace& ws = c.ws;
+    if (!c.use_v2 || !ws.seed || !ws.seed_work || !ws.prune_fail_list || !(ws.debug & ZSW_DEBUG_SCORE_PRUNE) || (ws.debug & ZSW_DEBUG_PRUNE_STRIP))
+        return hipErrorNotSupported;
+    if (bb.n_items < SEED_MIN_READS && !(ws.debug & ZSW_DEBUG_SCORE_PRUNE_ANY_SIZE)) return hipErrorNotSupported;
+    const size_t work_bytes = seed_workspace_bytes(bb.n_items, longest, band_grid_cap);
+    if (g == 32 || work_off + work_bytes > ws.seed_bytes) return hipErrorNotSupported;
+    ScoreArgsV2 ap = c.v2;
+    if (!build_tables_v2(c.h_sc, g, &ap) || !seed_applicable(*ws.seed, longest, c.ref_len, ap.limit)) return hipErrorNotSupported;
+    if (!ws.seed_gtab) return hipErrorNotSupported;
+    // the banded kernel works on doubled scores (zsw_seed.hpp: an odd value marks a path through a cell outside the band): its own
+    // drift constants and per-row table, if the doubled weights fit the table bytes
+    ScoreArgsV2 ab = c.v2;
+    const ScoreArgsV2* const band = !(ws.debug & ZSW_DEBUG_SEED_NO_BAND) && doubled_tables(c.h_sc, &ab) ? &ab : nullptr;
+    hipError_t pe = build_seed_gtabs(d, ap, band, stream);
+    if (pe != hipSuccess) return pe;
+    pe = hipMemsetAsync(counter, 0, 4, stream);
+    if (pe != hipSuccess) return pe;
+    ap.b = bb;
+    const RowChunks rc = row_chunks_for(c, longest);
+    static_assert(2 + NCLS <= 32, "the n0 words sit 32 behind their counters");
+    // (ws.prune_fail_count: 64 words, the counters in the first 2 + NCLS, the n0 word of each 32 behind it)
+    const SeedRegion region = {ws.seed_work + work_off, work_bytes, ws.prune_fail_list + list_off, counter, counter + 32};
+    bool coscheduled = false;
+    pe = launch_score_seeded(ap, g, cc, longest, ws, region, c.mode, band, band_grid_cap, rc.enabled, &coscheduled, stream);
+    if (pe != hipSuccess) return pe;
+    // out.skip_handed_back (the shared-profile role's passes, the seeded reverse pass of the ranges): the caller recomputes every
+    // read without the `unique` flag by other means, the handed-back reads among them — scoring them here would be thrown away
+    if (c.out.skip_handed_back) return hipSuccess;
+    ap.b.items = region.fail_list;
+    ap.n_items_dev = counter;
+    ap.first_item_dev = coscheduled ? region.n0 : nullptr;  // (not co-scheduled: n0 is not written, and nothing changes)
+    pe = rc.enabled ? score_handed_back_chunked(c, ap, rc, g, cc, bb.n_items, stream) : score_handed_back_gated(c, ap, g, cc, longest, bb.n_items, stream);
+    if (pe != hipSuccess) return pe;
+    // zsw_prune_rescored counts the reads scored over all their cells HERE: a pass whose handed-back reads the caller settles by
+    // other means (the reversed pass of the ranges, the shared role's ends) adds nothing
+    hipLaunchKernelGGL(add_count_kernel, dim3(1), dim3(1), 0, stream, counter, ws.prune_fail_count + 1);
+    return hipGetLastError();
+}
+
+// Column-pruned pass over the items of `bb` (reads of at most kPruneClasses[cls].max_len bases), then score_kernel_v2 over the
+// reads it hands back (device-side list and count). hipErrorNotSupported: not switched on, or the batch does not qualify.
+static hipError_t prune_items(const ScoreCall& c, const BatchDev& bb, int cls, uint32_t n_cls, hipStream_t stream) {
+    const ScoreWorkspace& ws = c.ws;
+    const bool wide = c.wide;
+    // 5-letter tables: behind ZSW_DEBUG_PRUNE_STRIP (the seeded pass is their default); 8..32 letter alphabets (WIDE tables): the
+    // default first pass — the seeded pass's k-mer argument does not hold for matrices whose substitutions score close to identities
+    if (!(c.use_v2 || wide) || !ws.prune_work || !(ws.debug & ZSW_DEBUG_SCORE_PRUNE)) return hipErrorNotSupported;
+    if (!wide && !(ws.debug & ZSW_DEBUG_PRUNE_STRIP)) return hipErrorNotSupported;
+    if (bb.n_items < PR_MIN_READS && !(ws.debug & ZSW_DEBUG_SCORE_PRUNE_ANY_SIZE)) return hipErrorNotSupported;
+    const int last = n_cls < bb.n_items ? cls + 1 : cls;  // the range may hold the next class too (same strip width)
+    ScoreArgsV2 ap = c.v2;
+    auto tables = [&](int g, ScoreArgsV2* t) { return wide ? build_tables_wide(c.h_sc, g, t) : build_tables_v2(c.h_sc, g, t); };
+    if (!tables(1, &ap)) return hipErrorNotSupported;
+    const uint32_t floor_strip = ap.floor0;
+    uint32_t limit = ap.limit, floor_window[2] = {0, 0};
+    for (int k = cls; k <= last; ++k) {
+        if (!tables(kPruneClasses[k].g, &ap)) return hipErrorNotSupported;
+        floor_window[k - cls] = ap.floor0;
+        limit = std::min(limit, ap.limit);
+    }
+    if (!prune_applicable(c.h_sc, kPruneClasses[last].max_len, c.ref_len, limit)) return hipErrorNotSupported;
+    int Gr = 0, Cr = 0;
+    if (!score_config_for(kPruneClasses[last].max_len, &Gr, &Cr)) return hipErrorNotSupported;
+    hipError_t pe = hipMemsetAsync(ws.prune_fail_count, 0, 4, stream);
+    if (pe != hipSuccess) return pe;
+    ap.b = bb;
+    uint32_t est_failed = 0xffffffffu;
+    pe = launch_score_pruned(ap, cls, n_cls, floor_strip, floor_window, c.h_sc, ws.prune_work, ws.prune_bytes, ws.prune_chunk,
+                             ws.prune_fail_list, ws.prune_fail_count, c.mode, wide, stream, &est_failed);
+    if (pe != hipSuccess) return pe;
+    note_launch(ws.launch_log, ZSW_LAUNCH_PRUNED, kPruneClasses[cls].g, kPruneClasses[cls].cp, std::min(c.mode, 2));
+    // a short list of handed-back reads is latency-bound in the narrowest configuration (20,000 reads of 150 residues: 3.4 ms
+    // at four lanes per pair, every block walking all R rows): with the probe's estimate it takes the small-batch configuration
+    if (est_failed != 0xffffffffu) (void)score_config_for_batch(kPruneClasses[last].max_len, est_failed + est_failed / 4 + 1024, &Gr, &Cr);
+    if (!tables(Gr, &ap)) return hipErrorInvalidValue;
+    ap.b.items = ws.prune_fail_list;
+    ap.n_items_dev = ws.prune_fail_count;
+    note_launch(ws.launch_log, wide ? ZSW_LAUNCH_WIDE : ZSW_LAUNCH_V2, Gr, Cr, wide ? (c.mode == 0 ? 0 : 2) : std::min(c.mode, 2));
+    pe = wide ? launch_table_cfg_v2_wide(ap, Gr, Cr, c.mode, stream) : launch_table_cfg_v2(ap, Gr, Cr, c.mode, stream);
+    if (pe != hipSuccess) return pe;
+    hipLaunchKernelGGL(add_count_kernel, dim3(1), dim3(1), 0, stream, ws.prune_fail_count, ws.prune_fail_count + 1);
+    return hipGetLastError();
+}
+
+// The length classes of a ragged batch: device-side histogram + scatter into ws.bucket_items, counts read back once.
+static hipError_t classify_lengths(const ScoreCall& c, BucketCaps* caps, uint32_t counts[NCLS + 1], uint32_t starts[NCLS + 1], hipStream_t stream) {
+    const BatchDev& b = c.b;
+    const ScoreWorkspace& ws = c.ws;
+    for (int k = 0; k < NCLS; ++k) caps->cap[k] = (uint32_t)(kCfgs[kBucketCfg[k]].G * kCfgs[kBucketCfg[k]].C);
+    hipError_t e = hipMemsetAsync(ws.bucket_counts, 0, 64 * sizeof(uint32_t), stream);
+    if (e != hipSuccess) return e;
+    const uint32_t hgrid = std::min<uint32_t>(1024, (b.n_items + 255) / 256);
+    hipLaunchKernelGGL(bucket_count_kernel, dim3(hgrid), dim3(256), 0, stream, b.offsets, b.n_items, *caps, ws.bucket_counts);
+    e = hipMemcpyAsync(counts, ws.bucket_counts, (NCLS + 1) * sizeof(uint32_t), hipMemcpyDeviceToHost, stream);
+    if (e != hipSuccess) return e;
+    e = hipStreamSynchronize(stream);
+    if (e != hipSuccess) return e;
+    uint32_t run = 0;
+    for (int k = 0; k <= NCLS; ++k) {
+        starts[k] = run;
+        run += counts[k];
+    }
+    e = hipMemcpyAsync(ws.bucket_counts + 32, starts, (NCLS + 1) * sizeof(uint32_t), hipMemcpyHostToDevice, stream);
+    if (e != hipSuccess) return e;
+    hipLaunchKernelGGL(bucket_scatter_kernel, dim3(hgrid), dim3(256), 0, stream, b.offsets, b.n_items, *caps, ws.bucket_counts + 32, ws.bucket_items);
+    return hipGetLastError();
+}
+
+// the items [first, first + n) of ws.bucket_items as a batch
+static BatchDev class_items(const ScoreCall& c, uint32_t first, uint32_t n) {
+    BatchDev bk = c.b;
+    bk.items = c.ws.bucket_items + first;
+    bk.n_items = n;
+    return bk;
+}
+
+// ragged: one launch per occupied length class
+static hipError_t score_ragged(ScoreDispatch& d, hipStream_t stream, KernelTimer* timer) {
+    const ScoreCall& c = d.call;
+    const ScoreWorkspace& ws = c.ws;
+    BucketCaps caps;
+    uint32_t counts[NCLS + 1], starts[NCLS + 1];
+    hipError_t e = classify_lengths(c, &caps, counts, starts, stream);
+    if (e != hipSuccess) return e;
+    if (timer) timer->begin(stream);
+    // The length classes are independent launches and the small ones cannot fill the chip on their own (a class of
+    // 70 k reads is two wavefronts per SIMD): they are spread over side streams, forked from and joined to `stream`.
+    SideStreams* side = ws.side;  // owned by the context: two contexts never share fork/join events
+    const bool fork = side != nullptr && !(ws.debug & ZSW_DEBUG_NO_SIDE_STREAMS);
+    if (c.use_v2 && ws.seed && ws.seed_gtab && (ws.debug & ZSW_DEBUG_SCORE_PRUNE) && !(ws.debug & ZSW_DEBUG_PRUNE_STRIP)) {
+        // the seeded pass's per-row score table, before the fork: every side stream reads it
+        ScoreArgsV2 ag = c.v2, ab = c.v2;
+        if (build_tables_v2(c.h_sc, 4, &ag)) {
+            e = build_seed_gtabs(d, ag, !(ws.debug & ZSW_DEBUG_SEED_NO_BAND) && doubled_tables(c.h_sc, &ab) ? &ab : nullptr, stream);
+            if (e != hipSuccess) return e;
+        }
+    }
+    if (fork) {
+        e = hipEventRecord(side->fork, stream);
+        if (e != hipSuccess) return e;
+        for (int i = 0; i < SideStreams::N; ++i) {
+            e = hipStreamWaitEvent(side->s[i], side->fork, 0);
+            if (e != hipSuccess) return e;
+        }
+    }
+    int used = 0;  // the classes take the side streams in turn
+    // seeded exact pass per length class: each class has its own region of the workspace, its own part of the worklist (at
+    // its items' offset) and its own counter, so every class runs its whole pipeline (seed, sort, window, full pass over the
+    // reads handed back) on a side stream of its own turn. A handed-back read walks all R rows however few there are of them —
+    // 15 ms per class against a 30 kb reference — so these launches must overlap.
+    {
+        size_t work_off = 0;
+        uint32_t n_seedable = 0;  // the banded kernel's blocks are shared among the classes in proportion to their reads
+        for (int k = 0; k < NCLS; ++k) n_seedable += counts[k];
+        for (int k = NCLS - 1; k >= 0; --k) {
+            if (!counts[k]) continue;
+            const Cfg& cf = kCfgs[kBucketCfg[k]];
+            const uint32_t grid_cap = seed_band_class_cap(counts[k], n_seedable);
+            e = seed_items(d, class_items(c, starts[k], counts[k]), cf.G, cf.C, caps.cap[k], work_off, starts[k], ws.prune_fail_count + 2 + k, grid_cap,
+                           fork ? side->s[used % SideStreams::N] : stream);
+            if (e == hipSuccess) {
+                ++used;
+                work_off += seed_workspace_bytes(counts[k], caps.cap[k], grid_cap);
+                counts[k] = 0;
+            } else if (e != hipErrorNotSupported) {
+                return e;
+            }
+        }
+    }
+    // column-pruned pass (strip + window; ZSW_DEBUG_PRUNE_STRIP): consecutive length classes that share a pruning class form
+    // one item range, and pruning classes with the same strip width share the strip launch
+    {
+        int k0[PR_N_CLASSES], k1[PR_N_CLASSES];
+        uint32_t cnt[PR_N_CLASSES];
+        for (int pc = 0; pc < PR_N_CLASSES; ++pc) {
+            k0[pc] = k1[pc] = -1;
+            cnt[pc] = 0;
+            for (int k = 0; k < NCLS; ++k) {
+                const uint32_t cap = caps.cap[k];
+                if (cap <= kPruneClasses[pc].max_len && (pc == 0 || cap > kPruneClasses[pc - 1].max_len) && cap > (uint32_t)kPruneClasses[pc].cp + 40) {
+                    if (k0[pc] < 0) k0[pc] = k;
+                    k1[pc] = k;
+                    cnt[pc] += counts[k];
+                }
+            }
+        }
+        for (int pc = 0; pc < PR_N_CLASSES; ++pc) {
+            if (k0[pc] < 0) continue;
+            int last = pc;
+            if (pc + 1 < PR_N_CLASSES && k0[pc + 1] == k1[pc] + 1 && kPruneClasses[pc + 1].cp == kPruneClasses[pc].cp && c.ref_len < (1u << 24)) last = pc + 1;
+            const BatchDev bp = class_items(c, starts[k0[pc]], starts[k1[last]] + counts[k1[last]] - starts[k0[pc]]);
+            if (bp.n_items) {
+                e = prune_items(c, bp, pc, cnt[pc], stream);
+                if (e == hipSuccess) {
+                    for (int k = k0[pc]; k <= k1[last]; ++k) counts[k] = 0;
+                } else if (e != hipErrorNotSupported) {
+                    return e;
+                }
+            }
+            pc = last;
+        }
+    }
+    for (int k = NCLS; k >= 0; --k) {  // longest class first
+        if (!counts[k]) continue;
+        const BatchDev bk = class_items(c, starts[k], counts[k]);
+        if (k == NCLS) {  // longer than every strip configuration; stays on the main stream (shares scratch with the pass below)
+            e = launch_tiled(c, bk, c.max_len, stream);
+            if (e == hipErrorNotSupported) e = launch_exact32(c, bk, nullptr, nullptr, nullptr, nullptr, stream);
+        } else {
+            e = launch_one(c, bk, kCfgs[kBucketCfg[k]].G, kCfgs[kBucketCfg[k]].C, fork ? side->s[used++ % SideStreams::N] : stream);
+        }
+        if (e != hipSuccess) return e;
+    }
+    if (fork) {
+        for (int i = 0; i < SideStreams::N; ++i) {
+            e = hipEventRecord(side->join[i], side->s[i]);
+            if (e != hipSuccess) return e;
+            e = hipStreamWaitEvent(stream, side->join[i], 0);
+            if (e != hipSuccess) return e;
+        }
+    }
+    if (timer) timer->end(stream);
+    return hipSuccess;
+}
+
 static hipError_t launch_score_passes(const ScoringDev* d_sc, const ScoringDev& h_sc, const BatchDev& b, uint32_t max_len,
                                       const uint8_t* d_ref, uint32_t ref_len, const ResultRule& rule, const ScoreOut& out,
-                                      const ScoreWorkspace& ws, hipStream_t stream, KernelTimer* timer, int mode);
+                                      const ScoreWorkspace& ws, hipStream_t stream, KernelTimer* timer, int mode) {
+    hipError_t e = hipMemsetAsync(out.fb_count, 0, sizeof(uint32_t), stream);
+    if (e != hipSuccess) return e;
+    ScoreDispatch d{ScoreCall(d_sc, h_sc, b, max_len, d_ref, ref_len, rule, out, ws, mode)};
+    const ScoreCall& c = d.call;
+    int G = 0, C = 0;
+    if (!c.table_ok) {  // alphabet outside the table kernels: exact kernel over the whole batch
+        if (timer) timer->begin(stream);
+        e = launch_exact32(c, b, nullptr, nullptr, nullptr, nullptr, stream);
+        if (timer) timer->end(stream);
+        return e;
+    }
+    if (b.offsets && !b.items && b.n_items > 0) {
+        e = score_ragged(d, stream, timer);
+    } else if (!score_config_for_batch(max_len, b.n_items, &G, &C)) {  // longer than every strip configuration
+        if (timer) timer->begin(stream);
+        BatchDev bl = b;
+        if (!bl.items && ws.bucket_items) {  // the tiles address reads through an item list
+            hipLaunchKernelGGL(iota_kernel, dim3((b.n_items + 255) / 256), dim3(256), 0, stream, ws.bucket_items, b.n_items);
+            bl.items = ws.bucket_items;
+        }
+        e = launch_tiled(c, bl, max_len, stream);
+        const bool tiled = e != hipErrorNotSupported;
+        if (!tiled) e = launch_exact32(c, b, nullptr, nullptr, nullptr, nullptr, stream);
+        if (timer) timer->end(stream);
+        if (!tiled) return e;
+    } else {
+        // The seeded exact pass (zsw_score_seed.hip), or the column-pruned pass (zsw_score_prune.hip; ZSW_DEBUG_PRUNE_STRIP); the
+        // reads they hand back are scored over all their cells. Otherwise the full pass. One timed interval either way.
+        if (timer) timer->begin(stream);
+        e = hipErrorNotSupported;
+        int Gs = 0, Cs = 0;
+        if (score_config_for(max_len, &Gs, &Cs)) e = seed_items(d, b, Gs, Cs, max_len, 0, 0, ws.prune_fail_count, SEED_BAND_MAX_GRID, stream);
+        const int cls = prune_class_for(max_len);
+        if (e == hipErrorNotSupported && cls >= 0) e = prune_items(c, b, cls, b.n_items, stream);
+        if (e == hipErrorNotSupported) e = launch_one(c, b, G, C, stream);
+        if (timer) timer->end(stream);
+    }
+    if (e != hipSuccess) return e;
+    return finish_worklist(c, stream);
+}
 
 hipError_t launch_score(const ScoringDev* d_sc, const ScoringDev& h_sc, const BatchDev& b, uint32_t max_len,
                         const uint8_t* d_ref, uint32_t ref_len, const ResultRule& rule, const ScoreOut& out,
@@ -453,481 +966,6 @@ hipError_t launch_score(const ScoringDev* d_sc, const ScoringDev& h_sc, const Ba
     hipLaunchKernelGGL(min_filter_kernel, dim3(std::min<uint32_t>((b.n_items + 255) / 256, 4096u)), dim3(256), 0, stream, b, min_threshold(rule, ws.min_score), out,
                        ws.min_counts + 2);
     return hipGetLastError();
-}
-
-static hipError_t launch_score_passes(const ScoringDev* d_sc, const ScoringDev& h_sc, const BatchDev& b, uint32_t max_len,
-                                      const uint8_t* d_ref, uint32_t ref_len, const ResultRule& rule, const ScoreOut& out,
-                                      const ScoreWorkspace& ws, hipStream_t stream, KernelTimer* timer, int mode) {
-    hipError_t e = hipMemsetAsync(out.fb_count, 0, sizeof(uint32_t), stream);
-    if (e != hipSuccess) return e;
-    int G = 0, C = 0;
-    const bool wide = wide_ok(h_sc, ws.debug);
-    const bool table_ok = h_sc.S <= 7 || fast_ok(h_sc) || wide;
-    const uint32_t exact_grid = (uint32_t)(ws.slots / 64);
-    ScoreArgs a;
-    a.b = b;
-    a.ref = d_ref;
-    a.ref_len = ref_len;
-    a.sc = d_sc;
-    a.rule = rule;
-    a.out = out;
-    a.rev_ref_end = nullptr;
-    a.rev_query_end = nullptr;
-    a.rev_score = nullptr;
-    a.gtab = nullptr;
-    const bool fast = fast_ok(h_sc);
-    if (table_ok && !wide) build_tables(h_sc, fast, &a);
-    const bool use_v2 = table_ok && !wide && v2_ok(h_sc, ws.debug);
-    ScoreArgsV2 a2;
-    a2.b = b;
-    a2.ref = d_ref;
-    a2.ref_len = ref_len;
-    a2.sc = d_sc;
-    a2.rule = rule;
-    a2.out = out;
-    a2.tile_q0 = 0;
-    a2.tile_in = nullptr;
-    a2.tile_out = nullptr;
-    a2.tile_state = nullptr;
-    a2.rev_ref_end = nullptr;
-    a2.rev_query_end = nullptr;
-    std::vector<uint32_t>* const launches = ws.launch_log;  // zsw_debug_score_launches
-    auto launch_one = [&](const BatchDev& bb, int g, int c) -> hipError_t {
-        if (wide) {
-            if (build_tables_wide(h_sc, g, &a2)) {
-                a2.b = bb;
-                if (bb.n_items) note_launch(launches, ZSW_LAUNCH_WIDE, g, c, mode == 0 ? 0 : 2);
-                return launch_table_cfg_v2_wide(a2, g, c, mode, stream);
-            }
-            note_launch(launches, ZSW_LAUNCH_EXACT32, 0, 0, std::min(mode, 2));
-            hipLaunchKernelGGL(exact32_kernel, dim3(exact_grid), dim3(64), 0, stream, bb, (const uint32_t*)nullptr,
-                               (const uint32_t*)nullptr, d_ref, ref_len, d_sc, rule, out, ws.scratch, (uint32_t)ws.slots,
-                               ws.scratch_len, (const uint32_t*)nullptr, (const uint32_t*)nullptr);
-            return hipGetLastError();
-        }
-        if (use_v2 && build_tables_v2(h_sc, g, &a2)) {
-            a2.b = bb;
-            if (bb.n_items) note_launch(launches, ZSW_LAUNCH_V2, g, c, std::min(mode, 2));
-            return launch_table_cfg_v2(a2, g, c, mode, stream);
-        }
-        a.b = bb;
-        if (bb.n_items) note_launch(launches, fast ? ZSW_LAUNCH_V1_FAST : ZSW_LAUNCH_V1_BIASED, g, c, std::min(mode, 2));
-        return launch_table_cfg(a, g, c, fast, mode, stream);
-    };
-    // Reads longer than the widest strip configuration: TILE_COLS query columns per launch, the strip boundary of every
-    // reference row handed from tile to tile through HBM, as many reads per round as the boundary buffers hold.
-    // Returns hipErrorNotSupported when the packed kernels cannot take the batch (the caller then uses the exact kernel).
-    auto launch_tiled = [&](const BatchDev& bb, uint32_t longest) -> hipError_t {
-        if (!ws.tile_buf || !ws.tile_state || !bb.items || (ws.debug & ZSW_DEBUG_NO_TILES)) return hipErrorNotSupported;
-        if (!(wide || use_v2)) return hipErrorNotSupported;
-        if (!(wide ? build_tables_wide(h_sc, TILE_G, &a2) : build_tables_v2(h_sc, TILE_G, &a2))) return hipErrorNotSupported;
-        const size_t per_pair = (size_t)ref_len * sizeof(uint2);
-        const size_t half = ws.tile_bytes / 2;
-        const size_t fit = per_pair ? half / per_pair : (size_t)bb.n_items;
-        if (fit == 0) return hipErrorNotSupported;
-        const uint32_t chunk = (uint32_t)std::min<size_t>(2 * fit, 0x7ffffffeu);
-        uint2* buf[2] = {ws.tile_buf, reinterpret_cast<uint2*>(reinterpret_cast<uint8_t*>(ws.tile_buf) + half)};
-        const uint32_t n_tiles = (longest + TILE_COLS - 1) / TILE_COLS;
-        for (uint32_t first = 0; first < bb.n_items; first += chunk) {
-            a2.b = bb;
-            a2.b.items = bb.items + first;
-            a2.b.n_items = std::min<uint32_t>(chunk, bb.n_items - first);
-            a2.tile_state = ws.tile_state;
-            for (uint32_t t = 0; t < n_tiles; ++t) {
-                a2.tile_q0 = t * (uint32_t)TILE_COLS;
-                a2.tile_in = t ? buf[(t - 1) & 1] : nullptr;
-                a2.tile_out = t + 1 < n_tiles ? buf[t & 1] : nullptr;
-                if (a2.b.n_items) note_launch(launches, wide ? ZSW_LAUNCH_TILE_WIDE : ZSW_LAUNCH_TILE_V2, TILE_G, TILE_C, mode == 0 ? 0 : 2);
-                hipError_t te = launch_tile_v2(a2, wide, mode, stream);
-                if (te != hipSuccess) return te;
-            }
-        }
-        return hipSuccess;
-    };
-    // Reads whose score is beyond the packed range sit in the device-side worklist (usually empty). Batches that can hold such
-    // scores at all (long reads) read the count back and run the 32-bit tile kernel over the list; everything else launches the
-    // exact kernel on the worklist unconditionally, which keeps short-read calls asynchronous.
-    auto finish_worklist = [&]() -> hipError_t {
-        int maxw = 1;
-        for (int i = 0; i < h_sc.S * h_sc.S; ++i) maxw = std::max(maxw, (int)h_sc.w[i]);
-        if ((uint64_t)max_len * (uint64_t)maxw >= 16384 && ws.tile_buf && ws.tile_state && w32_ok(h_sc, ref_len, max_len, ws.debug)) {
-            uint32_t cnt = 0;
-            hipError_t we = hipMemcpyAsync(&cnt, out.fb_count, sizeof(cnt), hipMemcpyDeviceToHost, stream);
-            if (we == hipSuccess) we = hipStreamSynchronize(stream);
-            if (we != hipSuccess) return we;
-            if (cnt == 0) return hipSuccess;
-            fill_wide_table(h_sc, &a2);
-            a2.ge2 = (uint32_t)h_sc.gap_extend * 0x00010001u;
-            a2.gd2 = (uint32_t)(h_sc.gap_open - h_sc.gap_extend) * 0x00010001u;
-            const size_t per_read = (size_t)ref_len * sizeof(uint2), half = ws.tile_bytes / 2;
-            const size_t fit = per_read ? half / per_read : (size_t)cnt;
-            if (fit > 0) {
-                uint2* buf[2] = {ws.tile_buf, reinterpret_cast<uint2*>(reinterpret_cast<uint8_t*>(ws.tile_buf) + half)};
-                const uint32_t n_tiles = (max_len + TILE_COLS - 1) / TILE_COLS;
-                for (uint32_t first = 0; first < cnt; first += (uint32_t)std::min<size_t>(fit, 0x7fffffffu)) {
-                    a2.b = b;
-                    a2.b.n_items = (uint32_t)std::min<size_t>(fit, cnt - first);
-                    a2.tile_state = ws.tile_state;
-                    for (uint32_t t = 0; t < n_tiles; ++t) {
-                        a2.tile_q0 = t * (uint32_t)TILE_COLS;
-                        a2.tile_in = t ? buf[(t - 1) & 1] : nullptr;
-                        a2.tile_out = t + 1 < n_tiles ? buf[t & 1] : nullptr;
-                        if (a2.b.n_items) note_launch(launches, ZSW_LAUNCH_TILE_W32, TILE_G, TILE_C, mode == 0 ? 0 : 2);
-                        we = launch_tile_w32(a2, out.fb_list + first, mode, stream);
-                        if (we != hipSuccess) return we;
-                    }
-                }
-                return hipSuccess;
-            }
-        }
-        note_launch(launches, ZSW_LAUNCH_EXACT32_WORKLIST, 0, 0, std::min(mode, 2));
-        hipLaunchKernelGGL(exact32_kernel, dim3(exact_grid), dim3(64), 0, stream, b, out.fb_list, out.fb_count, d_ref, ref_len, d_sc,
-                           rule, out, ws.scratch, (uint32_t)ws.slots, ws.scratch_len, (const uint32_t*)nullptr, (const uint32_t*)nullptr);
-        return hipGetLastError();
-    };
-    auto exact_all = [&](const BatchDev& bb) {
-        note_launch(launches, ZSW_LAUNCH_EXACT32, 0, 0, std::min(mode, 2));
-        hipLaunchKernelGGL(exact32_kernel, dim3(exact_grid), dim3(64), 0, stream, bb, (const uint32_t*)nullptr,
-                           (const uint32_t*)nullptr, d_ref, ref_len, d_sc, rule, out, ws.scratch, (uint32_t)ws.slots, ws.scratch_len, (const uint32_t*)nullptr, (const uint32_t*)nullptr);
-        return hipGetLastError();
-    };
-    // Seeded exact pass (zsw_score_seed.hip) over the items of `bb` in strip configuration (g, c): seed + sort + window kernel, then
-    // score_kernel_v2 over the reads it hands back (device-side list; `counter` = its count, zeroed here). The workspace region
-    // [work_off, work_off + seed_workspace_bytes(n_items)) and fail_list + list_off belong to this call alone.
-    bool gtab_built = false;
-    auto seed_items = [&](const BatchDev& bb, int g, int c, uint32_t longest, size_t work_off, uint32_t list_off, uint32_t* counter,
-                          uint32_t band_grid_cap) -> hipError_t {
-        if (!use_v2 || !ws.seed || !ws.seed_work || !ws.prune_fail_list || !(ws.debug & ZSW_DEBUG_SCORE_PRUNE) || (ws.debug & ZSW_DEBUG_PRUNE_STRIP))
-            return hipErrorNotSupported;
-        if (bb.n_items < SEED_MIN_READS && !(ws.debug & ZSW_DEBUG_SCORE_PRUNE_ANY_SIZE)) return hipErrorNotSupported;
-        if (g == 32 || work_off + seed_workspace_bytes(bb.n_items, longest, band_grid_cap) > ws.seed_bytes) return hipErrorNotSupported;
-        ScoreArgsV2 ap = a2;
-        if (!build_tables_v2(h_sc, g, &ap) || !seed_applicable(*ws.seed, longest, ref_len, ap.limit)) return hipErrorNotSupported;
-        if (!ws.seed_gtab) return hipErrorNotSupported;
-        hipError_t pe = hipSuccess;
-        // the banded kernel works on doubled scores (zsw_seed.hpp: an odd value marks a path through a cell outside the band): its own
-        // drift constants and per-row table, if the doubled weights fit the table bytes
-        ScoreArgsV2 ab = a2;
-        const bool band_ok = !(ws.debug & ZSW_DEBUG_SEED_NO_BAND) && doubled_tables(h_sc, &ab);
-        uint2* const gtab_band = ws.seed_gtab + (ref_len + 2 * SEED_GTAB_PAD);
-        if (!gtab_built) {  // the per-row score table, for blocks whose windows do not fit one LDS table (same bytes for every g)
-            pe = seed_build_gtab(ap, ws.seed_gtab, stream);
-            if (pe != hipSuccess) return pe;
-            if (band_ok) {
-                pe = seed_build_gtab(ab, gtab_band, stream);
-                if (pe != hipSuccess) return pe;
-            }
-            gtab_built = true;
-        }
-        pe = hipMemsetAsync(counter, 0, 4, stream);
-        if (pe != hipSuccess) return pe;
-        ap.b = bb;
-        // Against a long reference the few reads handed back are cut into chunks of rows, each an item of its own (a class of
-        // 2,000 reads walking 30,000 rows each is a dozen blocks on 256 CUs): chunks of at least four times the rows a
-        // positive path can span, so that the overlap costs a quarter more cells at most.
-        int maxw = 0;
-        for (int i = 0; i < h_sc.S * h_sc.S; ++i) maxw = std::max(maxw, (int)h_sc.w[i]);
-        const uint64_t overlap = h_sc.gap_extend > 0 ? (uint64_t)longest + (uint64_t)longest * (uint64_t)maxw / (uint64_t)h_sc.gap_extend + 2 : ~0ull;
-        const uint64_t rows = std::max<uint64_t>(4 * overlap, 2048);
-        const bool row_chunks = ws.chunk_keys && !(ws.debug & ZSW_DEBUG_NO_ROW_CHUNKS) && h_sc.gap_extend > 0 && rows * 2 <= ref_len && longest < (1u << CHUNK_COL_BITS) &&
-                                ref_len < (1u << CHUNK_ROW_BITS) - 2;
-        const uint32_t min_thr = (ws.min_score && ws.min_counts && !out.skip_handed_back) ? min_threshold(rule, ws.min_score) : 0u;
-        // The full pass over the reads the seed kernel hands back may run inside the first band tier's launch (zsw_handback.hpp:
-        // handback_coschedule); n0, one word per counter (the length classes of a ragged batch have their own), then holds how
-        // many reads of the list that launch scored, and the launches below score the rest.
-        CoscheduleCase co{};
-        co.mode = mode;
-        co.G = g;
-        co.mins = min_thr != 0;
-        co.row_chunks = row_chunks;
-        co.skip_handed_back = out.skip_handed_back;
-        co.disabled = (ws.debug & ZSW_DEBUG_SEED_NO_COSCHEDULE) != 0;
-        uint32_t* const n0 = counter + 32;  // (ws.prune_fail_count: 64 words, the counters in the first 2 + NCLS)
-        static_assert(2 + NCLS <= 32, "the n0 words sit 32 behind their counters");
-        bool coscheduled = false;
-        pe = launch_score_seeded(ap, g, c, longest, *ws.seed, ws.seed_work + work_off, seed_workspace_bytes(bb.n_items, longest, band_grid_cap), ws.seed_gtab,
-                                 ws.prune_fail_list + list_off, counter, mode, band_ok ? &ab : nullptr, gtab_band, ws.band_dbg,
-                                 (ws.debug & ZSW_DEBUG_SEED_WIDE_BAND) ? 0xffffffffu : (ws.debug & ZSW_DEBUG_SCORE_PRUNE_ANY_SIZE) ? 0u : SEED_NARROW_MIN_READS, band_grid_cap, stream,
-                                 ws.window_timer, out.narrow_only, out.reads_reversed && out.skip_handed_back, launches,
-                                 (ws.debug & ZSW_DEBUG_SEED_STRIP_FIRST_TIER) != 0, (ws.debug & ZSW_DEBUG_SEED_DIAG_LANE_EVENTS) != 0,
-                                 min_thr, ws.min_counts, &co, n0, &coscheduled, (ws.debug & ZSW_DEBUG_SEED_PLAIN_KERNEL) != 0);
-        if (pe != hipSuccess) return pe;
-        ap.b.items = ws.prune_fail_list + list_off;
-        ap.n_items_dev = counter;
-        ap.first_item_dev = coscheduled ? n0 : nullptr;  // (not co-scheduled: n0 is not written, and nothing changes)
-        // out.skip_handed_back (the shared-profile role's passes, the seeded reverse pass of the ranges): the caller recomputes every
-        // read without the `unique` flag by other means, the handed-back reads among them — scoring them here would be thrown away
-        if (!out.skip_handed_back) {
-            if (row_chunks) {  // (never co-scheduled: chunk_finalize_kernel writes the result of every read of the list)
-                ap.chunk_rows = (uint32_t)rows;
-                ap.chunk_overlap = (uint32_t)overlap;
-                ap.chunk_keys = ws.chunk_keys;
-                const uint32_t zgrid = (bb.n_items + 255) / 256;
-                hipLaunchKernelGGL(chunk_zero_kernel, dim3(zgrid), dim3(256), 0, stream, ap.b.items, counter, bb.n_items, ws.chunk_keys);
-                note_launch(launches, ZSW_LAUNCH_ROW_CHUNKS, (int)ap.chunk_rows, (int)ap.chunk_overlap, (int)((ref_len + ap.chunk_rows - 1) / ap.chunk_rows));
-                note_launch(launches, ZSW_LAUNCH_V2, g, c, std::min(mode, 2));
-                pe = launch_table_cfg_v2(ap, g, c, mode, stream);
-                if (pe != hipSuccess) return pe;
-                hipLaunchKernelGGL(chunk_finalize_kernel, dim3(zgrid), dim3(256), 0, stream, ap.b, counter, ws.chunk_keys, ap.limit, rule, out, std::min(mode, 2));
-                pe = hipGetLastError();
-            } else {
-                // A short list is latency-bound in the class's configuration (10,000 reads hand back a few hundred: one wavefront per
-                // 32 reads walking all R rows is 1.3 ms whatever the count), a long one throughput-bound in any other. The count
-                // stays on the device, so the list is launched in up to three configurations — the ones the cost model picks for
-                // 16 k, 128 k and many reads — and each launch returns at once unless the count lies in its range (measured, 1 M
-                // reads: 21 k handed back 1.27 ms at 8 lanes per pair, 1.1 ms at 16; 110 k: 4.3 ms at 4 lanes, 4.0 ms at 8).
-                // (zsw_handback.hpp: the plan, and the invariant tests/models/handback_plan.cpp holds it to.)
-                HandbackLaunch plan[HANDBACK_MAX_LAUNCHES];
-                ScoreArgsV2 tabs[HANDBACK_MAX_LAUNCHES];
-                int n_tabs = 0;
-                const int n_plan = handback_plan(kCfgs, N_CFGS, longest, g, c, bb.n_items, [&](int g2) {
-                    tabs[n_tabs] = a2;
-                    if (!build_tables_v2(h_sc, g2, &tabs[n_tabs])) return false;
-                    ++n_tabs;
-                    return true;
-                }, plan);
-                for (int k = 0, t = 0; k < n_plan && pe == hipSuccess; ++k) {
-                    ScoreArgsV2 ah = ap;
-                    if (plan[k].own_tables) {  // (tables_ok succeeded once per such launch, in the plan's order)
-                        ah = tabs[t++];
-                        ah.b = ap.b;
-                        ah.n_items_dev = counter;
-                        ah.first_item_dev = ap.first_item_dev;  // (the gates choose by the remainder)
-                    }
-                    ah.b.n_items = plan[k].grid_items;
-                    ah.gate_lo = plan[k].lo;
-                    ah.gate_hi = plan[k].hi;
-                    note_launch(launches, ZSW_LAUNCH_V2, plan[k].G, plan[k].C, std::min(mode, 2));
-                    pe = launch_table_cfg_v2(ah, plan[k].G, plan[k].C, mode, stream);
-                }
-            }
-        }
-        if (pe != hipSuccess) return pe;
-        // zsw_prune_rescored counts the reads scored over all their cells HERE: a pass whose handed-back reads the caller settles by
-        // other means (the reversed pass of the ranges, the shared role's ends) adds nothing
-        if (!out.skip_handed_back) hipLaunchKernelGGL(add_count_kernel, dim3(1), dim3(1), 0, stream, counter, ws.prune_fail_count + 1);
-        return hipGetLastError();
-    };
-    // Column-pruned pass over the items of `bb` (reads of at most kPruneClasses[cls].max_len bases), then score_kernel_v2 over the
-    // reads it hands back (device-side list and count). hipErrorNotSupported: not switched on, or the batch does not qualify.
-    auto prune_items = [&](const BatchDev& bb, int cls, uint32_t n_cls) -> hipError_t {
-        // 5-letter tables: behind ZSW_DEBUG_PRUNE_STRIP (the seeded pass is their default); 8..32 letter alphabets (WIDE tables): the
-        // default first pass — the seeded pass's k-mer argument does not hold for matrices whose substitutions score close to identities
-        if (!(use_v2 || wide) || !ws.prune_work || !(ws.debug & ZSW_DEBUG_SCORE_PRUNE)) return hipErrorNotSupported;
-        if (!wide && !(ws.debug & ZSW_DEBUG_PRUNE_STRIP)) return hipErrorNotSupported;
-        if (bb.n_items < PR_MIN_READS && !(ws.debug & ZSW_DEBUG_SCORE_PRUNE_ANY_SIZE)) return hipErrorNotSupported;
-        const int last = n_cls < bb.n_items ? cls + 1 : cls;  // the range may hold the next class too (same strip width)
-        ScoreArgsV2 ap = a2;
-        auto tables = [&](int g, ScoreArgsV2* t) { return wide ? build_tables_wide(h_sc, g, t) : build_tables_v2(h_sc, g, t); };
-        if (!tables(1, &ap)) return hipErrorNotSupported;
-        const uint32_t floor_strip = ap.floor0;
-        uint32_t limit = ap.limit, floor_window[2] = {0, 0};
-        for (int c = cls; c <= last; ++c) {
-            if (!tables(kPruneClasses[c].g, &ap)) return hipErrorNotSupported;
-            floor_window[c - cls] = ap.floor0;
-            limit = std::min(limit, ap.limit);
-        }
-        if (!prune_applicable(h_sc, kPruneClasses[last].max_len, ref_len, limit)) return hipErrorNotSupported;
-        int Gr = 0, Cr = 0;
-        if (!score_config_for(kPruneClasses[last].max_len, &Gr, &Cr)) return hipErrorNotSupported;
-        hipError_t pe = hipMemsetAsync(ws.prune_fail_count, 0, 4, stream);
-        if (pe != hipSuccess) return pe;
-        ap.b = bb;
-        uint32_t est_failed = 0xffffffffu;
-        pe = launch_score_pruned(ap, cls, n_cls, floor_strip, floor_window, h_sc, ws.prune_work, ws.prune_bytes, ws.prune_chunk,
-                                 ws.prune_fail_list, ws.prune_fail_count, mode, wide, stream, &est_failed);
-        if (pe != hipSuccess) return pe;
-        note_launch(launches, ZSW_LAUNCH_PRUNED, kPruneClasses[cls].g, kPruneClasses[cls].cp, std::min(mode, 2));
-        // a short list of handed-back reads is latency-bound in the narrowest configuration (20,000 reads of 150 residues: 3.4 ms
-        // at four lanes per pair, every block walking all R rows): with the probe's estimate it takes the small-batch configuration
-        if (est_failed != 0xffffffffu) (void)score_config_for_batch(kPruneClasses[last].max_len, est_failed + est_failed / 4 + 1024, &Gr, &Cr);
-        if (!tables(Gr, &a2)) return hipErrorInvalidValue;
-        a2.b = bb;
-        a2.b.items = ws.prune_fail_list;
-        a2.n_items_dev = ws.prune_fail_count;
-        note_launch(launches, wide ? ZSW_LAUNCH_WIDE : ZSW_LAUNCH_V2, Gr, Cr, wide ? (mode == 0 ? 0 : 2) : std::min(mode, 2));
-        pe = wide ? launch_table_cfg_v2_wide(a2, Gr, Cr, mode, stream) : launch_table_cfg_v2(a2, Gr, Cr, mode, stream);
-        a2.n_items_dev = nullptr;
-        if (pe != hipSuccess) return pe;
-        hipLaunchKernelGGL(add_count_kernel, dim3(1), dim3(1), 0, stream, ws.prune_fail_count, ws.prune_fail_count + 1);
-        return hipGetLastError();
-    };
-    if (!table_ok) {  // alphabet outside the table kernels: exact kernel over the whole batch
-        if (timer) timer->begin(stream);
-        e = exact_all(b);
-        if (timer) timer->end(stream);
-        return e;
-    }
-    if (b.offsets && !b.items && b.n_items > 0) {
-        // ragged: one launch per occupied length class (device-side histogram + scatter, counts read back once)
-        BucketCaps caps;
-        for (int k = 0; k < NCLS; ++k) caps.cap[k] = (uint32_t)(kCfgs[kBucketCfg[k]].G * kCfgs[kBucketCfg[k]].C);
-        e = hipMemsetAsync(ws.bucket_counts, 0, 64 * sizeof(uint32_t), stream);
-        if (e != hipSuccess) return e;
-        const uint32_t hgrid = std::min<uint32_t>(1024, (b.n_items + 255) / 256);
-        hipLaunchKernelGGL(bucket_count_kernel, dim3(hgrid), dim3(256), 0, stream, b.offsets, b.n_items, caps, ws.bucket_counts);
-        uint32_t counts[NCLS + 1];
-        e = hipMemcpyAsync(counts, ws.bucket_counts, sizeof(counts), hipMemcpyDeviceToHost, stream);
-        if (e != hipSuccess) return e;
-        e = hipStreamSynchronize(stream);
-        if (e != hipSuccess) return e;
-        uint32_t starts[NCLS + 1], run = 0;
-        for (int k = 0; k <= NCLS; ++k) {
-            starts[k] = run;
-            run += counts[k];
-        }
-        e = hipMemcpyAsync(ws.bucket_counts + 32, starts, sizeof(starts), hipMemcpyHostToDevice, stream);
-        if (e != hipSuccess) return e;
-        hipLaunchKernelGGL(bucket_scatter_kernel, dim3(hgrid), dim3(256), 0, stream, b.offsets, b.n_items, caps,
-                           ws.bucket_counts + 32, ws.bucket_items);
-        if (timer) timer->begin(stream);
-        // The length classes are independent launches and the small ones cannot fill the chip on their own (a class of
-        // 70 k reads is two wavefronts per SIMD): they are spread over side streams, forked from and joined to `stream`.
-        SideStreams* side = ws.side;  // owned by the context: two contexts never share fork/join events
-        const bool fork = side != nullptr && !(ws.debug & ZSW_DEBUG_NO_SIDE_STREAMS);
-        if (use_v2 && ws.seed && ws.seed_gtab && (ws.debug & ZSW_DEBUG_SCORE_PRUNE) && !(ws.debug & ZSW_DEBUG_PRUNE_STRIP)) {
-            // the seeded pass's per-row score table, before the fork: every side stream reads it
-            ScoreArgsV2 ag = a2;
-            if (build_tables_v2(h_sc, 4, &ag)) {
-                e = seed_build_gtab(ag, ws.seed_gtab, stream);
-                if (e != hipSuccess) return e;
-                ScoreArgsV2 ab = a2;
-                if (!(ws.debug & ZSW_DEBUG_SEED_NO_BAND) && doubled_tables(h_sc, &ab)) {
-                    e = seed_build_gtab(ab, ws.seed_gtab + (ref_len + 2 * SEED_GTAB_PAD), stream);
-                    if (e != hipSuccess) return e;
-                }
-                gtab_built = true;
-            }
-        }
-        if (fork) {
-            e = hipEventRecord(side->fork, stream);
-            if (e != hipSuccess) return e;
-            for (int i = 0; i < SideStreams::N; ++i) {
-                e = hipStreamWaitEvent(side->s[i], side->fork, 0);
-                if (e != hipSuccess) return e;
-            }
-        }
-        const hipStream_t main_stream = stream;
-        int used = 0;
-        // seeded exact pass per length class: each class has its own region of the workspace, its own part of the worklist (at
-        // its items' offset) and its own counter, so every class runs its whole pipeline (seed, sort, window, full pass over the
-        // reads handed back) on a side stream of its own turn. A handed-back read walks all R rows however few there are of them —
-        // 15 ms per class against a 30 kb reference — so these launches must overlap.
-        {
-            size_t work_off = 0;
-            uint32_t n_seedable = 0;  // the banded kernel's blocks are shared among the classes in proportion to their reads
-            for (int k = 0; k < NCLS; ++k) n_seedable += counts[k];
-            for (int k = NCLS - 1; k >= 0; --k) {
-                if (!counts[k]) continue;
-                BatchDev bk = b;
-                bk.items = ws.bucket_items + starts[k];
-                bk.n_items = counts[k];
-                const Cfg& cf = kCfgs[kBucketCfg[k]];
-                stream = fork ? side->s[used % SideStreams::N] : main_stream;
-                const uint32_t grid_cap = seed_band_class_cap(counts[k], n_seedable);
-                e = seed_items(bk, cf.G, cf.C, caps.cap[k], work_off, starts[k], ws.prune_fail_count + 2 + k, grid_cap);
-                stream = main_stream;
-                if (e == hipSuccess) ++used;
-                if (e == hipSuccess) {
-                    work_off += seed_workspace_bytes(counts[k], caps.cap[k], grid_cap);
-                    counts[k] = 0;
-                } else if (e != hipErrorNotSupported) {
-                    return e;
-                }
-            }
-        }
-        // column-pruned pass (strip + window; ZSW_DEBUG_PRUNE_STRIP): consecutive length classes that share a pruning class form
-        // one item range, and pruning classes with the same strip width share the strip launch
-        {
-            int k0[PR_N_CLASSES], k1[PR_N_CLASSES];
-            uint32_t cnt[PR_N_CLASSES];
-            for (int pc = 0; pc < PR_N_CLASSES; ++pc) {
-                k0[pc] = k1[pc] = -1;
-                cnt[pc] = 0;
-                for (int k = 0; k < NCLS; ++k) {
-                    const uint32_t cap = caps.cap[k];
-                    if (cap <= kPruneClasses[pc].max_len && (pc == 0 || cap > kPruneClasses[pc - 1].max_len) && cap > (uint32_t)kPruneClasses[pc].cp + 40) {
-                        if (k0[pc] < 0) k0[pc] = k;
-                        k1[pc] = k;
-                        cnt[pc] += counts[k];
-                    }
-                }
-            }
-            for (int pc = 0; pc < PR_N_CLASSES; ++pc) {
-                if (k0[pc] < 0) continue;
-                int last = pc;
-                if (pc + 1 < PR_N_CLASSES && k0[pc + 1] == k1[pc] + 1 && kPruneClasses[pc + 1].cp == kPruneClasses[pc].cp && ref_len < (1u << 24)) last = pc + 1;
-                BatchDev bp = b;
-                bp.items = ws.bucket_items + starts[k0[pc]];
-                bp.n_items = starts[k1[last]] + counts[k1[last]] - starts[k0[pc]];
-                if (bp.n_items) {
-                    e = prune_items(bp, pc, cnt[pc]);
-                    if (e == hipSuccess) {
-                        for (int k = k0[pc]; k <= k1[last]; ++k) counts[k] = 0;
-                    } else if (e != hipErrorNotSupported) {
-                        return e;
-                    }
-                }
-                pc = last;
-            }
-        }
-        for (int k = NCLS; k >= 0; --k) {  // longest class first
-            if (!counts[k]) continue;
-            BatchDev bk = b;
-            bk.items = ws.bucket_items + starts[k];
-            bk.n_items = counts[k];
-            if (k == NCLS) {  // longer than every strip configuration; stays on the main stream (shares scratch with the pass below)
-                e = launch_tiled(bk, max_len);
-                if (e == hipErrorNotSupported) e = exact_all(bk);
-            } else {
-                stream = fork ? side->s[used++ % SideStreams::N] : main_stream;
-                e = launch_one(bk, kCfgs[kBucketCfg[k]].G, kCfgs[kBucketCfg[k]].C);
-                stream = main_stream;
-            }
-            if (e != hipSuccess) return e;
-        }
-        if (fork) {
-            for (int i = 0; i < SideStreams::N; ++i) {
-                e = hipEventRecord(side->join[i], side->s[i]);
-                if (e != hipSuccess) return e;
-                e = hipStreamWaitEvent(stream, side->join[i], 0);
-                if (e != hipSuccess) return e;
-            }
-        }
-        if (timer) timer->end(stream);
-    } else {
-        if (!score_config_for_batch(max_len, b.n_items, &G, &C)) {  // longer than every strip configuration
-            if (timer) timer->begin(stream);
-            BatchDev bl = b;
-            if (!bl.items && ws.bucket_items) {  // the tiles address reads through an item list
-                hipLaunchKernelGGL(iota_kernel, dim3((b.n_items + 255) / 256), dim3(256), 0, stream, ws.bucket_items, b.n_items);
-                bl.items = ws.bucket_items;
-            }
-            e = launch_tiled(bl, max_len);
-            if (e == hipErrorNotSupported) {
-                e = exact_all(b);
-                if (timer) timer->end(stream);
-                return e;
-            }
-            if (timer) timer->end(stream);
-            if (e != hipSuccess) return e;
-            return finish_worklist();
-        }
-        // The seeded exact pass (zsw_score_seed.hip), or the column-pruned pass (zsw_score_prune.hip; ZSW_DEBUG_PRUNE_STRIP); the
-        // reads they hand back are scored over all their cells. Otherwise the full pass. One timed interval either way.
-        if (timer) timer->begin(stream);
-        e = hipErrorNotSupported;
-        {
-            int Gs = 0, Cs = 0;
-            if (score_config_for(max_len, &Gs, &Cs)) e = seed_items(b, Gs, Cs, max_len, 0, 0, ws.prune_fail_count, SEED_BAND_MAX_GRID);
-        }
-        const int cls = prune_class_for(max_len);
-        if (e == hipErrorNotSupported && cls >= 0) e = prune_items(b, cls, b.n_items);
-        if (e == hipErrorNotSupported) e = launch_one(b, G, C);
-        if (timer) timer->end(stream);
-        if (e != hipSuccess) return e;
-    }
-    return finish_worklist();
 }
 
 // ---- reverse pass of sw_simd_score_ranges -------------------------------------------------------------------
@@ -955,99 +993,52 @@ hipError_t launch_score_rev(const ScoringDev* d_sc, const ScoringDev& h_sc, cons
                             const uint32_t* d_fwd_score, uint2* d_gtab, hipStream_t stream) {
     hipError_t e = hipMemsetAsync(out.fb_count, 0, sizeof(uint32_t), stream);
     if (e != hipSuccess) return e;
-    const uint32_t exact_grid = (uint32_t)(ws.slots / 64);
+    const ScoreCall c(d_sc, h_sc, b, max_len, d_ref, ref_len, rule, out, ws, 2);
     int G = 0, C = 0;
-    const bool wide = wide_ok(h_sc, ws.debug);
-    const bool table_ok = (h_sc.S <= 7 || fast_ok(h_sc) || wide) && score_config_for(max_len, &G, &C);
-    if (!score_config_for(max_len, &G, &C) && ws.tile_buf && ws.tile_state && ws.bucket_items && w32_ok(h_sc, ref_len, max_len, ws.debug) && b.n_items) {
+    const bool fits = score_config_for(max_len, &G, &C);
+    if (!fits && ws.tile_buf && ws.tile_state && ws.bucket_items && w32_ok(h_sc, ref_len, max_len, ws.debug) && b.n_items) {
         // reads longer than every strip configuration: the 32-bit tile kernel over the reversed reference (held in d_gtab's bytes)
         uint8_t* d_rev = reinterpret_cast<uint8_t*>(d_gtab);
         if (ref_len) hipLaunchKernelGGL(reverse_bytes_kernel, dim3((ref_len + 255) / 256), dim3(256), 0, stream, d_ref, ref_len, d_rev);
         hipLaunchKernelGGL(iota_kernel, dim3((b.n_items + 255) / 256), dim3(256), 0, stream, ws.bucket_items, b.n_items);
-        ScoreArgsV2 a2;
-        a2.b = b;
+        ScoreArgsV2 a2 = w32_args(c);
         a2.ref = d_rev;
-        a2.ref_len = ref_len;
-        a2.sc = d_sc;
-        a2.rule = rule;
-        a2.out = out;
         a2.rev_ref_end = d_fwd_ref_end;
         a2.rev_query_end = d_fwd_query_end;
-        a2.tile_state = ws.tile_state;
-        fill_wide_table(h_sc, &a2);
-        a2.ge2 = (uint32_t)h_sc.gap_extend * 0x00010001u;
-        a2.gd2 = (uint32_t)(h_sc.gap_open - h_sc.gap_extend) * 0x00010001u;
-        const size_t per_read = (size_t)ref_len * sizeof(uint2), half = ws.tile_bytes / 2;
-        const size_t fit = per_read ? half / per_read : (size_t)b.n_items;
-        if (fit > 0) {
-            uint2* buf[2] = {ws.tile_buf, reinterpret_cast<uint2*>(reinterpret_cast<uint8_t*>(ws.tile_buf) + half)};
-            const uint32_t n_tiles = (max_len + TILE_COLS - 1) / TILE_COLS;
-            for (uint32_t first = 0; first < b.n_items; first += (uint32_t)std::min<size_t>(fit, 0x7fffffffu)) {
-                a2.b.n_items = (uint32_t)std::min<size_t>(fit, b.n_items - first);
-                for (uint32_t t = 0; t < n_tiles; ++t) {
-                    a2.tile_q0 = t * (uint32_t)TILE_COLS;
-                    a2.tile_in = t ? buf[(t - 1) & 1] : nullptr;
-                    a2.tile_out = t + 1 < n_tiles ? buf[t & 1] : nullptr;
-                    note_launch(ws.launch_log, ZSW_LAUNCH_TILE_W32, TILE_G, TILE_C, 2);
-                    e = launch_tile_w32(a2, ws.bucket_items + first, 2, stream);
-                    if (e != hipSuccess) return e;
-                }
-            }
-            return hipSuccess;
-        }
+        const uint32_t per_round = tile_round_items(c, 1, b.n_items);
+        if (per_round)
+            return tile_rounds(c, a2, b.n_items, per_round, max_len, ZSW_LAUNCH_TILE_W32,
+                               [&](const ScoreArgsV2& a, uint32_t first) { return launch_tile_w32(a, ws.bucket_items + first, 2, stream); });
     }
-    if (!table_ok) {
-        note_launch(ws.launch_log, ZSW_LAUNCH_EXACT32, 0, 0, 2);
-        hipLaunchKernelGGL(exact32_kernel, dim3(exact_grid), dim3(64), 0, stream, b, (const uint32_t*)nullptr,
-                           (const uint32_t*)nullptr, d_ref, ref_len, d_sc, rule, out, ws.scratch, (uint32_t)ws.slots,
-                           ws.scratch_len, d_fwd_ref_end, d_fwd_query_end);
-        return hipGetLastError();
-    }
-    ScoreArgs a;
-    a.b = b;
-    a.ref = d_ref;
-    a.ref_len = ref_len;
-    a.sc = d_sc;
-    a.rule = rule;
-    a.out = out;
+    if (!c.table_ok || !fits) return launch_exact32(c, b, nullptr, nullptr, d_fwd_ref_end, d_fwd_query_end, stream);
+    ScoreArgs a = c.v1;  // (not WIDE: with build_tables' tables)
     a.rev_ref_end = d_fwd_ref_end;
     a.rev_query_end = d_fwd_query_end;
     a.rev_score = d_fwd_score;
     a.gtab = d_gtab;
-    const bool fast = fast_ok(h_sc);
-    if (wide) {
+    if (c.wide) {
         for (int r = 0; r < 33; ++r)
             for (int q = 0; q < WIDE_STRIDE; ++q)
                 a.wide[r * WIDE_STRIDE + q] = (int8_t)((r < h_sc.S && q < h_sc.S) ? h_sc.w[r * h_sc.S + q] : 0);
         a.go2 = ((uint32_t)h_sc.gap_open & 0xffffu) * 0x00010001u;
         a.ge2 = ((uint32_t)h_sc.gap_extend & 0xffffu) * 0x00010001u;
         a.bias2 = 0;
-    } else {
-        build_tables(h_sc, fast, &a);
     }
-    if (ref_len) hipLaunchKernelGGL(gtab_kernel, dim3((ref_len + 255) / 256), dim3(256), 0, stream, d_ref, ref_len, d_sc, a, (int)wide, d_gtab);
-    if (wide) {
-        if (b.n_items) note_launch(ws.launch_log, ZSW_LAUNCH_WIDE_REV, G, C, 2);
+    if (ref_len) hipLaunchKernelGGL(gtab_kernel, dim3((ref_len + 255) / 256), dim3(256), 0, stream, d_ref, ref_len, d_sc, a, (int)c.wide, d_gtab);
+    if (b.n_items) note_launch(ws.launch_log, c.wide ? ZSW_LAUNCH_WIDE_REV : c.fast ? ZSW_LAUNCH_V1_FAST_REV : ZSW_LAUNCH_V1_BIASED_REV, G, C, 2);
+    if (c.wide) {
         e = launch_cfg_rev_wide(a, G, C, stream);
-        if (e != hipSuccess) return e;
-        note_launch(ws.launch_log, ZSW_LAUNCH_EXACT32_WORKLIST, 0, 0, 2);
-        hipLaunchKernelGGL(exact32_kernel, dim3(exact_grid), dim3(64), 0, stream, b, out.fb_list, out.fb_count, d_ref, ref_len, d_sc,
-                           rule, out, ws.scratch, (uint32_t)ws.slots, ws.scratch_len, d_fwd_ref_end, d_fwd_query_end);
-        return hipGetLastError();
-    }
-    if (b.n_items) note_launch(ws.launch_log, fast ? ZSW_LAUNCH_V1_FAST_REV : ZSW_LAUNCH_V1_BIASED_REV, G, C, 2);
-    switch (G * 100 + C) {
+    } else {
+        switch (G * 100 + C) {
 #define ZSW_CASE(GV, CV) \
-    case GV * 100 + CV: e = launch_cfg_rev<GV, CV>(a, fast, stream); break;
-        ZSW_FOR_EACH_STRIP_CONFIG(ZSW_CASE)
+    case GV * 100 + CV: e = launch_cfg_rev<GV, CV>(a, c.fast, stream); break;
+            ZSW_FOR_EACH_STRIP_CONFIG(ZSW_CASE)
 #undef ZSW_CASE
-        default: e = hipErrorInvalidValue;
+            default: e = hipErrorInvalidValue;
+        }
     }
     if (e != hipSuccess) return e;
-    note_launch(ws.launch_log, ZSW_LAUNCH_EXACT32_WORKLIST, 0, 0, 2);
-    hipLaunchKernelGGL(exact32_kernel, dim3(exact_grid), dim3(64), 0, stream, b, out.fb_list, out.fb_count, d_ref, ref_len, d_sc,
-                       rule, out, ws.scratch, (uint32_t)ws.slots, ws.scratch_len, d_fwd_ref_end, d_fwd_query_end);
-    return hipGetLastError();
+    return launch_exact32(c, b, out.fb_list, out.fb_count, d_fwd_ref_end, d_fwd_query_end, stream);
 }
 
 }  // namespace zsw

@@ -308,27 +308,27 @@ bool seed_applicable(const SeedIndex& ix, uint32_t max_len, uint32_t ref_len, ui
     return (uint64_t)ix.params.maxw * max_len + 8 < limit;  // no score can leave the packed range
 }
 
-hipError_t launch_score_seeded(const ScoreArgsV2& a2, int G, int C, uint32_t max_len, const SeedIndex& ix, uint8_t* work, size_t work_bytes,
-                               uint2* gtab, uint32_t* fail_list, uint32_t* fail_count, int mode, const ScoreArgsV2* band_tabs, const uint2* gtab_band, int32_t* band_dbg,
-                               uint32_t narrow_min_reads, uint32_t band_grid_cap, hipStream_t stream, KernelTimer* window_timer, bool narrow_only, bool reads_reversed,
-                               std::vector<uint32_t>* launches, bool strip_first_tier, bool diag_lane_events, uint32_t min_thr, uint32_t* min_counts,
-                               const CoscheduleCase* co, uint32_t* n0, bool* coscheduled, bool plain_seed_kernel) {
+hipError_t launch_score_seeded(const ScoreArgsV2& a2, int G, int C, uint32_t max_len, const ScoreWorkspace& ws, const SeedRegion& r, int mode,
+                               const ScoreArgsV2* band_tabs, uint32_t band_grid_cap, bool row_chunks, bool* coscheduled, hipStream_t stream) {
     const uint32_t n = a2.b.n_items;
-    if (coscheduled) *coscheduled = false;
-    if (!min_counts) min_thr = 0;
+    const SeedIndex& ix = *ws.seed;
+    // ZSW_OPTION_MIN_SCORE: min_threshold(), 0 = off (also where the caller settles the handed-back reads itself)
+    const uint32_t min_thr = (ws.min_score && ws.min_counts && !a2.out.skip_handed_back) ? min_threshold(a2.rule, ws.min_score) : 0u;
+    const bool reads_reversed = a2.out.reads_reversed && a2.out.skip_handed_back;
+    *coscheduled = false;
     if (n == 0) return hipSuccess;
-    if (!work || !gtab || work_bytes < seed_workspace_bytes(n, max_len, band_grid_cap)) return hipErrorNotSupported;
+    if (!r.work || !ws.seed_gtab || r.work_bytes < seed_workspace_bytes(n, max_len, band_grid_cap)) return hipErrorNotSupported;
     // the banded kernel (zsw_score_band.hip) when a strip's rows fit one drift period of the doubled scoring
-    const bool band = band_tabs != nullptr && gtab_band != nullptr && seed_band_applicable(ix.params, max_len, band_tabs->K, band_tabs->limit);
+    const bool band = band_tabs != nullptr && seed_band_applicable(ix.params, max_len, band_tabs->K, band_tabs->limit);
     const size_t per = round256((size_t)n * 4 + 8);
-    uint32_t* keys = reinterpret_cast<uint32_t*>(work);
-    uint32_t* keys_out = reinterpret_cast<uint32_t*>(work + per);
-    uint32_t* ids = reinterpret_cast<uint32_t*>(work + 2 * per);
-    uint32_t* order = reinterpret_cast<uint32_t*>(work + 3 * per);
-    uint32_t* info = reinterpret_cast<uint32_t*>(work + 4 * per);
-    uint32_t* masks = reinterpret_cast<uint32_t*>(work + 5 * per);
-    uint32_t* band_masks = reinterpret_cast<uint32_t*>(work + 6 * per);
-    uint8_t* p8 = work + 7 * per;
+    uint32_t* keys = reinterpret_cast<uint32_t*>(r.work);
+    uint32_t* keys_out = reinterpret_cast<uint32_t*>(r.work + per);
+    uint32_t* ids = reinterpret_cast<uint32_t*>(r.work + 2 * per);
+    uint32_t* order = reinterpret_cast<uint32_t*>(r.work + 3 * per);
+    uint32_t* info = reinterpret_cast<uint32_t*>(r.work + 4 * per);
+    uint32_t* masks = reinterpret_cast<uint32_t*>(r.work + 5 * per);
+    uint32_t* band_masks = reinterpret_cast<uint32_t*>(r.work + 6 * per);
+    uint8_t* p8 = r.work + 7 * per;
     uint8_t* band_dfb = p8;
     p8 += round256((size_t)n + 8);
     const uint32_t cs = seed_codes_stride(max_len);
@@ -360,15 +360,15 @@ hipError_t launch_score_seeded(const ScoreArgsV2& a2, int G, int C, uint32_t max
     s.key_bias = SEED_KEY_BIAS;
     s.fail_key = fail_key;
     s.ref_len = a2.ref_len;
-    s.fail_list = fail_list;
-    s.fail_count = fail_count;
+    s.fail_list = r.fail_list;
+    s.fail_count = r.fail_count;
     s.reversed = reads_reversed;
     s.min_thr = min_thr;
     s.out = a2.out;
-    s.min_count = min_counts;  // [0]: settled by the whole-read bound
+    s.min_count = ws.min_counts;  // [0]: settled by the whole-read bound
     const bool staged = !s.b.offsets && !s.b.items && s.b.fixed_len <= SEED_STAGE_LEN;
     // the two-phase kernel for the staged batches (cs: its residue rows hold a read's dwords, and i / cs by seed_div)
-    const bool packed = staged && !plain_seed_kernel && cs <= (uint32_t)SEED_PACKED_RES_WORDS_MAX;
+    const bool packed = staged && !(ws.debug & ZSW_DEBUG_SEED_PLAIN_KERNEL) && cs <= (uint32_t)SEED_PACKED_RES_WORDS_MAX;
     if (min_thr) {
         if (packed) hipLaunchKernelGGL((seed_packed_kernel<true>), dim3((n + 255) / 256), dim3(256), seed_packed_lds_bytes(s.b.fixed_len), stream, s);
         else if (staged) hipLaunchKernelGGL((seed_kernel<true, true>), dim3((n + 255) / 256), dim3(256), 0, stream, s);
@@ -401,15 +401,15 @@ hipError_t launch_score_seeded(const ScoreArgsV2& a2, int G, int C, uint32_t max
         b.band_dfb = band_dfb;
         b.codes = codes;
         b.cs = cs;
-        b.gtab = gtab_band;
+        b.gtab = seed_gtab_band(ws, a2.ref_len);
         b.bnd = band_buf;
-        b.dbg = band_dbg;
+        b.dbg = ws.band_dbg;  // zsw_debug_band_records
         b.nb = seed_band_rows(ix.params, max_len);
         b.grid = seed_band_grid(n, band_grid_cap);
         b.key_bias = SEED_KEY_BIAS;
         b.fail_key = fail_key;
-        b.fail_list = fail_list;
-        b.fail_count = fail_count;
+        b.fail_list = r.fail_list;
+        b.fail_count = r.fail_count;
         b.wu0 = ix.params.M1;
         b.wu_per16 = 2 * ix.params.M1_per8;
         b.wd0 = ix.params.Wd;
@@ -417,23 +417,25 @@ hipError_t launch_score_seeded(const ScoreArgsV2& a2, int G, int C, uint32_t max
         b.n_dev = nullptr;
         b.retry = nullptr;
         b.min_thr = min_thr;
-        b.min_count = min_counts ? min_counts + 1 : nullptr;  // [1]: settled by a band bound
+        b.min_count = ws.min_counts ? ws.min_counts + 1 : nullptr;  // [1]: settled by a band bound
         // work-queue counters of the (up to) two launches: the spare words behind `order` and `keys`
-        uint32_t* queue1 = reinterpret_cast<uint32_t*>(work + 3 * per + (size_t)n * 4) + 1;
-        uint32_t* queue2 = reinterpret_cast<uint32_t*>(work + (size_t)n * 4);
+        uint32_t* queue1 = reinterpret_cast<uint32_t*>(r.work + 3 * per + (size_t)n * 4) + 1;
+        uint32_t* queue2 = reinterpret_cast<uint32_t*>(r.work + (size_t)n * 4);
         e = hipMemsetAsync(queue1, 0, 4, stream);
         if (e != hipSuccess) return e;
         e = hipMemsetAsync(queue2, 0, 8, stream);  // (and the first tier's count of accepted reads behind it)
         if (e != hipSuccess) return e;
         uint32_t* accepted = queue2 + 1;
         b.next_pair = queue2;
-        if (window_timer) window_timer->begin(stream);
+        if (ws.window_timer) ws.window_timer->begin(stream);
+        // score-only calls of at least this many short reads walk a narrow band first (SEED_NARROW_*)
+        const uint32_t narrow_min_reads = (ws.debug & ZSW_DEBUG_SEED_WIDE_BAND) ? 0xffffffffu : (ws.debug & ZSW_DEBUG_SCORE_PRUNE_ANY_SIZE) ? 0u : SEED_NARROW_MIN_READS;
         if (max_len <= SEED_NARROW_MAX_LEN && n >= narrow_min_reads) {
             // two tiers: every read in a narrow band; the reads whose bounds fail there, still in anchor order, in the full band.
             // The sort's input values and output keys are free by now: flags and the second tier's order.
             uint8_t* retry = reinterpret_cast<uint8_t*>(ids);
             uint32_t* order2 = keys_out;
-            uint32_t* n2 = reinterpret_cast<uint32_t*>(work + 3 * per + (size_t)n * 4);  // the 8 spare bytes behind `order`
+            uint32_t* n2 = reinterpret_cast<uint32_t*>(r.work + 3 * per + (size_t)n * 4);  // the 8 spare bytes behind `order`
             e = hipMemsetAsync(retry, 0, n, stream);
             if (e != hipSuccess) return e;
             SeedBandArgs b1 = b;
@@ -441,36 +443,37 @@ hipError_t launch_score_seeded(const ScoreArgsV2& a2, int G, int C, uint32_t max
             b1.wu_per16 = SEED_NARROW_WU_PER16;
             b1.wd0 = SEED_NARROW_WD;
             b1.wd_per32 = SEED_NARROW_WD_PER32;
-            b1.retry = narrow_only ? nullptr : retry;  // no second tier: what fails joins the worklist at once
-            b1.accepted = narrow_only ? nullptr : accepted;
+            b1.retry = a2.out.narrow_only ? nullptr : retry;  // no second tier: what fails joins the worklist at once
+            b1.accepted = a2.out.narrow_only ? nullptr : accepted;
             b1.next_pair = queue1;
-            b1.diag_lane_events = diag_lane_events;
-            note_launch(launches, ZSW_LAUNCH_SEED_BAND, G, C, mode);
+            b1.diag_lane_events = (ws.debug & ZSW_DEBUG_SEED_DIAG_LANE_EVENTS) != 0;
+            note_launch(ws.launch_log, ZSW_LAUNCH_SEED_BAND, G, C, mode);
             // score only, as the first of two tiers: the band diagonal by diagonal (seed_diag_kernel) instead of 16-column strips
-            const bool diagonal = mode == 0 && !narrow_only && !strip_first_tier && seed_diag_applicable(max_len, band_tabs->K);
-            CoscheduleCase cc{};
-            if (co) cc = *co;
-            cc.two_tiers = !narrow_only;
-            cc.diagonal = diagonal;
-            if (co && n0 && coscheduled && handback_coschedule(cc) && cc.mode == mode && cc.G == G && cc.mins == (min_thr != 0)) {
+            const bool diagonal = mode == 0 && !a2.out.narrow_only && !(ws.debug & ZSW_DEBUG_SEED_STRIP_FIRST_TIER) && seed_diag_applicable(max_len, band_tabs->K);
+            // The full pass over the reads the seed kernel hands back may run inside this launch (zsw_handback.hpp:
+            // handback_coschedule); n0, one word per counter (the length classes of a ragged batch have their own), then holds how
+            // many reads of the list that launch scored, and the caller's launches score the rest.
+            const CoscheduleCase cc{mode, !a2.out.narrow_only, diagonal, G, min_thr != 0, row_chunks, a2.out.skip_handed_back,
+                                    (ws.debug & ZSW_DEBUG_SEED_NO_COSCHEDULE) != 0};  // (the fields in the struct's order)
+            if (handback_coschedule(cc)) {
                 // The full pass over the reads the seed kernel listed, in the first tier's grid. Invariant: b1.retry != nullptr and
                 // no bail-out (b1.bail_check is false), so the tier appends nothing to fail_list: the list and *fail_count are
                 // frozen for the whole launch, and *n0 — copied here, on the stream, behind the seed kernel — is the count every
                 // block of the launch reads. What the second tier appends behind it is the caller's (first_item_dev = n0).
-                e = hipMemcpyAsync(n0, fail_count, 4, hipMemcpyDeviceToDevice, stream);
+                e = hipMemcpyAsync(r.n0, r.fail_count, 4, hipMemcpyDeviceToDevice, stream);
                 if (e != hipSuccess) return e;
                 ScoreArgsV2 hb = a2;
-                hb.b.items = fail_list;
-                hb.n_items_dev = fail_count;
-                note_launch(launches, ZSW_LAUNCH_V2, G, C, 0);
+                hb.b.items = r.fail_list;
+                hb.n_items_dev = r.fail_count;
+                note_launch(ws.launch_log, ZSW_LAUNCH_V2, G, C, 0);
                 e = launch_seed_diag_handback(b1, hb, G, C, stream);
                 *coscheduled = true;
             } else {
                 e = launch_seed_band(b1, mode, true, stream, diagonal);
             }
             if (e != hipSuccess) return e;
-            if (narrow_only) {
-                if (window_timer) window_timer->end(stream);
+            if (a2.out.narrow_only) {
+                if (ws.window_timer) ws.window_timer->end(stream);
                 return hipSuccess;
             }
             e = hipcub::DeviceSelect::Flagged(temp, temp_bytes, (const uint32_t*)order, (const uint8_t*)retry, order2, n2, (int)n, stream);
@@ -485,11 +488,11 @@ hipError_t launch_score_seeded(const ScoreArgsV2& a2, int G, int C, uint32_t max
             // a third of the rest (worth it); at 10 % 3 % and an eighth (break-even); at 12 % 0.4 % and 3 % (4 ms spent to save 1)
             b.accepted = accepted;
             b.bail_check = true;
-            b.bail_below = band_dbg ? 0u : SEED_BAIL_BELOW;  // (the bounds test wants the second tier's records)
+            b.bail_below = ws.band_dbg ? 0u : SEED_BAIL_BELOW;  // (the bounds test wants the second tier's records)
         }
-        note_launch(launches, ZSW_LAUNCH_SEED_BAND, G, C, mode);
+        note_launch(ws.launch_log, ZSW_LAUNCH_SEED_BAND, G, C, mode);
         e = launch_seed_band(b, mode, false, stream);
-        if (window_timer) window_timer->end(stream);
+        if (ws.window_timer) ws.window_timer->end(stream);
         return e;
     }
     SeedWindowArgs w;
@@ -514,16 +517,16 @@ hipError_t launch_score_seeded(const ScoreArgsV2& a2, int G, int C, uint32_t max
     w.keys = keys;
     w.info = info;
     w.masks = masks;
-    w.gtab = gtab;
+    w.gtab = ws.seed_gtab;
     w.key_bias = SEED_KEY_BIAS;
     w.fail_key = fail_key;
-    w.fail_list = fail_list;
-    w.fail_count = fail_count;
+    w.fail_list = r.fail_list;
+    w.fail_count = r.fail_count;
     w.reversed = reads_reversed;
-    if (window_timer) window_timer->begin(stream);
-    note_launch(launches, ZSW_LAUNCH_SEED_WINDOW, G, C, std::min(mode, 2));
+    if (ws.window_timer) ws.window_timer->begin(stream);
+    note_launch(ws.launch_log, ZSW_LAUNCH_SEED_WINDOW, G, C, std::min(mode, 2));
     e = mode == 0 ? launch_seed_window_m0(w, G, C, stream) : mode == 1 ? launch_seed_window_m1(w, G, C, stream) : launch_seed_window_m2(w, G, C, stream);
-    if (window_timer) window_timer->end(stream);
+    if (ws.window_timer) ws.window_timer->end(stream);
     return e;
 }
 

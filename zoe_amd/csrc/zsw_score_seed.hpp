@@ -139,25 +139,28 @@ inline uint32_t seed_band_class_cap(uint32_t n_class, uint32_t n_total) {
 size_t seed_workspace_bytes(uint32_t n, uint32_t max_len, uint32_t band_grid_cap = SEED_BAND_MAX_GRID);
 // can reads of up to max_len bases be seeded with this index, given the packed kernels' score limit?
 bool seed_applicable(const SeedIndex& ix, uint32_t max_len, uint32_t ref_len, uint32_t limit);
-// narrow_min_reads: score-only calls of at least this many short reads walk a narrow band first (SEED_NARROW_*).
-// Seeds, sorts and runs the window kernel (strip configuration G x C of a2's tables) over the items of a2.b; reads without an
-// anchor and reads whose bounds fail are appended to fail_list (count at fail_count, not reset here).
 // gtab: (ref_len + 2 * SEED_GTAB_PAD) uint2, filled by seed_build_gtab (once per call of launch_score, from a2's tables).
 hipError_t seed_build_gtab(const ScoreArgsV2& a2, uint2* gtab, hipStream_t stream);
-// band_tabs: non-null = the banded kernel may run: drift constants of the DOUBLED scoring (ge2, gd2, floor0, K, limit), whose
-// per-row table is gtab_band (seed_build_gtab with those tables); band_dbg: zsw_debug_band_records.
-hipError_t launch_score_seeded(const ScoreArgsV2& a2, int G, int C, uint32_t max_len, const SeedIndex& ix, uint8_t* work, size_t work_bytes,
-                               uint2* gtab, uint32_t* fail_list, uint32_t* fail_count, int mode, const ScoreArgsV2* band_tabs, const uint2* gtab_band, int32_t* band_dbg,
-                               uint32_t narrow_min_reads, uint32_t band_grid_cap, hipStream_t stream, KernelTimer* window_timer, bool narrow_only = false, bool reads_reversed = false,
-                               std::vector<uint32_t>* launches = nullptr /* zsw_debug_score_launches */, bool strip_first_tier = false /* ZSW_DEBUG_SEED_STRIP_FIRST_TIER */,
-                               bool diag_lane_events = false /* ZSW_DEBUG_SEED_DIAG_LANE_EVENTS */,
-                               uint32_t min_thr = 0 /* ZSW_OPTION_MIN_SCORE: min_threshold(), 0 = off */, uint32_t* min_counts = nullptr /* [0] seed, [1] band */,
-                               // co (with n0): the caller's side of handback_coschedule (two_tiers and diagonal are filled in here). If the
-                               // decision holds, *fail_count as the seed kernel left it is copied to the device word n0 and the first tier's
-                               // launch scores fail_list[0, *n0) itself, with a2's tables: the caller's launches start at *n0
-                               // (ScoreArgsV2::first_item_dev). *coscheduled says whether that happened; if not, n0 is not written.
-                               const CoscheduleCase* co = nullptr, uint32_t* n0 = nullptr, bool* coscheduled = nullptr,
-                               bool plain_seed_kernel = false /* ZSW_DEBUG_SEED_PLAIN_KERNEL */);
+// ws.seed_gtab holds two such tables: the plain one, then the one of the DOUBLED scoring (the banded kernel's domain)
+inline uint2* seed_gtab_band(const ScoreWorkspace& ws, uint32_t ref_len) { return ws.seed_gtab + (ref_len + 2 * SEED_GTAB_PAD); }
+// What one seeded range owns, derived together from its offsets into the workspace and the worklist and from its counter
+struct SeedRegion {
+    uint8_t* work;         // seed_workspace_bytes(n_items, max_len, band_grid_cap) bytes
+    size_t work_bytes;
+    uint32_t* fail_list;   // its part of the hand-back list
+    uint32_t* fail_count;  // ... and the list's count (not reset by launch_score_seeded)
+    uint32_t* n0;          // the device word for the co-scheduled part of the list (below)
+};
+// Seeds, sorts and runs the banded kernel — or the window kernel, in strip configuration G x C of a2's tables — over the items of
+// a2.b; reads without an anchor and reads whose bounds fail are appended to r.fail_list. Index, per-row tables, debug bits (decoded
+// where each is used), band records, window timer, launch log and minimum-score counters are the workspace's; a2.out says whether
+// the pass stops after its narrow tier and whether it reads the reads back to front.
+// band_tabs: non-null = the banded kernel may run: drift constants of the DOUBLED scoring (ge2, gd2, floor0, K, limit).
+// row_chunks: the caller cuts the hand-backs into chunks of rows, the one fact of handback_coschedule only it knows. If that decision
+// holds, *r.fail_count as the seed kernel left it is copied to *r.n0 and the first tier's launch scores fail_list[0, *n0) itself,
+// with a2's tables: the caller's launches start at *n0 (ScoreArgsV2::first_item_dev). *coscheduled: whether that happened.
+hipError_t launch_score_seeded(const ScoreArgsV2& a2, int G, int C, uint32_t max_len, const ScoreWorkspace& ws, const SeedRegion& r, int mode,
+                               const ScoreArgsV2* band_tabs, uint32_t band_grid_cap, bool row_chunks, bool* coscheduled, hipStream_t stream);
 // (Re)builds the index for a reference given as residue indices on the host.
 hipError_t seed_index_update(SeedIndex* ix, const ScoringDev& sc, const uint8_t* h_ref, size_t ref_len);
 void seed_index_release(SeedIndex* ix);
