@@ -105,6 +105,27 @@ pub const ZSW_ANNOTATE_READ_IS_REF: i32 = 1;
 pub const ZSW_ANNOTATE_SHARED: i32 = 2;
 pub const ZSW_ANNOTATE_MATCH_RESIDUES: i32 = 4;
 
+/// `zsw_site_counts`: one site of the table of `zsw_pileup_batch` — `NucleotideCounts<u32>` in the order of `into_inner()`:
+/// A, C, G, T/U, N, gap, other IUPAC, invalid
+#[repr(C)]
+#[derive(Clone, Copy, Default, Debug, PartialEq, Eq)]
+pub struct ZswSiteCounts {
+    pub bin: [u32; 8],
+}
+
+/// `zsw_site_insertions`: the insertions in front of one position (`zsw_pileup_batch`)
+#[repr(C)]
+#[derive(Clone, Copy, Default, Debug, PartialEq, Eq)]
+pub struct ZswSiteInsertions {
+    pub runs:  u32,
+    pub bases: u32,
+}
+
+/// flag of `zsw_pileup_batch`, beside the `ZSW_ANNOTATE_*` role bits: zero the tables first
+pub const ZSW_PILEUP_CLEAR: i32 = 8;
+/// flag of `zsw_consensus_from_counts`: a site without any A C G T N count takes the fallback's byte
+pub const ZSW_CONSENSUS_KEEP_UNCOVERED: i32 = 1;
+
 /// `zsw_sam_fields`: what a SAM line holds beside the record (`zsw_sam_batch`); every array lives where the batch does, but `rname`
 #[repr(C)]
 #[derive(Clone, Copy, Debug)]
@@ -214,6 +235,8 @@ unsafe extern "C" {
     fn zsw_set_option(ctx: *mut ZswContext, option: i32, value: i64) -> i32;
     fn zsw_min_score_counts(ctx: *mut ZswContext, out: *mut u64) -> i32;
     fn zsw_annotate_batch(ctx: *mut ZswContext, reads: *const ZswBatch, flags: i32, aln: *const ZswAlignment, status: *const u8, inc: *const u32, op: *const u8, n_ciglets: u64, out_stats: *mut c_void, out_aln: *mut ZswAlignment, out_inc: *mut u32, out_op: *mut u8, ciglet_cap: u64, out_n_ciglets: *mut u64, stream: *mut c_void) -> i32;
+    fn zsw_pileup_batch(ctx: *mut ZswContext, reads: *const ZswBatch, flags: i32, aln: *const ZswAlignment, status: *const u8, inc: *const u32, op: *const u8, n_ciglets: u64, counts: *mut c_void, ins: *mut c_void, out_n_bad: *mut u64, stream: *mut c_void) -> i32;
+    fn zsw_consensus_from_counts(ctx: *mut ZswContext, counts: *const c_void, len: u64, mem: i32, flags: i32, fallback: *const u8, out_seq: *mut u8, stream: *mut c_void) -> i32;
     fn zsw_sam_batch(ctx: *mut ZswContext, reads: *const ZswBatch, fields: *const c_void, flags: i32, aln: *const ZswAlignment, status: *const u8, inc: *const u32, op: *const u8, n_ciglets: u64, out_text: *mut u8, text_cap: u64, out_n_bytes: *mut u64, out_line_offsets: *mut u64, out_n_bad: *mut u64, stream: *mut c_void) -> i32;
 }
 
@@ -849,6 +872,50 @@ impl GpuContext {
             oop.truncate(needed as usize);
             return Ok((stats, Some((out, oinc, oop))));
         }
+    }
+
+    /// `zsw_pileup_batch` over the raw records of an alignment call on this context: the records piled up over the sequence the
+    /// flags name (`len` bases, set on this context) — per position how often a read byte of each bin stood opposite it, and with
+    /// `ins` the insertion runs and bases in front of each position (`len + 1` entries). The call adds to `counts` and `ins`, so
+    /// batches accumulate; `ZSW_PILEUP_CLEAR` zeroes them first. `flags`: `ZSW_ANNOTATE_READ_IS_REF` / `ZSW_ANNOTATE_SHARED` by the
+    /// call that produced the records. -> the number of records that are no alignments of their reads (they count nothing).
+    #[allow(clippy::too_many_arguments)]
+    pub fn pileup_batch<Q: AsRef<[u8]>>(
+        &self, reads: &[Q], flags: i32, recs: &[ZswAlignment], status: &[u8], inc: &[u32], op: &[u8], counts: &mut [ZswSiteCounts],
+        ins: Option<&mut [ZswSiteInsertions]>,
+    ) -> Result<u64, GpuError> {
+        assert!(recs.len() == reads.len() && status.len() == reads.len() && inc.len() == op.len());
+        if let Some(t) = &ins {
+            assert_eq!(t.len(), counts.len() + 1);
+        }
+        let batch = HostBatch::new(reads);
+        let mut n_bad = 0u64;
+        let ins_ptr = ins.map_or(ptr::null_mut(), |t| t.as_mut_ptr().cast::<c_void>());
+        // SAFETY: counts holds one entry per position of the configured sequence (the library checks nothing else about it), ins one more
+        let code = unsafe {
+            zsw_pileup_batch(self.raw, &batch.as_c(), flags, recs.as_ptr(), status.as_ptr(), inc.as_ptr(), op.as_ptr(), inc.len() as u64,
+                             counts.as_mut_ptr().cast::<c_void>(), ins_ptr, &mut n_bad, ptr::null_mut())
+        };
+        self.check(code, 0, 0)?;
+        Ok(n_bad)
+    }
+
+    /// `zsw_consensus_from_counts`: `CreateConsensus::plurality_acgtn` of a table of `pileup_batch` — per site the most frequent of
+    /// A C G T N, ties in that order. `fallback`: sites without any such count keep its byte (`ZSW_CONSENSUS_KEEP_UNCOVERED`).
+    pub fn consensus_from_counts(&self, counts: &[ZswSiteCounts], fallback: Option<&[u8]>) -> Result<Vec<u8>, GpuError> {
+        if let Some(f) = fallback {
+            assert_eq!(f.len(), counts.len());
+        }
+        let mut out = vec![0u8; counts.len().max(1)];
+        let flags = if fallback.is_some() { ZSW_CONSENSUS_KEEP_UNCOVERED } else { 0 };
+        // SAFETY: out holds one byte per site; mem 0 = ZSW_MEM_HOST
+        let code = unsafe {
+            zsw_consensus_from_counts(self.raw, counts.as_ptr().cast::<c_void>(), counts.len() as u64, 0, flags, fallback.map_or(ptr::null(), |f| f.as_ptr()),
+                                      out.as_mut_ptr(), ptr::null_mut())
+        };
+        self.check(code, 0, 0)?;
+        out.truncate(counts.len());
+        Ok(out)
     }
 
     /// `zsw_sam_batch`: the SAM body for the raw records of an alignment call (or of `annotate_batch`), one line per read — what

@@ -5,6 +5,7 @@
 //
 //   g++ -O2 -std=c++17 -Iinclude examples/zsw_driver.cpp -o examples/zsw_driver -Lzoe_amd -lzoe_sw_hip -Wl,-rpath,$PWD/zoe_amd
 //   ./examples/zsw_driver reference.txt reads.fastq [--score-only | --3pass | --both-strands] [--min-score T] [--nm] [--verbose-cigar] [--device-sam]
+//                         [--consensus FILE]
 // --both-strands: every read is aligned on whichever strand scores higher (sw_align_strands_from_i8_3pass); a read answered by
 // its reverse complement gets flag 16, SEQ reverse complemented and QUAL reversed, and POS / CIGAR are those of that sequence.
 // --min-score T (with --3pass or --score-only, the calls ZSW_OPTION_MIN_SCORE covers): a read that scores less than T is written as
@@ -14,6 +15,9 @@
 // the output is what it always was.
 // --device-sam: the records are formatted on the GPU (zsw_sam_batch) and the body is written with one fwrite; the same bytes as
 // without it, under every option above. Without the flag neither the output nor the code path changes.
+// --consensus FILE: beside the SAM output, the plurality consensus of the run as a one-record FASTA: the alignments piled up over the
+// reference on the GPU (zsw_pileup_batch; under --both-strands from the reads as aligned), per position the most frequent of A C G T N
+// (zsw_consensus_from_counts), and the reference's own base where no read covers it.
 #include <algorithm>
 #include <cstdio>
 #include <cstdlib>
@@ -43,11 +47,12 @@ static std::string read_reference(const std::string& path, std::string* name) {
 
 int main(int argc, char** argv) {
     if (argc < 3) {
-        std::cerr << "usage: zsw_driver reference.(fa|txt) reads.fastq [--score-only | --3pass | --both-strands] [--min-score T] [--nm] [--verbose-cigar] [--device-sam]\n";
+        std::cerr << "usage: zsw_driver reference.(fa|txt) reads.fastq [--score-only | --3pass | --both-strands] [--min-score T] [--nm] [--verbose-cigar] [--device-sam] [--consensus FILE]\n";
         return 2;
     }
     bool score_only = false, three_pass = false, both_strands = false, nm = false, verbose_cigar = false, device_sam = false;
     long long min_score = 0;
+    std::string consensus_path;
     for (int k = 3; k < argc; ++k) {
         if (!std::strcmp(argv[k], "--score-only")) score_only = true;
         else if (!std::strcmp(argv[k], "--3pass")) three_pass = true;  // sw_align_from_i8_3pass instead of sw_align_from_i8
@@ -56,6 +61,7 @@ int main(int argc, char** argv) {
         else if (!std::strcmp(argv[k], "--nm")) nm = true;
         else if (!std::strcmp(argv[k], "--verbose-cigar")) verbose_cigar = true;
         else if (!std::strcmp(argv[k], "--device-sam")) device_sam = true;
+        else if (!std::strcmp(argv[k], "--consensus") && k + 1 < argc) consensus_path = argv[++k];
         else {
             std::cerr << "zsw_driver: unknown argument " << argv[k] << '\n';
             return 2;
@@ -63,6 +69,10 @@ int main(int argc, char** argv) {
     }
     if (min_score < 0 || min_score > 0x7fffffffll || (min_score > 0 && !(score_only || three_pass))) {
         std::cerr << "zsw_driver: --min-score takes a value in 1 .. 2^31 - 1 and goes with --3pass or --score-only\n";
+        return 2;
+    }
+    if (score_only && !consensus_path.empty()) {
+        std::cerr << "zsw_driver: --consensus needs alignments; it does not go with --score-only\n";
         return 2;
     }
     try {
@@ -91,6 +101,12 @@ int main(int argc, char** argv) {
         auto alns = both_strands ? profiles.sw_align_strands_from_i8_3pass(reference)
                     : three_pass ? profiles.sw_align_from_i8_3pass(reference)
                                  : profiles.sw_align_from_i8(reference);
+        if (!consensus_path.empty()) {
+            const zoe::Pileup pile = profiles.pileup(alns, reference, false, false, both_strands ? &profiles.last_strands() : nullptr);
+            std::ofstream fa(consensus_path);
+            if (!fa) throw std::runtime_error("cannot write " + consensus_path);
+            fa << '>' << ref_name << "_consensus\n" << ctx.plurality_acgtn(pile.counts, &reference) << '\n';
+        }
         zoe::Annotation ann;  // NM and = / X CIGARs: one pass over the alignments, against the reads as aligned
         if (nm || verbose_cigar) ann = profiles.annotate(alns, reference, false, false, verbose_cigar, both_strands ? &profiles.last_strands() : nullptr);
         if (device_sam) {  // the body from zsw_sam_batch: SEQ oriented, QUAL reversed and the decimals written on the device

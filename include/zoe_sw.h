@@ -387,6 +387,66 @@ zsw_error zsw_sam_batch(zsw_context* ctx, const zsw_batch* reads, const void* fi
                         uint64_t text_cap, uint64_t* out_n_bytes, uint64_t* out_line_offsets /* optional, n_reads + 1 */,
                         uint64_t* out_n_bad, void* stream);
 
+/* ---- pile-up: per-site base counts and the plurality consensus ------------------------------------ */
+/* zsw_pileup_batch reduces the records of an alignment call to one table over the context's sequence, the one the reads were
+ * aligned to: counts[pos].bin[b] = how often a byte of bin b stood opposite position pos. What AlignmentComposition::per_site_counts
+ * (src/composition/by_position/mod.rs:248-287) gives over the query rows of pairwise_align_with (src/alignment/pairwise.rs:26-65),
+ * placed at the positions of the reference row. The eight bins, in the order of NucleotideCounts::into_inner():
+ *   0 `A a`   1 `C c`   2 `G g`   3 `T t U u`   4 `N n`   5 `-`   6 the other IUPAC letters R Y S W K M B D H V in either case and `.`
+ *   7 every other byte.  The bins do not depend on the context's index_map.
+ * flags: ZSW_ANNOTATE_READ_IS_REF and ZSW_ANNOTATE_SHARED with the meaning they have for zsw_annotate_batch (which sequence the
+ * record's ref_* index, and which of the context's two sequences is meant; the table above says which call needs which), and
+ * ZSW_PILEUP_CLEAR. ZSW_ANNOTATE_MATCH_RESIDUES is not accepted. The record's reference cursor starts at ref_start, its query cursor
+ * at 0; S moves the query cursor, H and P do nothing.
+ *   without READ_IS_REF (record reference = the sequence, record query = the read):
+ *     M = X   counts[pos].bin[bin(read byte)] += 1 for each of the inc columns
+ *     D       counts[pos].bin[5] += 1 for each of the inc positions
+ *     N       counts[pos].bin[4] += 1 for each of the inc positions (the reference writes literal N bytes there)
+ *     I       no site count; ins[p].runs += 1 and ins[p].bases += inc with p the reference cursor: the insertion lies in front of
+ *             position p, p in 0..=len
+ *   with READ_IS_REF (record query = the sequence, record reference = the read) the gap ops change places: I is the gap bin at
+ *     inc positions, D goes to ins[] at the query cursor, N counts nothing and moves the read cursor, S skips positions of the
+ *     sequence without counting them, columns count bin(read byte) at the query cursor's position.
+ * Positions the ciglets do not cover get nothing. len = the length of the sequence the flags name; counts: len zsw_site_counts;
+ * ins: optional, len + 1 zsw_site_insertions (both declared void*, as out_stats of zsw_annotate_batch: the arrays convert without
+ * a cast). The call ADDS to both tables, so batches accumulate; ZSW_PILEUP_CLEAR zeroes them first. The counters are 32-bit and
+ * wrap: a site covered by more than 2^32 - 1 reads is the caller's concern. All arithmetic is modulo 2^32 and addition commutes:
+ * the table is the same on every run.
+ * All or nothing: a read contributes only if status[i] == ZSW_STATUS_SOME and its record passes the checks of zsw_annotate_batch
+ * that need no base: the ciglets inside [0, n_ciglets), ranges and lengths that agree with the actual sequences, no inc of 0, no
+ * op outside MIDNSHP=X, and no ciglet that leaves either sequence (the reference's within [ref_start, ref_end)). Every other
+ * ZSW_STATUS_SOME record contributes nothing at all and is counted in *out_n_bad (host memory). The ciglets are validated in a pass
+ * of their own before a counter is touched, and every index derived from caller memory is checked in 64-bit arithmetic before
+ * the load or add that uses it: a malformed record is a count, never a fault.
+ * Every array lives where reads->mem says, except out_n_bad. Device batches synchronise the stream once, for *out_n_bad. Host
+ * batches are staged and the call is synchronous: the host tables are copied in, added to and copied back. n_reads == 0 is ZSW_OK
+ * and, without ZSW_PILEUP_CLEAR, leaves the tables as they were. Unknown flag bits, a null required pointer (reads, out_n_bad,
+ * counts; bases, aln, status with reads; inc / op with n_ciglets), or a table that overlaps an input or the other table:
+ * ZSW_ERR_INVALID_ARGUMENT, nothing written. The sequence the flags name not set: ZSW_ERR_NOT_CONFIGURED (scoring is not needed).
+ * ZSW_ENCODING_PACKED4, or a sequence of 2^31 - 1 bases or more: ZSW_ERR_UNSUPPORTED.
+ * Workspace, kept by the context until zsw_destroy: 16 bytes per position of the sequence (three difference arrays and the per-site
+ * mismatches, see zoe_amd/csrc/zsw_pileup.hpp, which also has the lanes per alignment, the alignments per block and the sequence
+ * length up to which a block accumulates in LDS), the scan's scratch, and the staged arrays and tables of a host batch.
+ * zsw_group_* does not cover the call: the sum across GPUs is one all-reduce of the table and is left to the caller.
+ *
+ * zsw_consensus_from_counts: out_seq[pos] = NucleotideCounts::plurality_acgtn (by_position/mod.rs:147-162) of counts[pos]: the
+ * largest of bins 0..4, ties in the order A > C > G > T > N by strict >, so a site without any such count is `A`; the gap bin never
+ * wins. With ZSW_CONSENSUS_KEEP_UNCOVERED a site whose bins 0..4 are all zero takes fallback[pos] instead (what a refinement loop
+ * wants for the uncovered ends). counts, fallback and out_seq live where `mem` says; a device call is asynchronous on `stream`, a
+ * host call is staged and synchronous. out_seq in device memory is a valid argument of zsw_set_reference(.., ZSW_MEM_DEVICE): a
+ * refinement round never leaves the card. Needs neither scoring nor a sequence. Unknown flag bits, a null required pointer, or
+ * out_seq over an input: ZSW_ERR_INVALID_ARGUMENT; len == 0: ZSW_OK. */
+typedef struct zsw_site_counts { uint32_t bin[8]; } zsw_site_counts;             /* NucleotideCounts<u32> */
+typedef struct zsw_site_insertions { uint32_t runs, bases; } zsw_site_insertions;
+enum { ZSW_PILEUP_CLEAR = 8 };             /* beside the ZSW_ANNOTATE_* role bits */
+zsw_error zsw_pileup_batch(zsw_context* ctx, const zsw_batch* reads, int flags, const zsw_alignment* aln, const uint8_t* status,
+                           const uint32_t* inc, const uint8_t* op, uint64_t n_ciglets, void* counts /* len zsw_site_counts */,
+                           void* ins /* optional, len + 1 zsw_site_insertions */, uint64_t* out_n_bad /* host */, void* stream);
+enum { ZSW_CONSENSUS_KEEP_UNCOVERED = 1 };
+zsw_error zsw_consensus_from_counts(zsw_context* ctx, const void* counts, uint64_t len, zsw_mem mem, int flags,
+                                    const uint8_t* fallback /* len bytes, with KEEP_UNCOVERED */, uint8_t* out_seq /* len */,
+                                    void* stream);
+
 /* ---- pre-alignment filter ------------------------------------------------------------------ */
 /* out_pass[i] = sneaky_snake(&reference[ref_start[i] .. ref_start[i]+ref_len[i]], read_i, threshold)
  * (src/alignment/sneaky_snake.rs:78-131): the SneakySnake edit-distance filter between a read and a candidate window of the

@@ -156,6 +156,15 @@ struct Annotation {
     uint32_t nm(size_t i) const { return stats[i].mismatches + stats[i].ins_bases + stats[i].del_bases; }
 };
 
+// What pileup() of the profile classes returns (zsw_pileup_batch): per position of the sequence the reads were aligned to, how often a
+// read byte of each bin (A, C, G, T/U, N, gap, other IUPAC, invalid) stood opposite it; with `insertions`, per position the
+// insertion runs and bases in front of it (len + 1 entries). Passed back in, a later call adds to it.
+struct Pileup {
+    std::vector<zsw_site_counts> counts;
+    std::vector<zsw_site_insertions> insertions;  // empty without `insertions`
+    uint64_t n_bad = 0;                           // records that are no alignments of their reads to the sequence: they count nothing
+};
+
 class GpuContext {
   public:
     explicit GpuContext(int device = 0) {
@@ -219,6 +228,35 @@ class GpuContext {
             out.verbose[i].value.states.clear();
             for (uint32_t k = 0; k < vrec[i].n_ciglets; ++k) out.verbose[i].value.states.push_back({vinc[vrec[i].ciglet_offset + k], vop[vrec[i].ciglet_offset + k]});
         }
+        return out;
+    }
+    // zsw_pileup_batch over alignments that a call on `reads` (a host batch: the reads as aligned) returned, with the sequence the
+    // flags name (len bases) set on this context. flags: ZSW_ANNOTATE_READ_IS_REF / ZSW_ANNOTATE_SHARED. `into`: the table of an
+    // earlier call over the same sequence, which is added to.
+    Pileup pileup(const zsw_batch& reads, int flags, const std::vector<MaybeAligned<Alignment>>& alns, size_t len, bool insertions, const Pileup* into = nullptr) const {
+        if (alns.size() != reads.n_reads) throw GpuError(ZSW_ERR_INVALID_ARGUMENT, "one alignment per read");
+        std::vector<zsw_alignment> rec;
+        std::vector<uint8_t> status;
+        std::vector<uint32_t> inc;
+        std::vector<uint8_t> op;
+        flatten(alns, rec, status, inc, op);
+        Pileup out;
+        if (into) out = *into;
+        out.counts.resize(len);
+        if (insertions) out.insertions.resize(len + 1);
+        uint64_t n_bad = 0;
+        check(zsw_pileup_batch(ctx_, &reads, flags, rec.data(), status.data(), inc.data(), op.data(), inc.size(), out.counts.data(),
+                               insertions ? out.insertions.data() : nullptr, &n_bad, nullptr));
+        out.n_bad += n_bad;
+        return out;
+    }
+    // zsw_consensus_from_counts: CreateConsensus::plurality_acgtn of a table of pileup(); fallback: positions without any A C G T N
+    // count keep its byte (ZSW_CONSENSUS_KEEP_UNCOVERED)
+    std::string plurality_acgtn(const std::vector<zsw_site_counts>& counts, const std::string* fallback = nullptr) const {
+        if (fallback && fallback->size() != counts.size()) throw GpuError(ZSW_ERR_INVALID_ARGUMENT, "one fallback byte per position");
+        std::string out(counts.size(), 'A');
+        check(zsw_consensus_from_counts(ctx_, counts.data(), counts.size(), ZSW_MEM_HOST, fallback ? ZSW_CONSENSUS_KEEP_UNCOVERED : 0,
+                                        fallback ? reinterpret_cast<const uint8_t*>(fallback->data()) : nullptr, reinterpret_cast<uint8_t*>(&out[0]), nullptr));
         return out;
     }
     // zsw_sam_batch over alignments that a call on `reads` (a host batch: the reads as aligned) returned: the SAM body, one line per
@@ -355,6 +393,23 @@ class ProfileBatchBase {
             b.bases = oriented.data();
         }
         return ctx_.annotate(b, (seq_is_query ? ZSW_ANNOTATE_READ_IS_REF : 0) | (residues ? ZSW_ANNOTATE_MATCH_RESIDUES : 0), alns, verbose);
+    }
+    // zsw_pileup_batch over the alignments `alns` that one of this batch's alignment calls returned for `seq` (with the same
+    // seq_is_query): the table over `seq`. strand: the strands of a strand-aware call, whose alignments are piled up from the reads
+    // as aligned (zsw_orient_batch). into: the table of an earlier call over the same `seq`, which is added to.
+    // ctx.plurality_acgtn(pileup.counts) is the consensus.
+    Pileup pileup(const std::vector<MaybeAligned<Alignment>>& alns, const std::string& seq, bool seq_is_query = false, bool insertions = false,
+                  const std::vector<uint8_t>* strand = nullptr, const Pileup* into = nullptr) {
+        set_reference(seq);
+        zsw_batch b = batch();
+        std::vector<uint8_t> oriented;
+        if (strand) {
+            if (strand->size() != size()) throw GpuError(ZSW_ERR_INVALID_ARGUMENT, "one strand per read");
+            oriented.resize(bases_.size());
+            ctx_.check(zsw_orient_batch(ctx_.raw(), &b, strand->data(), oriented.data(), nullptr));
+            b.bases = oriented.data();
+        }
+        return ctx_.pileup(b, seq_is_query ? ZSW_ANNOTATE_READ_IS_REF : 0, alns, seq.size(), insertions, into);
     }
     // zsw_sam_batch: the SAM body for the alignments `alns` of this batch (those of an alignment call, or Annotation::verbose for
     // = / X CIGARs), one line per read in read order, as `SamData::from_alignment(..)` / `SamData::unmapped(..)` print them — without
@@ -602,7 +657,8 @@ class LocalProfilesBatch : public ProfileBatchBase {
 // sequence unless seq_is_query (SeqSrc::Query(read), alignment/mod.rs:176-190) hands the roles back.
 class SharedProfileBase {
   protected:
-    SharedProfileBase(GpuContext& ctx, const std::string& sequence, const WeightMatrix& matrix, int8_t gap_open, int8_t gap_extend) : ctx_(ctx) {
+    SharedProfileBase(GpuContext& ctx, const std::string& sequence, const WeightMatrix& matrix, int8_t gap_open, int8_t gap_extend)
+        : ctx_(ctx), seq_len_(sequence.size()) {
         if (sequence.empty()) throw ProfileError(1);  // StripedProfile::new -> ProfileError::EmptySequence (profile.rs:32-44)
         ctx_.check(zsw_set_scoring(ctx_.raw(), matrix.weights.data(), matrix.S, matrix.mapping->index_map.data(), gap_open, gap_extend));
         ctx_.check(zsw_set_profile_sequence(ctx_.raw(), (const uint8_t*)sequence.data(), sequence.size(), ZSW_MEM_HOST));
@@ -663,8 +719,16 @@ class SharedProfileBase {
         return out;
     }
     GpuContext& ctx_;
+    size_t seq_len_;  // of the profile's sequence
 
   public:
+    // zsw_pileup_batch over the alignments one of this profile's alignment calls returned for `reads` (with the same seq_is_query):
+    // the table over the profile's own sequence; results as ProfileBatchBase::pileup
+    Pileup pileup(const std::vector<MaybeAligned<Alignment>>& alns, const std::vector<std::string>& reads, bool seq_is_query = true, bool insertions = false,
+                  const Pileup* into = nullptr) {
+        const HostReads h = pack(reads);
+        return ctx_.pileup(h.batch(), ZSW_ANNOTATE_SHARED | (seq_is_query ? 0 : ZSW_ANNOTATE_READ_IS_REF), alns, seq_len_, insertions, into);
+    }
     // zsw_annotate_batch over the alignments one of this profile's alignment calls returned for `reads` (with the same seq_is_query);
     // results as ProfileBatchBase::annotate
     Annotation annotate(const std::vector<MaybeAligned<Alignment>>& alns, const std::vector<std::string>& reads, bool seq_is_query = true, bool residues = false,

@@ -53,7 +53,7 @@ SYMBOLS = [
     "zsw_group_set_reference", "zsw_group_score_batch_from", "zsw_group_score_batch_from_device", "zsw_group_align_batch_from",
     "zsw_group_align_3pass_batch_from",
     "zsw_set_complement", "zsw_score_strands_batch_from", "zsw_orient_batch", "zsw_align_3pass_strands_batch_from", "zsw_strand_counts", "zsw_debug_strand_records", "zsw_debug_score_launches",
-    "zsw_min_score_counts", "zsw_annotate_batch", "zsw_sam_batch",
+    "zsw_min_score_counts", "zsw_annotate_batch", "zsw_sam_batch", "zsw_pileup_batch", "zsw_consensus_from_counts",
 ]
 
 
@@ -116,6 +116,11 @@ class ZswSamFields(C.Structure):
 
 
 SAM_OMIT_SEQ = 1
+
+# zsw_pileup_batch / zsw_consensus_from_counts: the flag beside the ANNOTATE_* role bits, the bins of a zsw_site_counts
+PILEUP_CLEAR = 8
+CONSENSUS_KEEP_UNCOVERED = 1
+PILEUP_BINS = ("A", "C", "G", "T", "N", "-", "other", "invalid")
 
 
 class ZswError(RuntimeError):
@@ -215,5 +220,7 @@ def load() -> C.CDLL:
     lib.zsw_annotate_batch.argtypes = [vp, C.POINTER(ZswBatch), C.c_int, vp, u8p, u32p, u8p, C.c_uint64, vp, vp, u32p, u8p, C.c_uint64, C.POINTER(C.c_uint64), vp]
     lib.zsw_sam_batch.argtypes = [vp, C.POINTER(ZswBatch), C.POINTER(ZswSamFields), C.c_int, vp, u8p, u32p, u8p, C.c_uint64, u8p, C.c_uint64, C.POINTER(C.c_uint64),
                                   u64p, C.POINTER(C.c_uint64), vp]
+    lib.zsw_pileup_batch.argtypes = [vp, C.POINTER(ZswBatch), C.c_int, vp, u8p, u32p, u8p, C.c_uint64, vp, vp, C.POINTER(C.c_uint64), vp]
+    lib.zsw_consensus_from_counts.argtypes = [vp, vp, C.c_uint64, C.c_int, C.c_int, u8p, u8p, vp]
     _lib = lib
     return lib

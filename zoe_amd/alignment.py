@@ -626,6 +626,71 @@ def _annotate(ctx: "SwContext", rb: "ReadBatch", aln: AlignmentBatch, flags: int
     return AlignmentBatch(aln.status, h_out.view(ALN_DTYPE), h_inc.view(np.uint32), h_op, aln.tier, aln.strand), h_stats.view(STATS_DTYPE)
 
 
+def _pileup(ctx: "SwContext", rb: "ReadBatch", aln: AlignmentBatch, flags: int, seq_len: int, counts, insertions: bool):
+    """zsw_pileup_batch over the records of `aln` (host arrays: they are uploaded), with the sequence the flags name set on the context
+    by the caller. counts: None (a new table) or the (seq_len, 8) CUDA int32 tensor of an earlier call, which is added to.
+    -> the table, or with `insertions` (the table, a (seq_len + 1, 2) CUDA int32 tensor of runs and bases in front of each position)"""
+    torch = _torch()
+    n, dev = rb.n_reads, rb.bases.device
+    if len(aln.status) != n:
+        raise ValueError("the alignments are not those of this batch of reads")
+    if counts is None:
+        counts = torch.zeros((seq_len, len(_lib.PILEUP_BINS)), dtype=torch.int32, device=dev)
+    elif not (counts.is_cuda and counts.dtype == torch.int32 and counts.is_contiguous() and tuple(counts.shape) == (seq_len, 8)):
+        raise ValueError("counts: the contiguous (len, 8) CUDA int32 tensor of an earlier pileup over this sequence")
+    ins = torch.zeros((seq_len + 1, 2), dtype=torch.int32, device=dev) if insertions else None
+    up = lambda a, dt: torch.from_numpy(np.ascontiguousarray(a).view(dt).reshape(-1).copy() if a.size else np.zeros(1, dtype=dt)).to(dev)
+    d_aln, d_status = up(aln.records, np.uint8), up(aln.status, np.uint8)
+    d_inc, d_op = up(aln.inc, np.int32), up(aln.op, np.uint8)
+    b = rb.c_batch()
+    n_bad = C.c_uint64(0)
+    ctx.check(ctx.lib.zsw_pileup_batch(ctx.h, C.byref(b), flags, d_aln.data_ptr(), d_status.data_ptr(), d_inc.data_ptr(), d_op.data_ptr(), int(aln.inc.size),
+                                       counts.data_ptr() if seq_len else None, ins.data_ptr() if insertions else None, C.byref(n_bad), ctx.stream()),
+              profile_errors=False)
+    torch.cuda.synchronize(dev)
+    if n_bad.value:
+        raise ValueError(f"{n_bad.value} records are not alignments of these reads to this sequence")
+    return (counts, ins) if insertions else counts
+
+
+def plurality_acgtn(counts, fallback=None):
+    """zsw_consensus_from_counts: `CreateConsensus::plurality_acgtn` of a (len, 8) table of `pileup` — per site the most frequent of
+    A C G T N, ties in that order, so `A` where nothing was counted. fallback (bytes, or a CUDA uint8 tensor of len entries): sites
+    without any A C G T N count take its byte instead. counts on a GPU -> a CUDA uint8 tensor, which `SwContext.set_reference`
+    takes as it is (zsw_set_reference with ZSW_MEM_DEVICE); a numpy array -> bytes."""
+    torch = _torch()
+    host = not isinstance(counts, torch.Tensor)
+    if host:
+        t = np.ascontiguousarray(counts, dtype=np.uint32)
+        device = 0
+    else:
+        t = counts.contiguous()
+        if not t.is_cuda or t.dtype != torch.int32:
+            raise ValueError("counts: a CUDA int32 tensor or a numpy array")
+        device = t.device.index
+    if t.ndim != 2 or t.shape[1] != 8:
+        raise ValueError("counts: (len, 8)")
+    n = int(t.shape[0])
+    ctx = SwContext.get(device)
+    flags = _lib.CONSENSUS_KEEP_UNCOVERED if fallback is not None else 0
+    if host:
+        fb = np.frombuffer(bytes(fallback), dtype=np.uint8) if fallback is not None else None
+        out = np.zeros(max(n, 1), dtype=np.uint8)
+        if fb is not None and fb.size != n:
+            raise ValueError("fallback: one byte per site")
+        ctx.check(ctx.lib.zsw_consensus_from_counts(ctx.h, t.ctypes.data if n else None, n, _lib.MEM_HOST, flags, fb.ctypes.data if fb is not None and n else None,
+                                                    out.ctypes.data, None), profile_errors=False)
+        return out[:n].tobytes()
+    if fallback is not None and not isinstance(fallback, torch.Tensor):
+        fallback = torch.from_numpy(np.frombuffer(bytes(fallback), dtype=np.uint8).copy()).to(t.device)
+    if fallback is not None and (fallback.numel() != n or fallback.dtype != torch.uint8 or not fallback.is_cuda):
+        raise ValueError("fallback: one byte per site")
+    out = torch.empty(max(n, 1), dtype=torch.uint8, device=t.device)
+    ctx.check(ctx.lib.zsw_consensus_from_counts(ctx.h, t.data_ptr() if n else None, n, _lib.MEM_DEVICE, flags, fallback.contiguous().data_ptr() if fallback is not None and n else None,
+                                                out.data_ptr(), ctx.stream()), profile_errors=False)
+    return out[:n]
+
+
 def _sam_text(ctx: "SwContext", rb: "ReadBatch", aln: AlignmentBatch, qnames, quals, rname, mapq: int, strands, stats, omit_seq: bool, device_out: bool):
     """zsw_sam_batch over the records of `aln` (host arrays: they are uploaded) beside the reads `rb` as aligned.
     -> bytes, or with device_out (a CUDA uint8 tensor with the text, a CUDA int64 tensor with the n + 1 line offsets)"""
@@ -782,6 +847,19 @@ class _ProfileBatchBase:
             reads = self.ctx.orient(reads, _torch().from_numpy(np.ascontiguousarray(aln.strand, dtype=np.uint8)).to(reads.bases.device))
         flags = (_lib.ANNOTATE_READ_IS_REF if seq.is_query else 0) | (_lib.ANNOTATE_MATCH_RESIDUES if residues else 0)
         return _annotate(self.ctx, reads, aln, flags, verbose)
+
+    def pileup(self, aln: AlignmentBatch, seq: SeqSrc, counts=None, insertions: bool = False):
+        """zsw_pileup_batch over the alignments `aln` that one of this batch's alignment calls returned for `seq` (the same SeqSrc):
+        -> the (len(seq), 8) CUDA int32 table of how often a read byte of each bin — _lib.PILEUP_BINS: A C G T/U N, gap, other IUPAC,
+        invalid — stood opposite each position of `seq` (`AlignmentComposition::per_site_counts` in the coordinates of `seq`).
+        counts: the table of an earlier call, which is added to (batches accumulate). insertions: also the (len + 1, 2) table of
+        insertion runs and bases in front of each position. `plurality_acgtn(counts)` is the consensus. Alignments of a
+        strand-aware call are piled up from the reads as aligned (strand 1: the reverse complement)."""
+        self._prep(seq.seq)
+        reads = self.reads
+        if aln.strand is not None:
+            reads = self.ctx.orient(reads, _torch().from_numpy(np.ascontiguousarray(aln.strand, dtype=np.uint8)).to(reads.bases.device))
+        return _pileup(self.ctx, reads, aln, _lib.ANNOTATE_READ_IS_REF if seq.is_query else 0, len(seq.seq), counts, insertions)
 
     def to_sam_text(self, aln: AlignmentBatch, qnames, quals=None, rname="ref", mapq: int = 255, strands=None, stats=None, omit_seq: bool = False,
                     device: bool = False):
@@ -1148,6 +1226,15 @@ class _SharedBase:
         self._prep()
         flags = _lib.ANNOTATE_SHARED | (0 if is_query else _lib.ANNOTATE_READ_IS_REF) | (_lib.ANNOTATE_MATCH_RESIDUES if residues else 0)
         return _annotate(self.ctx, rb, aln, flags, verbose)
+
+    def pileup(self, aln: AlignmentBatch, seq, counts=None, insertions: bool = False):
+        """zsw_pileup_batch over the alignments `aln` that one of this profile's alignment calls returned for `seq` (the same reads,
+        or the same SeqBatchSrc): the table over the profile's own sequence; results as `_ProfileBatchBase.pileup`."""
+        reads, is_query = self._reads_of(seq)
+        rb = _as_batch(reads, self.device)
+        self._prep()
+        flags = _lib.ANNOTATE_SHARED | (0 if is_query else _lib.ANNOTATE_READ_IS_REF)
+        return _pileup(self.ctx, rb, aln, flags, len(bytes(self.sequence)), counts, insertions)
 
     def to_sam_text(self, aln: AlignmentBatch, seq, qnames, quals=None, rname="ref", mapq: int = 255, strands=None, stats=None, omit_seq: bool = False,
                     device: bool = False):

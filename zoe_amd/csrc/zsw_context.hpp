@@ -116,6 +116,9 @@ struct zsw_context {
     zsw::DevBuf an_ws[16];
     // zsw_sam_batch (zsw_sam.hip): the staged arrays of a host call, RNAME, the line lengths / starts, the lines' shapes, the text
     zsw::DevBuf sam_ws[20];
+    // zsw_pileup_batch / zsw_consensus_from_counts (zsw_pileup.hip): the accumulators (16 bytes per site), the scan's scratch, the
+    // counter of malformed records, the staged arrays and tables of a host call
+    zsw::DevBuf pu_ws[16];
 };
 
 namespace zsw {
