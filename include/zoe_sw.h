@@ -632,7 +632,12 @@ typedef enum zsw_debug_flag {
     /* score: contiguous reads of one length of up to 160 bases are seeded by the one-pass kernel (seed_kernel<true, .>: every
      * thread sweeps its read byte by byte from LDS). By default the block converts its reads to packed rows once and every thread
      * sweeps words (zsw_score_seed.hip: seed_packed_kernel) */
-    ZSW_DEBUG_SEED_PLAIN_KERNEL = 524288
+    ZSW_DEBUG_SEED_PLAIN_KERNEL = 524288,
+    /* score: the diagonal first tier walks every wavefront's reads with the edge masks applied and the sixteenth diagonal computed.
+     * By default a wavefront of a one-length batch whose walks all stay inside the reference (zsw_seed_diag.hpp:
+     * diag_walk_is_interior) takes a copy of the column loop without the masks, and a wavefront whose lane partners all share
+     * their anchor skips the sixteenth diagonal's cell */
+    ZSW_DEBUG_SEED_DIAG_MASKED = 1048576
 } zsw_debug_flag;
 zsw_error zsw_debug_set(zsw_context* ctx, uint32_t flags);
 

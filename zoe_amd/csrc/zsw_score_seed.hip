@@ -447,6 +447,7 @@ hipError_t launch_score_seeded(const ScoreArgsV2& a2, int G, int C, uint32_t max
             b1.accepted = a2.out.narrow_only ? nullptr : accepted;
             b1.next_pair = queue1;
             b1.diag_lane_events = (ws.debug & ZSW_DEBUG_SEED_DIAG_LANE_EVENTS) != 0;
+            b1.diag_masked = (ws.debug & ZSW_DEBUG_SEED_DIAG_MASKED) != 0;
             note_launch(ws.launch_log, ZSW_LAUNCH_SEED_BAND, G, C, mode);
             // score only, as the first of two tiers: the band diagonal by diagonal (seed_diag_kernel) instead of 16-column strips
             const bool diagonal = mode == 0 && !a2.out.narrow_only && !(ws.debug & ZSW_DEBUG_SEED_STRIP_FIRST_TIER) && seed_diag_applicable(max_len, band_tabs->K);

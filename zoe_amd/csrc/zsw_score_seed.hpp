@@ -104,7 +104,8 @@ struct SeedBandArgs {
     uint32_t bail_below = 0;  // ... or with fewer items than this: a handful of reads costs the second tier one wavefront's whole walk (0.4 ms)
                               // and the full pass 30 ns each
     bool diag_lane_events = false;     // seed_diag_kernel: every lane derives its reads' k-mer patterns, in a batch of one length too (ZSW_DEBUG_SEED_DIAG_LANE_EVENTS)
-    int* dbg;                          // non-null (tests): 8 ints per read — the walk's own values (maximum, oa, ob) and its geometry
+    bool diag_masked = false;          // seed_diag_kernel: every wavefront takes the masked column loop with the sixteenth diagonal computed (ZSW_DEBUG_SEED_DIAG_MASKED)
+    int* dbg;                         // non-null (tests): 8 ints per read — the walk's own values (maximum, oa, ob) and its geometry
     uint32_t key_bias, fail_key;
     uint32_t* fail_list;
     uint32_t* fail_count;

@@ -63,4 +63,17 @@ ZSW_SEED_HD uint32_t seed_group_pick(const uint32_t* pat, int j0, uint32_t mask)
     return ((0u - (b & 1u)) & pat[0]) | ((0u - ((b >> 1) & 1u)) & pat[1]) | ((0u - ((b >> 2) & 1u)) & pat[2]);
 }
 
+// A walk whose band stays inside the reference: in every column c < lenmax of every group, the five edge words of the kernel's
+// group prologue (zsw_seed_diag_body.inc: above, topin, below, exits, yfok) have the column's bit set. Column c of the walk covers
+// the rows [dtmin - wu + c, dtmax + c + 1 + wd); with t0 = dtmin - wu + k0, t1 = dtmax + k0 + 1 + wd and c = k0 + u the words say
+//   above: t0 + u >= 1          topin: 0 <= t0 + u < R          below: t1 + u < R          exits: below, t1 + u >= 1          yfok: below, t1 + u >= 0
+// Each bound is tightest in the first or the last column, so the walk's two corners decide: the first row of column 0 has a row above
+// it inside the matrix (dtmin - wu >= 1: above; topin's lower bound with it), and the first row below the band in the last column is
+// a row of the reference (dtmax + lenmax + wd < R: below; topin's upper bound with it, as dtmin - wu <= dtmax + wd + 1). exits and
+// yfok add dtmax + wd >= 0, which the first condition implies for wu, wd >= 0; it is kept so that the predicate stands without
+// that premise. Model: tests/models/seed_diag_interior.cpp (every column's words as the body evaluates them).
+ZSW_SEED_HD bool diag_walk_is_interior(int dtmin, int dtmax, int wu, int wd, int lenmax, int R) {
+    return dtmin - wu >= 1 && dtmin - wu + lenmax - 1 < R && dtmax + lenmax + wd < R && dtmax + wd >= 0;
+}
+
 }  // namespace zsw

@@ -77,25 +77,48 @@
         up.ch = lo.ch = PKB2;
         up.fr = lo.fr = 0;
         uint32_t oa2 = 0, ob2 = 0, best = 0;
+        // One wave-uniform choice (UNI; ZSW_DEBUG_SEED_DIAG_MASKED switches it off), taken once per wavefront and walk: the INTERIOR copy
+        // of the column loop, if every active lane's pair is `narrow` and its walk stays inside the reference (diag_walk_is_interior:
+        // the edge words above, topin, below, exits and yfok are all-ones in every executed column). A one-length batch has realA
+        // all-ones in those columns too, so the six masks built from them (inj, join, ex, bel, nm through pair_mask, topin through
+        // lane_mask) are all-ones wherever they matter and the copy passes their operands unmasked. With every pair narrow, diagonal
+        // D - 1 counts for nothing in the whole wavefront: the copy does not compute its cell (H[D - 1] goes stale, nothing reads it;
+        // F[D - 1] = Fbelow as ever). Two cases differ from the masked loop, and neither reaches a result:
+        // (a) a lane without a partner (lenB == 0) has realB == 0, so the masked loop clears the high half of every masked operand.
+        //     Unmasked, that half walks the neutral codes of the missing read and holds values the masked loop would not.
+        //     band_finish never reads the high half of such a lane, and the low half cannot see it: the packed instructions keep the
+        //     halves apart, and in the plain 32-bit additions, subtractions and left shifts (up.ch += maxw2, h - gd2, ... - ge2,
+        //     pk_tag's v << 1) a carry, a borrow or a shifted bit travels from the low half to the high one only.
+        // (b) join is 0 in a read's last column: the first cell of that column joins nothing. What it would feed, up.fr / up.ch, is
+        //     read by the next column's v alone, and a one-length batch has no column behind lenmax - 1.
+        // tests/test_gpu_diag_interior.py compares both with the masked loop, record for record.
+        const bool interior = UNI && !a.diag_masked && __ballot(!(narrow && diag_walk_is_interior(dtmin, dtmax, wu, wd, lenmax, R))) == 0;
+        const auto walk = [&](auto interior_copy) __attribute__((always_inline)) {
+        constexpr bool INTERIOR = decltype(interior_copy)::value;
 #pragma unroll 1
         for (int k0 = 0; k0 < lenmax; k0 += D) {
-            uint32_t sel[D];
+            // the group's residue codes; a column's selectors are looked up one column ahead of their use (sixteen selectors held
+            // across the group would be twelve registers more than the two copies of the loop leave free)
+            uint32_t wa[D / 8], wb[D / 8];
 #pragma unroll
             for (int d = 0; d < D / 8; ++d) {
                 const uint32_t di = (uint32_t)(k0 / 8 + d);
-                const uint32_t wa = di < a.cs ? codeA[di] : 0xffffffffu;
-                const uint32_t wb = (validB && di < a.cs) ? codeB[di] : 0xffffffffu;
-#pragma unroll
-                for (int j = 0; j < 8; ++j)
-                    sel[8 * d + j] = (uint32_t)sel_lut[(wa >> (4 * j)) & 15u] | ((uint32_t)sel_lut[(wb >> (4 * j)) & 15u] << 16);
+                wa[d] = di < a.cs ? codeA[di] : 0xffffffffu;
+                wb[d] = (validB && di < a.cs) ? codeB[di] : 0xffffffffu;
             }
+            const auto sel_of = [&](int c) __attribute__((always_inline)) {
+                return (uint32_t)sel_lut[(wa[c / 8] >> (4 * (c % 8))) & 15u] | ((uint32_t)sel_lut[(wb[c / 8] >> (4 * (c % 8))) & 15u] << 16);
+            };
+            uint32_t sel_next = sel_of(0);
             // the group's columns as bit masks: the k-mer events of both programmes, and where the band's ends are cells of the matrix
-            uint32_t upS, upE, loS, loE, loI, freeb, anyup, anylo, inj, join, ex, bel, nm, topin;
+            uint32_t upS, upE, loS, loE, loI, freeb, anyup, anylo, inj = 0, join = 0, ex = 0, bel = 0, nm = 0, topin = 0;
+            uint32_t gany = 0xffffu;  // UNI: the columns in which a k-mer of the layout starts or ends, on scalar registers
             {
                 DiagGroupEvents ev;
                 if (UNI) {  // (a missing partner shares A's patterns: its masks are 0)
                     const SeedGroupPatterns g = seed_group_patterns(k0, D, um, uc0, ustride, a.sp.K, a.sp.spacer, umagic);
                     ev = diag_group_events(g, g, fa2, fb2);
+                    gany = g.start[0] | g.start[1] | g.start[2] | g.end[0] | g.end[1] | g.end[2];
                 } else {
                     const BandLayout yA = band_layout(st, false), yB = band_layout(st, true);
                     ev = diag_group_events(seed_group_patterns(k0, D, yA.m, yA.c0, yA.stride, a.sp.K, a.sp.spacer, yA.magic),
@@ -111,6 +134,7 @@
                 anyup |= anyup >> 16;
                 anylo = loS | loE;
                 anylo |= anylo >> 16;
+                if (!INTERIOR) {
                 // column c: first row base + c (a cell above it exists if that is > 0), first row below dtmax + c + 1 + wd
                 const int t0 = base + k0, t1 = dtmax + k0 + 1 + wd;
                 const uint32_t above = seed_bits_from(1 - t0), below = seed_bits_below(R - t1);
@@ -122,25 +146,36 @@
                 ex = pair_bits(realA & exits, realB & exits);
                 bel = pair_bits(realA & below, realB & below);
                 nm = pair_bits(realA & yfok, realB & yfok);
+                }
             }
             const uint32_t enter = (uint32_t)(base + k0 + D) * (uint32_t)sizeof(uint2);  // column k0's entering row, as a byte offset
 #pragma unroll
             for (int u = 0; u < D; ++u) {
                 if (k0 + u < lenmax) {  // (no break: a loop with two exits around a __ballot is not unrolled)
+                const uint32_t sel_u = sel_next;
+                if (u + 1 < D) sel_next = sel_of(u + 1);
                 Dc = pk_addu(Dc, ge2);
                 const uint32_t Dn = pk_addu(Dc, ge2);
                 // above the column: a(c); the band's first cell receives it from above (E: less gap_open)
                 up.ch += maxw2;
                 up.fr += maxw2;
-                if (__ballot((anyup >> u) & 1u) != 0) pk_events(&up, pair_mask(upS, u), pair_mask(upE, u), lam2);
-                const uint32_t v = pk_subu_sat(pk_maxu(up.ch, up.fr), PKB2) & pair_mask(inj, u);
+                // (UNI: no lane has an event in a column where the layout has none; the scalar test spares the vector one)
+                if ((!UNI || ((gany >> u) & 1u) != 0) && __ballot((anyup >> u) & 1u) != 0) pk_events(&up, pair_mask(upS, u), pair_mask(upE, u), lam2);
+                uint32_t v = pk_subu_sat(pk_maxu(up.ch, up.fr), PKB2);
+                if (!INTERIOR) v &= pair_mask(inj, u);
                 oa2 = pk_maxu(oa2, v);
-                uint32_t E = pk_addu(Dc, pk_tag<TAG>(pk_subu_sat(v, go2p) & lane_mask(topin, u)));
+                uint32_t vin = pk_subu_sat(v, go2p);
+                if (!INTERIOR) vin &= lane_mask(topin, u);
+                uint32_t E = pk_addu(Dc, pk_tag<TAG>(vin));
                 uint32_t rmax = 0x04000400u;
 #pragma unroll
                 for (int j = 0; j < D; ++j) {
+                    if (j == D - 1 && INTERIOR) {
+                        rmax = pk_maxu(rmax, H[j - 1]);
+                        break;
+                    }
                     const uint2 wr = w[(u + j) % D];
-                    const uint32_t hd = pk_addu(H[j], __builtin_amdgcn_perm(wr.y, wr.x, sel[u]));
+                    const uint32_t hd = pk_addu(H[j], __builtin_amdgcn_perm(wr.y, wr.x, sel_u));
                     const uint32_t Fin = j + 1 < D ? F[j + 1 < D ? j + 1 : j] : Fbelow;
                     const uint32_t h = pk_max3(hd, E, Fin);
                     H[j] = h;
@@ -154,7 +189,8 @@
                 best = pk_maxu(best, pk_subu(rmax, Dc));
                 // the first cell's value joins the paths above the band behind this column
                 {
-                    const uint32_t ux = pk_addu(pk_untag<TAG>(pk_subu(H[0], Dc)), PKB2) & pair_mask(join, u);
+                    uint32_t ux = pk_addu(pk_untag<TAG>(pk_subu(H[0], Dc)), PKB2);
+                    if (!INTERIOR) ux &= pair_mask(join, u);
                     const uint32_t fm = pair_mask(freeb, u);
                     up.fr = pk_maxu(up.fr, ux & fm);
                     up.ch = pk_maxu(up.ch, ux & ~fm);
@@ -162,19 +198,29 @@
                 // below the column: b(c), joined by the band's last cell
                 lo.ch += maxw2;
                 lo.fr += maxw2;
-                if (__ballot((anylo >> u) & 1u) != 0) pk_events(&lo, pair_mask(loS, u), pair_mask(loE, u), lam2);
-                const uint32_t he = pk_addu(pk_untag<TAG>(pk_subu(narrow ? H[D - 2] : H[D - 1], Dc)), PKB2) & pair_mask(ex, u);
+                if ((!UNI || ((gany >> u) & 1u) != 0) && __ballot((anylo >> u) & 1u) != 0) pk_events(&lo, pair_mask(loS, u), pair_mask(loE, u), lam2);
+                uint32_t he = pk_addu(pk_untag<TAG>(pk_subu((INTERIOR || narrow) ? H[D - 2] : H[D - 1], Dc)), PKB2);
+                if (!INTERIOR) he &= pair_mask(ex, u);
                 const uint32_t im = pair_mask(loI, u);
                 lo.fr = pk_maxu(lo.fr, he & im);
                 lo.ch = pk_maxu(lo.ch, he & ~im);
                 const uint32_t b2 = pk_subu_sat(pk_maxu(lo.ch, lo.fr), PKB2);
-                ob2 = pk_maxu(ob2, b2 & pair_mask(bel, u));
+                ob2 = pk_maxu(ob2, INTERIOR ? b2 : b2 & pair_mask(bel, u));
                 // the next column's last cell: F entering from the left (the bound may have stood lambda - maxw higher just before a
                 // k-mer's last column; a horizontal run opens with gap_open)
-                Fbelow = pk_addu(Dn, pk_tag<TAG>(pk_subu_sat(pk_addu(b2, lamx), go2p) & pair_mask(nm, u)));
-                if (narrow) F[D - 1] = Fbelow;
+                uint32_t yf = pk_subu_sat(pk_addu(b2, lamx), go2p);
+                if (!INTERIOR) yf &= pair_mask(nm, u);
+                Fbelow = pk_addu(Dn, pk_tag<TAG>(yf));
+                if (INTERIOR || narrow) F[D - 1] = Fbelow;
                 }
             }
+        }
+        };  // walk
+        if constexpr (UNI) {
+            if (interior) walk(std::true_type{});
+            else walk(std::false_type{});
+        } else {
+            walk(std::false_type{});
         }
         band_finish<0, MINS>(a, P, best, oa2, ob2, dtmin, dtmax, lenmax | (wu << 8) | (wd << 20), 1, infoA, infoB, BandEnds{}, &n_accepted, &n_below);
         }  // fetched == 2
