@@ -142,6 +142,42 @@ pub struct ZswSamFields {
 /// flag of `zsw_sam_batch`: SEQ `*` on every line
 pub const ZSW_SAM_OMIT_SEQ: i32 = 1;
 
+/// flags of `zsw_fastq_parse_batch`: the buffer ends the file; names end in front of the first space or tab
+pub const ZSW_FASTQ_FINAL: i32 = 1;
+pub const ZSW_FASTQ_NAME_TO_BLANK: i32 = 2;
+/// the first failing check of a record (`report[ZSW_FASTQ_INFO_ERROR]`), in the order of `FastQReader`
+pub const ZSW_FASTQ_MISSING_AT: u64 = 1;
+pub const ZSW_FASTQ_MISSING_HEADER: u64 = 2;
+pub const ZSW_FASTQ_INVALID_UTF8: u64 = 3;
+pub const ZSW_FASTQ_MISSING_SEQUENCE: u64 = 4;
+pub const ZSW_FASTQ_MISSING_PLUS: u64 = 5;
+pub const ZSW_FASTQ_MISSING_QUALITY: u64 = 6;
+pub const ZSW_FASTQ_LENGTH_MISMATCH: u64 = 7;
+pub const ZSW_FASTQ_INVALID_QUALITY: u64 = 8;
+/// the words of the report
+pub const ZSW_FASTQ_INFO_RECORDS: usize = 0;
+pub const ZSW_FASTQ_INFO_BASES: usize = 1;
+pub const ZSW_FASTQ_INFO_NAME_BYTES: usize = 2;
+pub const ZSW_FASTQ_INFO_CONSUMED: usize = 3;
+pub const ZSW_FASTQ_INFO_ERROR: usize = 4;
+pub const ZSW_FASTQ_INFO_ERROR_RECORD: usize = 5;
+pub const ZSW_FASTQ_INFO_ERROR_OFFSET: usize = 6;
+pub const ZSW_FASTQ_INFO_MIN_LEN: usize = 7;
+pub const ZSW_FASTQ_INFO_MAX_LEN: usize = 8;
+pub const ZSW_FASTQ_INFO_WORDS: usize = 9;
+
+/// What `fastq_parse_batch` returns: record i has the bases `bases[offsets[i]..offsets[i + 1]]`, the qualities at the same place
+/// in `quals`, and the name `names[name_offsets[i]..name_offsets[i + 1]]`.
+#[derive(Clone, Debug, Default)]
+pub struct FastqBatch {
+    pub bases:        Vec<u8>,
+    pub quals:        Vec<u8>,
+    pub offsets:      Vec<u64>,
+    pub names:        Vec<u8>,
+    pub name_offsets: Vec<u64>,
+    pub report:       [u64; ZSW_FASTQ_INFO_WORDS],
+}
+
 pub const ZSW_OK: i32 = 0;
 pub const ZSW_MEM_HOST: i32 = 0;
 pub const ZSW_ENCODING_BYTES: i32 = 0;
@@ -238,6 +274,7 @@ unsafe extern "C" {
     fn zsw_pileup_batch(ctx: *mut ZswContext, reads: *const ZswBatch, flags: i32, aln: *const ZswAlignment, status: *const u8, inc: *const u32, op: *const u8, n_ciglets: u64, counts: *mut c_void, ins: *mut c_void, out_n_bad: *mut u64, stream: *mut c_void) -> i32;
     fn zsw_consensus_from_counts(ctx: *mut ZswContext, counts: *const c_void, len: u64, mem: i32, flags: i32, fallback: *const u8, out_seq: *mut u8, stream: *mut c_void) -> i32;
     fn zsw_sam_batch(ctx: *mut ZswContext, reads: *const ZswBatch, fields: *const c_void, flags: i32, aln: *const ZswAlignment, status: *const u8, inc: *const u32, op: *const u8, n_ciglets: u64, out_text: *mut u8, text_cap: u64, out_n_bytes: *mut u64, out_line_offsets: *mut u64, out_n_bad: *mut u64, stream: *mut c_void) -> i32;
+    fn zsw_fastq_parse_batch(ctx: *mut ZswContext, text: *const u8, n_bytes: u64, mem: i32, flags: i32, out_bases: *mut u8, out_quals: *mut u8, base_cap: u64, out_offsets: *mut u64, out_qnames: *mut u8, name_cap: u64, out_qname_offsets: *mut u64, record_cap: u64, out_info: *mut u64, stream: *mut c_void) -> i32;
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -967,6 +1004,37 @@ impl GpuContext {
             self.check(code, 0, 0)?;
         }
         Ok((text, n_bad))
+    }
+
+    /// `zsw_fastq_parse_batch` over FASTQ bytes in host memory: the records `FastQReader` yields in front of its first error, as
+    /// names, bases and qualities back to back with their offsets, and the report (`ZSW_FASTQ_INFO_*`). `last`: the buffer ends the
+    /// file (`ZSW_FASTQ_FINAL`); otherwise parse on from `report[ZSW_FASTQ_INFO_CONSUMED]` with the next chunk appended.
+    /// `name_to_blank`: names end in front of the first space or tab. The capacities are the bounds that always suffice.
+    pub fn fastq_parse_batch(&self, text: &[u8], last: bool, name_to_blank: bool) -> Result<FastqBatch, GpuError> {
+        let n = text.len() as u64;
+        let flags = if last { ZSW_FASTQ_FINAL } else { 0 } | if name_to_blank { ZSW_FASTQ_NAME_TO_BLANK } else { 0 };
+        let (base_cap, name_cap, record_cap) = (n / 2, n, n / 8 + 1);
+        let mut out = FastqBatch {
+            bases: vec![0u8; base_cap as usize],
+            quals: vec![0u8; base_cap as usize],
+            offsets: vec![0u64; record_cap as usize + 1],
+            names: vec![0u8; name_cap as usize],
+            name_offsets: vec![0u64; record_cap as usize + 1],
+            report: [0u64; ZSW_FASTQ_INFO_WORDS],
+        };
+        // SAFETY: every array holds the capacity it is declared with; the report holds ZSW_FASTQ_INFO_WORDS entries
+        let code = unsafe {
+            zsw_fastq_parse_batch(self.raw, text.as_ptr(), n, ZSW_MEM_HOST, flags, out.bases.as_mut_ptr(), out.quals.as_mut_ptr(), base_cap, out.offsets.as_mut_ptr(),
+                                  out.names.as_mut_ptr(), name_cap, out.name_offsets.as_mut_ptr(), record_cap, out.report.as_mut_ptr(), ptr::null_mut())
+        };
+        self.check(code, 0, 0)?;
+        let records = out.report[ZSW_FASTQ_INFO_RECORDS] as usize;
+        out.bases.truncate(out.report[ZSW_FASTQ_INFO_BASES] as usize);
+        out.quals.truncate(out.report[ZSW_FASTQ_INFO_BASES] as usize);
+        out.names.truncate(out.report[ZSW_FASTQ_INFO_NAME_BYTES] as usize);
+        out.offsets.truncate(records + 1);
+        out.name_offsets.truncate(records + 1);
+        Ok(out)
     }
 
     /// Per read: `profiles.sw_align_from_i{from_width}_3pass(seq)` of the read or of its reverse complement, whichever scores

@@ -5,7 +5,7 @@
 //
 //   g++ -O2 -std=c++17 -Iinclude examples/zsw_driver.cpp -o examples/zsw_driver -Lzoe_amd -lzoe_sw_hip -Wl,-rpath,$PWD/zoe_amd
 //   ./examples/zsw_driver reference.txt reads.fastq [--score-only | --3pass | --both-strands] [--min-score T] [--nm] [--verbose-cigar] [--device-sam]
-//                         [--consensus FILE]
+//                         [--consensus FILE] [--device-fastq]
 // --both-strands: every read is aligned on whichever strand scores higher (sw_align_strands_from_i8_3pass); a read answered by
 // its reverse complement gets flag 16, SEQ reverse complemented and QUAL reversed, and POS / CIGAR are those of that sequence.
 // --min-score T (with --3pass or --score-only, the calls ZSW_OPTION_MIN_SCORE covers): a read that scores less than T is written as
@@ -18,12 +18,16 @@
 // --consensus FILE: beside the SAM output, the plurality consensus of the run as a one-record FASTA: the alignments piled up over the
 // reference on the GPU (zsw_pileup_batch; under --both-strands from the reads as aligned), per position the most frequent of A C G T N
 // (zsw_consensus_from_counts), and the reference's own base where no read covers it.
+// --device-fastq: the FASTQ file is read with one fread and parsed on the GPU (zsw_fastq_parse_batch with ZSW_FASTQ_FINAL |
+// ZSW_FASTQ_NAME_TO_BLANK) instead of line by line on the host; a malformed record ends the driver with exit status 1 and a message
+// naming the code and the record. Everything downstream, and the output, is the same.
 #include <algorithm>
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
 #include <fstream>
 #include <iostream>
+#include <memory>
 #include <sstream>
 
 #include "zoe_sw.hpp"
@@ -47,10 +51,10 @@ static std::string read_reference(const std::string& path, std::string* name) {
 
 int main(int argc, char** argv) {
     if (argc < 3) {
-        std::cerr << "usage: zsw_driver reference.(fa|txt) reads.fastq [--score-only | --3pass | --both-strands] [--min-score T] [--nm] [--verbose-cigar] [--device-sam] [--consensus FILE]\n";
+        std::cerr << "usage: zsw_driver reference.(fa|txt) reads.fastq [--score-only | --3pass | --both-strands] [--min-score T] [--nm] [--verbose-cigar] [--device-sam] [--consensus FILE] [--device-fastq]\n";
         return 2;
     }
-    bool score_only = false, three_pass = false, both_strands = false, nm = false, verbose_cigar = false, device_sam = false;
+    bool score_only = false, three_pass = false, both_strands = false, nm = false, verbose_cigar = false, device_sam = false, device_fastq = false;
     long long min_score = 0;
     std::string consensus_path;
     for (int k = 3; k < argc; ++k) {
@@ -61,6 +65,7 @@ int main(int argc, char** argv) {
         else if (!std::strcmp(argv[k], "--nm")) nm = true;
         else if (!std::strcmp(argv[k], "--verbose-cigar")) verbose_cigar = true;
         else if (!std::strcmp(argv[k], "--device-sam")) device_sam = true;
+        else if (!std::strcmp(argv[k], "--device-fastq")) device_fastq = true;
         else if (!std::strcmp(argv[k], "--consensus") && k + 1 < argc) consensus_path = argv[++k];
         else {
             std::cerr << "zsw_driver: unknown argument " << argv[k] << '\n';
@@ -78,17 +83,39 @@ int main(int argc, char** argv) {
     try {
         std::string ref_name;
         const std::string reference = read_reference(argv[1], &ref_name);
-        std::ifstream fq(argv[2]);
-        if (!fq) throw std::runtime_error(std::string("cannot open ") + argv[2]);
         std::vector<std::string> names, reads, quals;
-        std::string h, s, p, q;
-        while (std::getline(fq, h) && std::getline(fq, s) && std::getline(fq, p) && std::getline(fq, q)) {
-            if (h.empty() || h[0] != '@') throw std::runtime_error("malformed FASTQ header: " + h);
-            names.push_back(h.substr(1, h.find_first_of(" \t") == std::string::npos ? std::string::npos : h.find_first_of(" \t") - 1));
-            reads.push_back(s);
-            quals.push_back(q);
+        std::unique_ptr<zoe::GpuContext> ctx_holder;
+        if (device_fastq) {  // the whole file with one fread, the records from zsw_fastq_parse_batch
+            std::FILE* f = std::fopen(argv[2], "rb");
+            if (!f) throw std::runtime_error(std::string("cannot open ") + argv[2]);
+            std::fseek(f, 0, SEEK_END);
+            const long size = std::ftell(f);
+            std::fseek(f, 0, SEEK_SET);
+            std::string text(size > 0 ? (size_t)size : 0, '\0');
+            const size_t got = text.empty() ? 0 : std::fread(&text[0], 1, text.size(), f);
+            std::fclose(f);
+            if (got != text.size()) throw std::runtime_error(std::string("cannot read ") + argv[2]);
+            ctx_holder.reset(new zoe::GpuContext(0));
+            zoe::FastqRecords fastq = ctx_holder->parse_fastq(text, true, true);
+            if (fastq.error())
+                throw std::runtime_error("malformed FASTQ: code " + std::to_string(fastq.error()) + " at record " + std::to_string(fastq.report[ZSW_FASTQ_INFO_ERROR_RECORD]) +
+                                         " (byte " + std::to_string(fastq.report[ZSW_FASTQ_INFO_ERROR_OFFSET]) + ")");
+            names = std::move(fastq.names);
+            reads = std::move(fastq.reads);
+            quals = std::move(fastq.quals);
+        } else {
+            std::ifstream fq(argv[2]);
+            if (!fq) throw std::runtime_error(std::string("cannot open ") + argv[2]);
+            std::string h, s, p, q;
+            while (std::getline(fq, h) && std::getline(fq, s) && std::getline(fq, p) && std::getline(fq, q)) {
+                if (h.empty() || h[0] != '@') throw std::runtime_error("malformed FASTQ header: " + h);
+                names.push_back(h.substr(1, h.find_first_of(" \t") == std::string::npos ? std::string::npos : h.find_first_of(" \t") - 1));
+                reads.push_back(s);
+                quals.push_back(q);
+            }
         }
-        zoe::GpuContext ctx(0);
+        if (!ctx_holder) ctx_holder.reset(new zoe::GpuContext(0));
+        zoe::GpuContext& ctx = *ctx_holder;
         if (min_score > 0) ctx.set_min_score((uint32_t)min_score);
         const zoe::WeightMatrix weights = zoe::WeightMatrix::new_dna_matrix(2, -5, 'N');
         zoe::LocalProfilesBatch profiles(ctx, reads, weights, -10, -1);

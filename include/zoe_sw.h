@@ -447,6 +447,62 @@ zsw_error zsw_consensus_from_counts(zsw_context* ctx, const void* counts, uint64
                                     const uint8_t* fallback /* len bytes, with KEEP_UNCOVERED */, uint8_t* out_seq /* len */,
                                     void* stream);
 
+/* ---- FASTQ parsed on the device --------------------------------------------------------------------- */
+/* zsw_fastq_parse_batch turns a buffer of single-line FASTQ into the arrays zsw_batch and zsw_sam_fields take: the bases of all
+ * records back to back with out_offsets, the qualities laid out the same way, the names back to back with out_qname_offsets. The
+ * semantics are FastQReader's (src/data/records/fastq/reader.rs:87-187). A line ends at '\n'; only the last line of the buffer can be
+ * unterminated; record r is lines 4 r .. 4 r + 3. With ZSW_FASTQ_FINAL the buffer ends the file: a non-empty unterminated tail is a
+ * line, the records are ceil(lines / 4), and a line the file does not have reads as empty. Without it only the records whose four
+ * lines are all terminated are parsed; the tail is neither parsed nor an error (the caller prepends it to the next chunk).
+ * chop_line_break removes one trailing '\n' and then one trailing '\r'; a '\r' without a '\n' behind it stays. Per record, the first
+ * failing check, in the reader's order, is its code:
+ *   1 ZSW_FASTQ_MISSING_AT        the header line does not start with '@' (a blank line where a header belongs, too)
+ *   2 ZSW_FASTQ_MISSING_HEADER    nothing behind '@' after the chop
+ *   3 ZSW_FASTQ_INVALID_UTF8      the header is not UTF-8 by String::from_utf8: overlong forms, surrogates, values above U+10FFFF
+ *                                 and truncated sequences are invalid
+ *   4 ZSW_FASTQ_MISSING_SEQUENCE  the sequence line is empty after the chop
+ *   5 ZSW_FASTQ_MISSING_PLUS      the third line does not start with '+' (the rest of that line is ignored)
+ *   6 ZSW_FASTQ_MISSING_QUALITY   the quality line is empty after the chop
+ *   7 ZSW_FASTQ_LENGTH_MISMATCH   sequence and quality differ in length
+ *   8 ZSW_FASTQ_INVALID_QUALITY   a quality byte outside '!' ..= '~'
+ * Trailing blank lines are not skipped. The records in front of the failing record with the lowest index are delivered — what a
+ * consumer of the iterator that stops at the first Err has seen; that index is a minimum over the records, not an order of arrival,
+ * and outputs and report are the same on every run. The name is the whole header behind '@', chopped; with ZSW_FASTQ_NAME_TO_BLANK
+ * it ends in front of the first space or tab (what zsw_driver writes as QNAME). The UTF-8 check always covers the whole header.
+ * Positions and lengths are 64-bit throughout.
+ * text and every output array live where `mem` says; out_info is host memory, ZSW_FASTQ_INFO_WORDS entries, always filled by a call
+ * that gets past its argument checks: RECORDS delivered, their BASES and NAME_BYTES, CONSUMED = the offset one past the last delivered
+ * record (a caller that reads a file in chunks restarts there), ERROR = 0 or a code of the table with ERROR_RECORD the failing
+ * record's index and ERROR_OFFSET the start of its header line (both 0 without an error), MIN_LEN / MAX_LEN over the delivered
+ * sequences (0 for none; where they are equal the bases are a fixed-length batch as well). A malformed file is ZSW_OK and a report,
+ * never a fault: every position derived from the text is checked in 64-bit arithmetic before the load that uses it. n_bytes == 0 is
+ * ZSW_OK with zero records. out_offsets and out_qname_offsets hold record_cap + 1 entries. out_quals, or out_qnames together with
+ * out_qname_offsets, may be NULL: that part is not written (and name_cap is ignored, NAME_BYTES still reported).
+ * Capacity protocol, as for zsw_sam_batch: RECORDS > record_cap, BASES > base_cap or NAME_BYTES > name_cap is
+ * ZSW_ERR_INVALID_ARGUMENT with the needed sizes in out_info and no byte of any output array written; every output NULL with every
+ * capacity 0 is the sizing call (ZSW_OK). Bounds that always suffice, so that a caller can do without the sizing call:
+ *   base_cap = n_bytes / 2,  name_cap = n_bytes,  record_cap = n_bytes / 8 + 1  (the shortest record is "@x\nA\n+\nA" at the file's end)
+ * No byte at or beyond out_bases[BASES], out_quals[BASES], out_qnames[NAME_BYTES] or entry RECORDS + 1 of the offsets is written.
+ * Unknown flag bits, a null required pointer (ctx, out_info; text with n_bytes > 0; out_bases and out_offsets outside the sizing
+ * call; one of out_qnames / out_qname_offsets without the other), an unknown mem, or an output that overlaps the text or another
+ * output: ZSW_ERR_INVALID_ARGUMENT, nothing written, out_info included. More than 2^36 bytes, or about 2^33 newlines, per call: ZSW_ERR_UNSUPPORTED.
+ * The launches: newlines counted per tile, an exclusive sum, the position of every newline at its rank, a record pass (one wavefront
+ * per record), two exclusive sums for the offsets, a gather; a minimum and a maximum are the only atomics. Device calls synchronise the
+ * stream once, for the report; one case aside: the workspace for the newline positions is sized for a newline per 16 bytes before the
+ * count is known, and a denser text makes the call repeat its later launches once with the exact size. Host calls are staged and
+ * synchronous. The call needs neither scoring nor a reference, ZSW_OPTION_* do not matter, and zsw_group_* does not cover it.
+ * Workspace, kept by the context until zsw_destroy: 8 bytes per newline (n_bytes / 2 at least), 33 bytes per four newlines, 16 bytes
+ * per tile, the scans' scratch, and the staged text and outputs of a host call. Tile and block constants: zoe_amd/csrc/zsw_fastq.hpp. */
+enum { ZSW_FASTQ_FINAL = 1, ZSW_FASTQ_NAME_TO_BLANK = 2 };
+enum { ZSW_FASTQ_MISSING_AT = 1, ZSW_FASTQ_MISSING_HEADER = 2, ZSW_FASTQ_INVALID_UTF8 = 3, ZSW_FASTQ_MISSING_SEQUENCE = 4,
+       ZSW_FASTQ_MISSING_PLUS = 5, ZSW_FASTQ_MISSING_QUALITY = 6, ZSW_FASTQ_LENGTH_MISMATCH = 7, ZSW_FASTQ_INVALID_QUALITY = 8 };
+enum { ZSW_FASTQ_INFO_RECORDS = 0, ZSW_FASTQ_INFO_BASES = 1, ZSW_FASTQ_INFO_NAME_BYTES = 2, ZSW_FASTQ_INFO_CONSUMED = 3,
+       ZSW_FASTQ_INFO_ERROR = 4, ZSW_FASTQ_INFO_ERROR_RECORD = 5, ZSW_FASTQ_INFO_ERROR_OFFSET = 6,
+       ZSW_FASTQ_INFO_MIN_LEN = 7, ZSW_FASTQ_INFO_MAX_LEN = 8, ZSW_FASTQ_INFO_WORDS = 9 };
+zsw_error zsw_fastq_parse_batch(zsw_context* ctx, const uint8_t* text, uint64_t n_bytes, zsw_mem mem, int flags, uint8_t* out_bases,
+                                uint8_t* out_quals, uint64_t base_cap, uint64_t* out_offsets, uint8_t* out_qnames, uint64_t name_cap,
+                                uint64_t* out_qname_offsets, uint64_t record_cap, uint64_t* out_info, void* stream);
+
 /* ---- pre-alignment filter ------------------------------------------------------------------ */
 /* out_pass[i] = sneaky_snake(&reference[ref_start[i] .. ref_start[i]+ref_len[i]], read_i, threshold)
  * (src/alignment/sneaky_snake.rs:78-131): the SneakySnake edit-distance filter between a read and a candidate window of the

@@ -165,6 +165,14 @@ struct Pileup {
     uint64_t n_bad = 0;                           // records that are no alignments of their reads to the sequence: they count nothing
 };
 
+// What GpuContext::parse_fastq returns (zsw_fastq_parse_batch): the records in front of the first malformed one, and the report
+// (ZSW_FASTQ_INFO_*: records, bases, name bytes, consumed, error, its record and offset, min / max length)
+struct FastqRecords {
+    std::vector<std::string> names, reads, quals;
+    uint64_t report[ZSW_FASTQ_INFO_WORDS] = {};
+    uint64_t error() const { return report[ZSW_FASTQ_INFO_ERROR]; }
+};
+
 class GpuContext {
   public:
     explicit GpuContext(int device = 0) {
@@ -275,6 +283,28 @@ class GpuContext {
             check(zsw_sam_batch(ctx_, &reads, &fields, flags, rec.data(), status.data(), inc.data(), op.data(), inc.size(), (uint8_t*)&text[0], total, &total, nullptr,
                                 &n_bad, nullptr));
         return text;
+    }
+    // zsw_fastq_parse_batch over the bytes of a FASTQ buffer (host memory): the records FastQReader yields in front of its first
+    // error, as names, reads and qualities, and the report. last: the buffer ends the file (ZSW_FASTQ_FINAL); without it only the
+    // records whose four lines are all terminated are parsed and report[ZSW_FASTQ_INFO_CONSUMED] says where the rest begins.
+    // name_to_blank: names end in front of the first space or tab. A malformed record does not throw: report[ZSW_FASTQ_INFO_ERROR].
+    FastqRecords parse_fastq(const std::string& text, bool last = true, bool name_to_blank = false) const {
+        const uint64_t n = text.size(), base_cap = n / 2, name_cap = n, record_cap = n / 8 + 1;  // the bounds that always suffice
+        std::vector<uint8_t> bases(base_cap + 1), quals(base_cap + 1), qnames(name_cap + 1);
+        std::vector<uint64_t> off(record_cap + 1), noff(record_cap + 1);
+        FastqRecords out;
+        check(zsw_fastq_parse_batch(ctx_, reinterpret_cast<const uint8_t*>(text.data()), n, ZSW_MEM_HOST, (last ? ZSW_FASTQ_FINAL : 0) | (name_to_blank ? ZSW_FASTQ_NAME_TO_BLANK : 0),
+                                    bases.data(), quals.data(), base_cap, off.data(), qnames.data(), name_cap, noff.data(), record_cap, out.report, nullptr));
+        const size_t records = (size_t)out.report[ZSW_FASTQ_INFO_RECORDS];
+        out.names.reserve(records);
+        out.reads.reserve(records);
+        out.quals.reserve(records);
+        for (size_t i = 0; i < records; ++i) {
+            out.names.emplace_back(qnames.begin() + noff[i], qnames.begin() + noff[i + 1]);
+            out.reads.emplace_back(bases.begin() + off[i], bases.begin() + off[i + 1]);
+            out.quals.emplace_back(quals.begin() + off[i], quals.begin() + off[i + 1]);
+        }
+        return out;
     }
 
   private:

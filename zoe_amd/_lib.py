@@ -54,7 +54,7 @@ SYMBOLS = [
     "zsw_group_set_reference", "zsw_group_score_batch_from", "zsw_group_score_batch_from_device", "zsw_group_align_batch_from",
     "zsw_group_align_3pass_batch_from",
     "zsw_set_complement", "zsw_score_strands_batch_from", "zsw_orient_batch", "zsw_align_3pass_strands_batch_from", "zsw_strand_counts", "zsw_debug_strand_records", "zsw_debug_score_launches",
-    "zsw_min_score_counts", "zsw_annotate_batch", "zsw_sam_batch", "zsw_pileup_batch", "zsw_consensus_from_counts",
+    "zsw_min_score_counts", "zsw_annotate_batch", "zsw_sam_batch", "zsw_pileup_batch", "zsw_consensus_from_counts", "zsw_fastq_parse_batch",
 ]
 
 
@@ -122,6 +122,13 @@ SAM_OMIT_SEQ = 1
 PILEUP_CLEAR = 8
 CONSENSUS_KEEP_UNCOVERED = 1
 PILEUP_BINS = ("A", "C", "G", "T", "N", "-", "other", "invalid")
+
+# zsw_fastq_parse_batch: flags, the codes of a record's first failing check, the words of the report
+FASTQ_FINAL, FASTQ_NAME_TO_BLANK = 1, 2
+(FASTQ_MISSING_AT, FASTQ_MISSING_HEADER, FASTQ_INVALID_UTF8, FASTQ_MISSING_SEQUENCE, FASTQ_MISSING_PLUS, FASTQ_MISSING_QUALITY, FASTQ_LENGTH_MISMATCH,
+ FASTQ_INVALID_QUALITY) = range(1, 9)
+(FASTQ_INFO_RECORDS, FASTQ_INFO_BASES, FASTQ_INFO_NAME_BYTES, FASTQ_INFO_CONSUMED, FASTQ_INFO_ERROR, FASTQ_INFO_ERROR_RECORD, FASTQ_INFO_ERROR_OFFSET,
+ FASTQ_INFO_MIN_LEN, FASTQ_INFO_MAX_LEN, FASTQ_INFO_WORDS) = range(10)
 
 
 class ZswError(RuntimeError):
@@ -223,5 +230,6 @@ def load() -> C.CDLL:
                                   u64p, C.POINTER(C.c_uint64), vp]
     lib.zsw_pileup_batch.argtypes = [vp, C.POINTER(ZswBatch), C.c_int, vp, u8p, u32p, u8p, C.c_uint64, vp, vp, C.POINTER(C.c_uint64), vp]
     lib.zsw_consensus_from_counts.argtypes = [vp, vp, C.c_uint64, C.c_int, C.c_int, u8p, u8p, vp]
+    lib.zsw_fastq_parse_batch.argtypes = [vp, u8p, C.c_uint64, C.c_int, C.c_int, u8p, u8p, C.c_uint64, u64p, u8p, C.c_uint64, u64p, C.c_uint64, C.POINTER(C.c_uint64), vp]
     _lib = lib
     return lib

@@ -703,7 +703,13 @@ def _sam_text(ctx: "SwContext", rb: "ReadBatch", aln: AlignmentBatch, qnames, qu
     d_inc, d_op = up(aln.inc, np.int32), up(aln.op, np.uint8)
     keep = [d_aln, d_status, d_inc, d_op]
     f = _lib.ZswSamFields()
-    if qnames is not None:
+    if isinstance(qnames, tuple) and len(qnames) == 2 and isinstance(qnames[0], torch.Tensor):  # (names back to back, n + 1 offsets) on the device
+        d_names, d_noff = qnames[0].contiguous(), qnames[1].contiguous()
+        if not (d_names.is_cuda and d_noff.is_cuda) or d_names.dtype != torch.uint8 or d_noff.dtype != torch.int64 or d_noff.numel() < n + 1:
+            raise ValueError("qnames: a CUDA uint8 tensor of the names and a CUDA int64 tensor of n + 1 offsets")
+        keep += [d_names, d_noff]
+        f.qnames, f.qname_offsets = d_names.data_ptr(), d_noff.data_ptr()
+    elif qnames is not None:
         names = [q.encode() if isinstance(q, str) else bytes(q) for q in qnames]
         if len(names) != n:
             raise ValueError("one QNAME per read")
@@ -865,7 +871,8 @@ class _ProfileBatchBase:
                     device: bool = False):
         """zsw_sam_batch: the SAM body for the alignments `aln` of this batch (those of an alignment call, or the verbose ones of
         `annotate`), one line per read — what `str(SamData.from_alignment(..))` / `str(SamData.unmapped(..))` of zoe_amd/records.py give,
-        each closed by a newline — formatted on the GPU. qnames: one name per read, or None ("*"); quals: the qualities as read, one
+        each closed by a newline — formatted on the GPU. qnames: one name per read, a pair of CUDA tensors (the names back to back, uint8; n + 1
+        offsets, int64) as `records.fastq_batch_from_text` leaves them, or None ("*"); quals: the qualities as read, one
         byte string per read or a CUDA uint8 tensor laid out as the reads, or None ("*"); strands: default `aln.strand` — strand 1:
         FLAG 16, SEQ the reverse complement (the reads are oriented as for `annotate`), QUAL reversed; stats: the stats array of
         `annotate`, for NM:i:; omit_seq: SEQ "*". -> bytes, or with `device` (a CUDA uint8 tensor, a CUDA int64 tensor of n + 1 line

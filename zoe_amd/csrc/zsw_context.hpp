@@ -119,6 +119,9 @@ struct zsw_context {
     // zsw_pileup_batch / zsw_consensus_from_counts (zsw_pileup.hip): the accumulators (16 bytes per site), the scan's scratch, the
     // counter of malformed records, the staged arrays and tables of a host call
     zsw::DevBuf pu_ws[16];
+    // zsw_fastq_parse_batch (zsw_fastq.hip): the tile counts and their sum, 8 bytes per newline, the per-record arrays and their
+    // sums, the scans' scratch, the state block with the report, the staged text and outputs of a host call
+    zsw::DevBuf fq_ws[16];
 };
 
 namespace zsw {
