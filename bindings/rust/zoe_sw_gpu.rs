@@ -178,6 +178,99 @@ pub struct FastqBatch {
     pub report:       [u64; ZSW_FASTQ_INFO_WORDS],
 }
 
+/// flags of `zsw_sam_parse_batch`: the buffer ends the file; the QUAL of a record with FLAG & 16 is stored back to front
+pub const ZSW_SAMTEXT_FINAL: i32 = 1;
+pub const ZSW_SAMTEXT_QUAL_FORWARD: i32 = 2;
+/// the first failing check of a line (`report[ZSW_SAMTEXT_INFO_ERROR]`), in the order of `SAMReader`
+pub const ZSW_SAMTEXT_INVALID_UTF8: u64 = 1;
+pub const ZSW_SAMTEXT_TOO_FEW_FIELDS: u64 = 2;
+pub const ZSW_SAMTEXT_INVALID_FLAG: u64 = 3;
+pub const ZSW_SAMTEXT_INVALID_POS: u64 = 4;
+pub const ZSW_SAMTEXT_INVALID_MAPQ: u64 = 5;
+pub const ZSW_SAMTEXT_INVALID_QUALITY: u64 = 6;
+/// why a data line that is not unmapped could not become an alignment (`ZswSamParsed::code`)
+pub const ZSW_SAMREC_SEQ_MISSING: u8 = 1;
+pub const ZSW_SAMREC_CIGAR_INVALID_OP: u8 = 2;
+pub const ZSW_SAMREC_CIGAR_MISSING_INC: u8 = 3;
+pub const ZSW_SAMREC_CIGAR_INC_ZERO: u8 = 4;
+pub const ZSW_SAMREC_CIGAR_INC_OVERFLOW: u8 = 5;
+pub const ZSW_SAMREC_CIGAR_MISSING_OP: u8 = 6;
+pub const ZSW_SAMREC_CIGAR_MERGE_OVERFLOW: u8 = 7;
+pub const ZSW_SAMREC_POS_ZERO: u8 = 8;
+pub const ZSW_SAMREC_CLIPS_EXCEED_SEQ: u8 = 9;
+pub const ZSW_SAMREC_TOO_LARGE: u8 = 10;
+/// `ZswSamParsed::bits`
+pub const ZSW_SAMREC_BIT_NO_SCORE: u32 = 1;
+pub const ZSW_SAMREC_BIT_OTHER_RNAME: u32 = 2;
+pub const ZSW_SAMREC_BIT_SEQ_MISSING: u32 = 4;
+pub const ZSW_SAMREC_BIT_QUAL_MISSING: u32 = 8;
+pub const ZSW_SAMREC_BIT_QUAL_LENGTH: u32 = 16;
+/// the words of the report
+pub const ZSW_SAMTEXT_INFO_RECORDS: usize = 0;
+pub const ZSW_SAMTEXT_INFO_HEADERS: usize = 1;
+pub const ZSW_SAMTEXT_INFO_BASES: usize = 2;
+pub const ZSW_SAMTEXT_INFO_NAME_BYTES: usize = 3;
+pub const ZSW_SAMTEXT_INFO_CIGLETS: usize = 4;
+pub const ZSW_SAMTEXT_INFO_CONSUMED: usize = 5;
+pub const ZSW_SAMTEXT_INFO_ERROR: usize = 6;
+pub const ZSW_SAMTEXT_INFO_ERROR_LINE: usize = 7;
+pub const ZSW_SAMTEXT_INFO_ERROR_OFFSET: usize = 8;
+pub const ZSW_SAMTEXT_INFO_MAPPED: usize = 9;
+pub const ZSW_SAMTEXT_INFO_CODED: usize = 10;
+pub const ZSW_SAMTEXT_INFO_MIN_LEN: usize = 11;
+pub const ZSW_SAMTEXT_INFO_MAX_LEN: usize = 12;
+pub const ZSW_SAMTEXT_INFO_WORDS: usize = 13;
+
+/// `zsw_sam_parsed`: what `zsw_sam_parse_batch` keeps of a SAM line beside its `ZswAlignment`
+#[repr(C)]
+#[derive(Clone, Copy, Default, Debug, PartialEq, Eq)]
+pub struct ZswSamParsed {
+    pub pos:  u64,
+    pub line: u64,
+    pub flag: u16,
+    pub mapq: u8,
+    pub code: u8,
+    pub bits: u32,
+}
+
+/// `zsw_sam_parse_out`: the output arrays of `zsw_sam_parse_batch` and their capacities, in entries
+#[repr(C)]
+pub struct ZswSamParseOut {
+    pub bases:         *mut u8,
+    pub quals:         *mut u8,
+    pub base_cap:      u64,
+    pub offsets:       *mut u64,
+    pub qnames:        *mut u8,
+    pub name_cap:      u64,
+    pub qname_offsets: *mut u64,
+    pub aln:           *mut ZswAlignment,
+    pub status:        *mut u8,
+    pub inc:           *mut u32,
+    pub op:            *mut u8,
+    pub ciglet_cap:    u64,
+    pub strand:        *mut u8,
+    pub parsed:        *mut c_void,
+    pub record_cap:    u64,
+}
+
+/// What `sam_parse_batch` returns: record i is `aln[i]` with `status[i]` and its ciglets in `inc` / `op`; its read, qualities and
+/// name lie as in a `FastqBatch`; `strand[i]` is FLAG & 16 and `parsed[i]` the rest of the line.
+#[derive(Clone, Default)]
+pub struct SamBatch {
+    pub bases:        Vec<u8>,
+    pub quals:        Vec<u8>,
+    pub offsets:      Vec<u64>,
+    pub names:        Vec<u8>,
+    pub name_offsets: Vec<u64>,
+    pub aln:          Vec<ZswAlignment>,
+    pub status:       Vec<u8>,
+    pub inc:          Vec<u32>,
+    pub op:           Vec<u8>,
+    pub strand:       Vec<u8>,
+    pub parsed:       Vec<ZswSamParsed>,
+    pub report:       [u64; ZSW_SAMTEXT_INFO_WORDS],
+}
+
 pub const ZSW_OK: i32 = 0;
 pub const ZSW_MEM_HOST: i32 = 0;
 pub const ZSW_ENCODING_BYTES: i32 = 0;
@@ -275,6 +368,7 @@ unsafe extern "C" {
     fn zsw_consensus_from_counts(ctx: *mut ZswContext, counts: *const c_void, len: u64, mem: i32, flags: i32, fallback: *const u8, out_seq: *mut u8, stream: *mut c_void) -> i32;
     fn zsw_sam_batch(ctx: *mut ZswContext, reads: *const ZswBatch, fields: *const c_void, flags: i32, aln: *const ZswAlignment, status: *const u8, inc: *const u32, op: *const u8, n_ciglets: u64, out_text: *mut u8, text_cap: u64, out_n_bytes: *mut u64, out_line_offsets: *mut u64, out_n_bad: *mut u64, stream: *mut c_void) -> i32;
     fn zsw_fastq_parse_batch(ctx: *mut ZswContext, text: *const u8, n_bytes: u64, mem: i32, flags: i32, out_bases: *mut u8, out_quals: *mut u8, base_cap: u64, out_offsets: *mut u64, out_qnames: *mut u8, name_cap: u64, out_qname_offsets: *mut u64, record_cap: u64, out_info: *mut u64, stream: *mut c_void) -> i32;
+    fn zsw_sam_parse_batch(ctx: *mut ZswContext, text: *const u8, n_bytes: u64, mem: i32, flags: i32, rname: *const c_char, rname_len: u32, ref_len: u32, out: *const c_void, out_info: *mut u64, stream: *mut c_void) -> i32;
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -1034,6 +1128,68 @@ impl GpuContext {
         out.names.truncate(out.report[ZSW_FASTQ_INFO_NAME_BYTES] as usize);
         out.offsets.truncate(records + 1);
         out.name_offsets.truncate(records + 1);
+        Ok(out)
+    }
+
+    /// `zsw_sam_parse_batch` over SAM text in host memory: the data lines `SAMReader` yields in front of its first error, each
+    /// converted as `SamData::to_alignment` does (`ref_len` is the reference's length; with `rname` the records of every other
+    /// RNAME are unmapped), and the report (`ZSW_SAMTEXT_INFO_*`). `last`: the buffer ends the file (`ZSW_SAMTEXT_FINAL`);
+    /// otherwise parse on from `report[ZSW_SAMTEXT_INFO_CONSUMED]` with the next chunk appended. `qual_forward`: QUAL of a FLAG 16
+    /// record is stored back to front, as `zsw_sam_batch` expects it. The capacities are the bounds that always suffice.
+    pub fn sam_parse_batch(&self, text: &[u8], last: bool, qual_forward: bool, rname: Option<&[u8]>, ref_len: u32) -> Result<SamBatch, GpuError> {
+        let n = text.len() as u64;
+        let flags = if last { ZSW_SAMTEXT_FINAL } else { 0 } | if qual_forward { ZSW_SAMTEXT_QUAL_FORWARD } else { 0 };
+        let (base_cap, name_cap, ciglet_cap, record_cap) = (n, n, n / 2, n / 14 + 1);
+        let mut out = SamBatch {
+            bases: vec![0u8; base_cap as usize],
+            quals: vec![0u8; base_cap as usize],
+            offsets: vec![0u64; record_cap as usize + 1],
+            names: vec![0u8; name_cap as usize],
+            name_offsets: vec![0u64; record_cap as usize + 1],
+            aln: vec![ZswAlignment::default(); record_cap as usize],
+            status: vec![0u8; record_cap as usize],
+            inc: vec![0u32; ciglet_cap as usize],
+            op: vec![0u8; ciglet_cap as usize],
+            strand: vec![0u8; record_cap as usize],
+            parsed: vec![ZswSamParsed::default(); record_cap as usize],
+            report: [0u64; ZSW_SAMTEXT_INFO_WORDS],
+        };
+        let arrays = ZswSamParseOut {
+            bases: out.bases.as_mut_ptr(),
+            quals: out.quals.as_mut_ptr(),
+            base_cap,
+            offsets: out.offsets.as_mut_ptr(),
+            qnames: out.names.as_mut_ptr(),
+            name_cap,
+            qname_offsets: out.name_offsets.as_mut_ptr(),
+            aln: out.aln.as_mut_ptr(),
+            status: out.status.as_mut_ptr(),
+            inc: out.inc.as_mut_ptr(),
+            op: out.op.as_mut_ptr(),
+            ciglet_cap,
+            strand: out.strand.as_mut_ptr(),
+            parsed: out.parsed.as_mut_ptr().cast::<c_void>(),
+            record_cap,
+        };
+        let (rname_ptr, rname_len) = rname.map_or((ptr::null(), 0), |r| (r.as_ptr().cast::<c_char>(), r.len() as u32));
+        // SAFETY: every array holds the capacity it is declared with; the report holds ZSW_SAMTEXT_INFO_WORDS entries
+        let code = unsafe {
+            zsw_sam_parse_batch(self.raw, text.as_ptr(), n, ZSW_MEM_HOST, flags, rname_ptr, rname_len, ref_len, (&arrays as *const ZswSamParseOut).cast::<c_void>(), out.report.as_mut_ptr(),
+                                ptr::null_mut())
+        };
+        self.check(code, 0, 0)?;
+        let records = out.report[ZSW_SAMTEXT_INFO_RECORDS] as usize;
+        out.bases.truncate(out.report[ZSW_SAMTEXT_INFO_BASES] as usize);
+        out.quals.truncate(out.report[ZSW_SAMTEXT_INFO_BASES] as usize);
+        out.names.truncate(out.report[ZSW_SAMTEXT_INFO_NAME_BYTES] as usize);
+        out.offsets.truncate(records + 1);
+        out.name_offsets.truncate(records + 1);
+        out.aln.truncate(records);
+        out.status.truncate(records);
+        out.strand.truncate(records);
+        out.parsed.truncate(records);
+        out.inc.truncate(out.report[ZSW_SAMTEXT_INFO_CIGLETS] as usize);
+        out.op.truncate(out.report[ZSW_SAMTEXT_INFO_CIGLETS] as usize);
         Ok(out)
     }
 

@@ -5,7 +5,7 @@
 //
 //   g++ -O2 -std=c++17 -Iinclude examples/zsw_driver.cpp -o examples/zsw_driver -Lzoe_amd -lzoe_sw_hip -Wl,-rpath,$PWD/zoe_amd
 //   ./examples/zsw_driver reference.txt reads.fastq [--score-only | --3pass | --both-strands] [--min-score T] [--nm] [--verbose-cigar] [--device-sam]
-//                         [--consensus FILE] [--device-fastq]
+//                         [--consensus FILE] [--device-fastq] [--from-sam FILE]
 // --both-strands: every read is aligned on whichever strand scores higher (sw_align_strands_from_i8_3pass); a read answered by
 // its reverse complement gets flag 16, SEQ reverse complemented and QUAL reversed, and POS / CIGAR are those of that sequence.
 // --min-score T (with --3pass or --score-only, the calls ZSW_OPTION_MIN_SCORE covers): a read that scores less than T is written as
@@ -21,6 +21,10 @@
 // --device-fastq: the FASTQ file is read with one fread and parsed on the GPU (zsw_fastq_parse_batch with ZSW_FASTQ_FINAL |
 // ZSW_FASTQ_NAME_TO_BLANK) instead of line by line on the host; a malformed record ends the driver with exit status 1 and a message
 // naming the code and the record. Everything downstream, and the output, is the same.
+// --from-sam FILE: the records come from a SAM file instead of from an alignment call: one fread and one zsw_sam_parse_batch (with
+// ZSW_SAMTEXT_FINAL | ZSW_SAMTEXT_QUAL_FORWARD, the loaded reference's name as RNAME and its length as ref_len); the reads argument is
+// not opened (pass -). --nm, --verbose-cigar, --device-sam and --consensus work on these records as on aligned ones: run on a file the
+// driver wrote, --device-sam writes that file again. A line the reader rejects ends the driver with exit status 1, naming the line.
 #include <algorithm>
 #include <cstdio>
 #include <cstdlib>
@@ -49,14 +53,27 @@ static std::string read_reference(const std::string& path, std::string* name) {
     return seq;
 }
 
+static std::string read_whole(const std::string& path) {
+    std::FILE* f = std::fopen(path.c_str(), "rb");
+    if (!f) throw std::runtime_error("cannot open " + path);
+    std::fseek(f, 0, SEEK_END);
+    const long size = std::ftell(f);
+    std::fseek(f, 0, SEEK_SET);
+    std::string text(size > 0 ? (size_t)size : 0, '\0');
+    const size_t got = text.empty() ? 0 : std::fread(&text[0], 1, text.size(), f);
+    std::fclose(f);
+    if (got != text.size()) throw std::runtime_error("cannot read " + path);
+    return text;
+}
+
 int main(int argc, char** argv) {
     if (argc < 3) {
-        std::cerr << "usage: zsw_driver reference.(fa|txt) reads.fastq [--score-only | --3pass | --both-strands] [--min-score T] [--nm] [--verbose-cigar] [--device-sam] [--consensus FILE] [--device-fastq]\n";
+        std::cerr << "usage: zsw_driver reference.(fa|txt) reads.fastq [--score-only | --3pass | --both-strands] [--min-score T] [--nm] [--verbose-cigar] [--device-sam] [--consensus FILE] [--device-fastq] [--from-sam FILE]\n";
         return 2;
     }
     bool score_only = false, three_pass = false, both_strands = false, nm = false, verbose_cigar = false, device_sam = false, device_fastq = false;
     long long min_score = 0;
-    std::string consensus_path;
+    std::string consensus_path, from_sam;
     for (int k = 3; k < argc; ++k) {
         if (!std::strcmp(argv[k], "--score-only")) score_only = true;
         else if (!std::strcmp(argv[k], "--3pass")) three_pass = true;  // sw_align_from_i8_3pass instead of sw_align_from_i8
@@ -67,6 +84,7 @@ int main(int argc, char** argv) {
         else if (!std::strcmp(argv[k], "--device-sam")) device_sam = true;
         else if (!std::strcmp(argv[k], "--device-fastq")) device_fastq = true;
         else if (!std::strcmp(argv[k], "--consensus") && k + 1 < argc) consensus_path = argv[++k];
+        else if (!std::strcmp(argv[k], "--from-sam") && k + 1 < argc) from_sam = argv[++k];
         else {
             std::cerr << "zsw_driver: unknown argument " << argv[k] << '\n';
             return 2;
@@ -80,21 +98,34 @@ int main(int argc, char** argv) {
         std::cerr << "zsw_driver: --consensus needs alignments; it does not go with --score-only\n";
         return 2;
     }
+    if (!from_sam.empty() && (score_only || three_pass || both_strands || min_score > 0 || device_fastq)) {
+        std::cerr << "zsw_driver: --from-sam takes its records from the file; it goes with --nm, --verbose-cigar, --device-sam and --consensus only\n";
+        return 2;
+    }
     try {
         std::string ref_name;
         const std::string reference = read_reference(argv[1], &ref_name);
         std::vector<std::string> names, reads, quals;
         std::unique_ptr<zoe::GpuContext> ctx_holder;
-        if (device_fastq) {  // the whole file with one fread, the records from zsw_fastq_parse_batch
-            std::FILE* f = std::fopen(argv[2], "rb");
-            if (!f) throw std::runtime_error(std::string("cannot open ") + argv[2]);
-            std::fseek(f, 0, SEEK_END);
-            const long size = std::ftell(f);
-            std::fseek(f, 0, SEEK_SET);
-            std::string text(size > 0 ? (size_t)size : 0, '\0');
-            const size_t got = text.empty() ? 0 : std::fread(&text[0], 1, text.size(), f);
-            std::fclose(f);
-            if (got != text.size()) throw std::runtime_error(std::string("cannot read ") + argv[2]);
+        std::vector<zoe::MaybeAligned<zoe::Alignment>> sam_alns;
+        std::vector<uint8_t> sam_strands;
+        if (!from_sam.empty()) {  // the whole file with one fread, records and reads from zsw_sam_parse_batch
+            const std::string text = read_whole(from_sam);
+            ctx_holder.reset(new zoe::GpuContext(0));
+            zoe::SamRecords sam = ctx_holder->parse_sam(text, true, true, ref_name, (uint32_t)reference.size());
+            if (sam.error())
+                throw std::runtime_error("malformed SAM: line " + std::to_string(sam.report[ZSW_SAMTEXT_INFO_ERROR_LINE] + 1) + " (byte " +
+                                         std::to_string(sam.report[ZSW_SAMTEXT_INFO_ERROR_OFFSET]) + "): " + zoe::SamRecords::error_text(sam.error()) + " (code " +
+                                         std::to_string(sam.error()) + ")");
+            names = std::move(sam.names);
+            quals = std::move(sam.quals);
+            sam_alns = std::move(sam.alns);
+            sam_strands = std::move(sam.strands);
+            // SEQ is the read as aligned; the profile classes take the reads as sequenced and orient them by strand
+            const zoe::WeightMatrix w = zoe::WeightMatrix::new_dna_matrix(2, -5, 'N');
+            reads = sam.reads.empty() ? sam.reads : zoe::LocalProfilesBatch(*ctx_holder, sam.reads, w, -10, -1).orient(sam_strands);
+        } else if (device_fastq) {  // the whole file with one fread, the records from zsw_fastq_parse_batch
+            const std::string text = read_whole(argv[2]);
             ctx_holder.reset(new zoe::GpuContext(0));
             zoe::FastqRecords fastq = ctx_holder->parse_fastq(text, true, true);
             if (fastq.error())
@@ -125,27 +156,29 @@ int main(int argc, char** argv) {
                 std::cout << names[i] << '\t' << (scores[i].is_some() ? std::to_string(scores[i].value) : std::string("*")) << '\n';
             return 0;
         }
-        auto alns = both_strands ? profiles.sw_align_strands_from_i8_3pass(reference)
-                    : three_pass ? profiles.sw_align_from_i8_3pass(reference)
-                                 : profiles.sw_align_from_i8(reference);
+        auto alns = !from_sam.empty() ? std::move(sam_alns)
+                    : both_strands  ? profiles.sw_align_strands_from_i8_3pass(reference)
+                    : three_pass    ? profiles.sw_align_from_i8_3pass(reference)
+                                    : profiles.sw_align_from_i8(reference);
+        // which strand each alignment is of: from a strand-aware call, or FLAG & 16 of the file's lines
+        const std::vector<uint8_t>* strands = !from_sam.empty() ? &sam_strands : both_strands ? &profiles.last_strands() : nullptr;
         if (!consensus_path.empty()) {
-            const zoe::Pileup pile = profiles.pileup(alns, reference, false, false, both_strands ? &profiles.last_strands() : nullptr);
+            const zoe::Pileup pile = profiles.pileup(alns, reference, false, false, strands);
             std::ofstream fa(consensus_path);
             if (!fa) throw std::runtime_error("cannot write " + consensus_path);
             fa << '>' << ref_name << "_consensus\n" << ctx.plurality_acgtn(pile.counts, &reference) << '\n';
         }
         zoe::Annotation ann;  // NM and = / X CIGARs: one pass over the alignments, against the reads as aligned
-        if (nm || verbose_cigar) ann = profiles.annotate(alns, reference, false, false, verbose_cigar, both_strands ? &profiles.last_strands() : nullptr);
+        if (nm || verbose_cigar) ann = profiles.annotate(alns, reference, false, false, verbose_cigar, strands);
         if (device_sam) {  // the body from zsw_sam_batch: SEQ oriented, QUAL reversed and the decimals written on the device
             std::cout << "@HD\tVN:1.6\n@SQ\tSN:" << ref_name << "\tLN:" << reference.size() << '\n' << std::flush;
-            const std::string text = profiles.sam_text(verbose_cigar ? ann.verbose : alns, names, quals, ref_name, 255, both_strands ? &profiles.last_strands() : nullptr,
-                                                       nm ? &ann : nullptr);
+            const std::string text = profiles.sam_text(verbose_cigar ? ann.verbose : alns, names, quals, ref_name, 255, strands, nm ? &ann : nullptr);
             std::fwrite(text.data(), 1, text.size(), stdout);
             return 0;
         }
         std::vector<uint8_t> strand(reads.size(), 0);
-        if (both_strands) {  // SEQ and QUAL as aligned: the reverse complement of a read answered on the reverse strand, its qualities reversed
-            strand = profiles.last_strands();
+        if (strands) {  // SEQ and QUAL as aligned: the reverse complement of a read answered on the reverse strand, its qualities reversed
+            strand = *strands;
             reads = profiles.orient(strand);
             for (size_t i = 0; i < reads.size(); ++i)
                 if (strand[i]) std::reverse(quals[i].begin(), quals[i].end());

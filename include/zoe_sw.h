@@ -503,6 +503,122 @@ zsw_error zsw_fastq_parse_batch(zsw_context* ctx, const uint8_t* text, uint64_t 
                                 uint8_t* out_quals, uint64_t base_cap, uint64_t* out_offsets, uint8_t* out_qnames, uint64_t name_cap,
                                 uint64_t* out_qname_offsets, uint64_t record_cap, uint64_t* out_info, void* stream);
 
+/* ---- SAM parsed on the device ----------------------------------------------------------------------- */
+/* zsw_sam_parse_batch turns a buffer of SAM text into the arrays zsw_annotate_batch, zsw_sam_batch, zsw_pileup_batch and (through
+ * the pile-up) zsw_consensus_from_counts take: per data line a zsw_alignment with its status and its ciglets in inc / op, and the
+ * reads as bases / quals / qnames with offsets, as zsw_fastq_parse_batch leaves them. Lines and fields are SAMReader's
+ * (src/data/records/sam/reader.rs:189-286), records SamData::is_unmapped / to_alignment's (sam/mod.rs:305-354), ciglets as
+ * AlignmentStates::try_from(&Cigar) builds them (src/alignment/types/std_traits.rs:119-155).
+ * Lines (BufRead::lines): a line ends at '\n'; one '\n' and then one '\r' in front of it are removed, a bare trailing '\r' stays.
+ * With ZSW_SAMTEXT_FINAL a non-empty unterminated tail is a line; without it the tail is neither parsed nor an error and CONSUMED
+ * says where the caller restarts. Nothing behind the last '\n' is a line. A line that starts with '@' is a header line: counted
+ * and skipped, wherever it stands. A blank line is a data line with one field.
+ * Reader errors: per line the first failing check, in this order, is the line's code, and delivery ends in front of the line with
+ * the lowest index that has one — what a consumer who stops at the first Err has seen; a minimum over the lines, not an order of
+ * arrival:
+ *   1 ZSW_SAMTEXT_INVALID_UTF8     the line is not UTF-8 by String::from_utf8 (header lines too)
+ *   2 ZSW_SAMTEXT_TOO_FEW_FIELDS   fewer than 11 tab-separated fields
+ *   3 ZSW_SAMTEXT_INVALID_FLAG     | str::parse::<u16 / usize / u8>: one optional '+', then at least one ASCII digit and nothing
+ *   4 ZSW_SAMTEXT_INVALID_POS      | else; leading zeros are allowed; the value must be within the type (usize is 64-bit); "-0",
+ *   5 ZSW_SAMTEXT_INVALID_MAPQ     | "+", an empty field and a blank inside the field are errors
+ *   6 ZSW_SAMTEXT_INVALID_QUALITY  QUAL is neither empty nor "*" and holds a byte outside '!' ..= '~'
+ * RNEXT, PNEXT and TLEN are not looked at. The CIGAR is not validated by the reader: it is trim_ascii-ed, and "*" is the empty CIGAR.
+ * Score: what opt_fields.get("AS") followed by .int() gives (sam/mod.rs:517-540, 581-633). The optional fields are taken in order; a
+ * field without a ':' in front of the AS field is an Err; the first field whose tag text is "AS" decides: its type must be the single
+ * character 'i' and its value must parse as i64 (optional '+' / '-', then digits). Ok(Some(v)) with 0 <= v <= 2^32 - 1 is the score;
+ * everything else is score 0 and ZSW_SAMREC_BIT_NO_SCORE.
+ * Conversion, for every delivered data line i, into status[i], aln[i] and the ciglets:
+ *  1. Unmapped iff FLAG & 4, or the sum of inc over the M D N = X ciglets that the UNCHECKED CigletIterator yields is 0
+ *     (cigar/iter.rs:52-99: left to right; it stops silently at the first byte that is neither digit nor op, at an op without digits,
+ *     or at an inc beyond 64 bits; it yields incs of 0 and ignores trailing digits — "0M", "5I3Q" and "Q" are unmapped with code 0):
+ *     ZSW_STATUS_UNMAPPED and a zeroed record.
+ *  2. With `rname` given, a line whose RNAME differs from it byte for byte: ZSW_STATUS_UNMAPPED, a zeroed record and
+ *     ZSW_SAMREC_BIT_OTHER_RNAME; no conversion is attempted (the context has one reference; files name several).
+ *  3. Otherwise the record is converted; the first code in this order makes it ZSW_STATUS_UNMAPPED, zeroed, with the code in
+ *     parsed[i].code, and counts it in CODED:
+ *       1 ZSW_SAMREC_SEQ_MISSING           SEQ is empty or "*"
+ *       2 ZSW_SAMREC_CIGAR_INVALID_OP      | the first error of CigletIteratorChecked (iter.rs:478-537): a byte that is neither
+ *       3 ZSW_SAMREC_CIGAR_MISSING_INC     | digit nor one of MIDNSHPX=, an op without digits, an inc of 0, an inc beyond 64 bits,
+ *       4 ZSW_SAMREC_CIGAR_INC_ZERO        | digits without an op behind them
+ *       5 ZSW_SAMREC_CIGAR_INC_OVERFLOW    |
+ *       6 ZSW_SAMREC_CIGAR_MISSING_OP      |
+ *       7 ZSW_SAMREC_CIGAR_MERGE_OVERFLOW  the merged inc of adjacent equal ops leaves 64 bits
+ *       8 ZSW_SAMREC_POS_ZERO              pos - 1 would underflow
+ *       9 ZSW_SAMREC_CLIPS_EXCEED_SEQ      query_len - soft_clipping would underflow
+ *      10 ZSW_SAMREC_TOO_LARGE             a merged inc, pos - 1 + ref_len_in_alignment, the number of ciglets or the length of SEQ
+ *                                          does not fit the 32-bit fields of zsw_alignment (all sums 64-bit and saturating)
+ *     Where the reference returns Err or panics on a record with two of these faults, which of the two it names may differ from this
+ *     order (it subtracts pos - 1 and the clips before it validates the CIGAR, and meets a merge overflow before a later ciglet's
+ *     error). Neither side ever delivers such a record as an alignment.
+ *  4. A converted record is ZSW_STATUS_SOME with score from AS, ref_start = pos - 1, ref_end = ref_start + ref_len_in_alignment,
+ *     ref_len = the call's argument, query_len = the length of SEQ. The soft clips are taken from the RAW ciglets, before merging:
+ *     from the front one optional H and then one optional S; from the back the same, among the ciglets the front has not consumed
+ *     ("2S3S5M" clips 2 in front); query_start = front, query_end = front + (query_len - front - back). The ciglets are the
+ *     checked ciglets with adjacent equal ops merged ("3M2M" is 5M; no inc is 0), laid out in record order: ciglet_offset /
+ *     n_ciglets point into inc / op, and no atomic decides a place. As in the reference, SEQ's length is not compared with the
+ *     CIGAR's query length: zsw_annotate_batch and zsw_pileup_batch report such records as bad.
+ * Reads: SEQ bytes go to bases as they stand (a missing SEQ is a read of length 0 with ZSW_SAMREC_BIT_SEQ_MISSING), QNAME bytes to
+ * qnames, QUAL to quals in the layout of bases. A QUAL that is missing, or whose length differs from SEQ's, fills its slot with '!'
+ * and sets ZSW_SAMREC_BIT_QUAL_MISSING or ZSW_SAMREC_BIT_QUAL_LENGTH (the reference accepts both kinds of line). With
+ * ZSW_SAMTEXT_QUAL_FORWARD the QUAL of a record with FLAG & 16 is stored back to front: (bases, quals, strand) is then what
+ * zsw_sam_fields expects, and zsw_sam_batch -> zsw_sam_parse_batch -> zsw_sam_batch gives the same bytes.
+ * out: a zsw_sam_parse_out (declared const void*, as `fields` of zsw_sam_batch). text and every array of it live where `mem` says;
+ * rname and out_info are host memory. out_info holds ZSW_SAMTEXT_INFO_WORDS entries, always filled by a call that gets past its
+ * argument checks: RECORDS (data lines delivered), HEADERS (header lines in front of CONSUMED), BASES, NAME_BYTES, CIGLETS, CONSUMED
+ * (the offset one past the last delivered line), ERROR = 0 or a reader code with ERROR_LINE the failing line's index among all lines
+ * and ERROR_OFFSET its first byte (both 0 without an error), MAPPED (records with status SOME), CODED, MIN_LEN / MAX_LEN over the
+ * delivered reads. A malformed file is ZSW_OK and a report, never a fault: every position derived from the text is checked in 64-bit
+ * arithmetic before the load that uses it. n_bytes == 0 is ZSW_OK with nothing delivered.
+ * Capacity protocol, as for zsw_fastq_parse_batch: RECORDS > record_cap, BASES > base_cap, NAME_BYTES > name_cap or CIGLETS >
+ * ciglet_cap is ZSW_ERR_INVALID_ARGUMENT with the needed sizes in out_info and no byte of any output written; every output NULL with
+ * every capacity 0 is the sizing call (ZSW_OK). Bounds that always suffice, so that a caller can do without the sizing call:
+ *   base_cap = n_bytes,  name_cap = n_bytes,  ciglet_cap = n_bytes / 2,  record_cap = n_bytes / 14 + 1
+ * (the shortest data line is ten tabs and three digits). quals, qnames together with qname_offsets, strand and parsed may be NULL:
+ * that part is not written (NAME_BYTES is still reported). Unknown flag bits, a null required pointer (ctx, out, out_info; text with
+ * n_bytes > 0; bases, offsets, aln, status, inc, op outside the sizing call; one of qnames / qname_offsets or of rname / rname_len
+ * without the other), rname_len > 255, an unknown mem, or an output that overlaps the text or another output:
+ * ZSW_ERR_INVALID_ARGUMENT, nothing written, out_info included. More than 2^36 bytes or 2^31 lines per call: ZSW_ERR_UNSUPPORTED.
+ * The launches: the newline index of zsw_fastq_parse_batch, a line pass (one wavefront per line), six exclusive sums over the
+ * delivered lines, a gather that walks each CIGAR once more to write its ciglets; a minimum and a min / max are the only atomics and
+ * the outputs are the same on every run. Device calls synchronise the stream once, for the report; the workspace for the newline
+ * positions is sized for a line per 64 bytes before the count is known, and a denser text makes the call repeat its later launches
+ * once with the exact size. Host calls are staged and synchronous. The call needs neither scoring nor a reference, ZSW_OPTION_* do
+ * not matter, and zsw_group_* does not cover it. Workspace, kept by the context until zsw_destroy: 8 bytes per newline, 176 bytes
+ * per line (n_bytes * 2.75 at least), 16 bytes per tile, the scans' scratch, and the staged text and outputs of a host call. */
+typedef struct zsw_sam_parsed {        /* 24 bytes, one per delivered record */
+    uint64_t pos;                      /* POS as parsed (1-based; 0 allowed on unmapped lines) */
+    uint64_t line;                     /* index of the record's line among ALL lines of the text, headers included */
+    uint16_t flag;                     /* FLAG */
+    uint8_t  mapq;                     /* MAPQ */
+    uint8_t  code;                     /* 0, or a ZSW_SAMREC_* conversion code */
+    uint32_t bits;                     /* ZSW_SAMREC_BIT_* */
+} zsw_sam_parsed;
+typedef struct zsw_sam_parse_out {     /* zero-initialise; every array lives where `mem` says; caps in entries */
+    uint8_t*  bases;    uint8_t* quals;          /* quals optional; laid out exactly as bases */
+    uint64_t  base_cap; uint64_t* offsets;       /* record_cap + 1 */
+    uint8_t*  qnames;   uint64_t name_cap; uint64_t* qname_offsets; /* both or neither; record_cap + 1 */
+    zsw_alignment* aln; uint8_t* status;         /* record_cap each */
+    uint32_t* inc;      uint8_t* op; uint64_t ciglet_cap;
+    uint8_t*  strand;                            /* optional, record_cap: (FLAG & 16) != 0 */
+    void*     parsed;                            /* optional, record_cap zsw_sam_parsed */
+    uint64_t  record_cap;
+} zsw_sam_parse_out;
+enum { ZSW_SAMTEXT_FINAL = 1, ZSW_SAMTEXT_QUAL_FORWARD = 2 };
+enum { ZSW_SAMTEXT_INVALID_UTF8 = 1, ZSW_SAMTEXT_TOO_FEW_FIELDS = 2, ZSW_SAMTEXT_INVALID_FLAG = 3, ZSW_SAMTEXT_INVALID_POS = 4,
+       ZSW_SAMTEXT_INVALID_MAPQ = 5, ZSW_SAMTEXT_INVALID_QUALITY = 6 };
+enum { ZSW_SAMREC_SEQ_MISSING = 1, ZSW_SAMREC_CIGAR_INVALID_OP = 2, ZSW_SAMREC_CIGAR_MISSING_INC = 3, ZSW_SAMREC_CIGAR_INC_ZERO = 4,
+       ZSW_SAMREC_CIGAR_INC_OVERFLOW = 5, ZSW_SAMREC_CIGAR_MISSING_OP = 6, ZSW_SAMREC_CIGAR_MERGE_OVERFLOW = 7, ZSW_SAMREC_POS_ZERO = 8,
+       ZSW_SAMREC_CLIPS_EXCEED_SEQ = 9, ZSW_SAMREC_TOO_LARGE = 10 };
+enum { ZSW_SAMREC_BIT_NO_SCORE = 1, ZSW_SAMREC_BIT_OTHER_RNAME = 2, ZSW_SAMREC_BIT_SEQ_MISSING = 4, ZSW_SAMREC_BIT_QUAL_MISSING = 8,
+       ZSW_SAMREC_BIT_QUAL_LENGTH = 16 };
+enum { ZSW_SAMTEXT_INFO_RECORDS = 0, ZSW_SAMTEXT_INFO_HEADERS = 1, ZSW_SAMTEXT_INFO_BASES = 2, ZSW_SAMTEXT_INFO_NAME_BYTES = 3,
+       ZSW_SAMTEXT_INFO_CIGLETS = 4, ZSW_SAMTEXT_INFO_CONSUMED = 5, ZSW_SAMTEXT_INFO_ERROR = 6, ZSW_SAMTEXT_INFO_ERROR_LINE = 7,
+       ZSW_SAMTEXT_INFO_ERROR_OFFSET = 8, ZSW_SAMTEXT_INFO_MAPPED = 9, ZSW_SAMTEXT_INFO_CODED = 10, ZSW_SAMTEXT_INFO_MIN_LEN = 11,
+       ZSW_SAMTEXT_INFO_MAX_LEN = 12, ZSW_SAMTEXT_INFO_WORDS = 13 };
+zsw_error zsw_sam_parse_batch(zsw_context* ctx, const uint8_t* text, uint64_t n_bytes, zsw_mem mem, int flags,
+                              const char* rname /* HOST, optional */, uint32_t rname_len, uint32_t ref_len,
+                              const void* out /* zsw_sam_parse_out */, uint64_t* out_info /* host */, void* stream);
+
 /* ---- pre-alignment filter ------------------------------------------------------------------ */
 /* out_pass[i] = sneaky_snake(&reference[ref_start[i] .. ref_start[i]+ref_len[i]], read_i, threshold)
  * (src/alignment/sneaky_snake.rs:78-131): the SneakySnake edit-distance filter between a read and a candidate window of the

@@ -173,6 +173,30 @@ struct FastqRecords {
     uint64_t error() const { return report[ZSW_FASTQ_INFO_ERROR]; }
 };
 
+// What GpuContext::parse_sam returns (zsw_sam_parse_batch): the data lines in front of the first malformed line — names, the reads
+// as aligned (SEQ), qualities, the alignments as SamData::to_alignment builds them (Status::Unmapped for unmapped lines, lines of
+// another RNAME and lines with a conversion code), FLAG & 16 per record, the rest of each line — and the report (ZSW_SAMTEXT_INFO_*)
+struct SamRecords {
+    std::vector<std::string> names, reads, quals;
+    std::vector<MaybeAligned<Alignment>> alns;
+    std::vector<uint8_t> strands;
+    std::vector<zsw_sam_parsed> parsed;
+    uint64_t report[ZSW_SAMTEXT_INFO_WORDS] = {};
+    uint64_t error() const { return report[ZSW_SAMTEXT_INFO_ERROR]; }
+    // the reader's words for a ZSW_SAMTEXT_* code
+    static const char* error_text(uint64_t code) {
+        switch (code) {
+            case ZSW_SAMTEXT_INVALID_UTF8: return "the line is not valid UTF-8";
+            case ZSW_SAMTEXT_TOO_FEW_FIELDS: return "SAM file did not have at least 11 fields";
+            case ZSW_SAMTEXT_INVALID_FLAG: return "invalid SAM bit flag";
+            case ZSW_SAMTEXT_INVALID_POS: return "invalid SAM reference position";
+            case ZSW_SAMTEXT_INVALID_MAPQ: return "invalid SAM mapq";
+            case ZSW_SAMTEXT_INVALID_QUALITY: return "invalid quality score byte";
+            default: return "no error";
+        }
+    }
+};
+
 class GpuContext {
   public:
     explicit GpuContext(int device = 0) {
@@ -303,6 +327,47 @@ class GpuContext {
             out.names.emplace_back(qnames.begin() + noff[i], qnames.begin() + noff[i + 1]);
             out.reads.emplace_back(bases.begin() + off[i], bases.begin() + off[i + 1]);
             out.quals.emplace_back(quals.begin() + off[i], quals.begin() + off[i + 1]);
+        }
+        return out;
+    }
+    // zsw_sam_parse_batch over SAM text (host memory): a sizing call, then the call with arrays of the reported sizes. last: the
+    // buffer ends the file (ZSW_SAMTEXT_FINAL); otherwise report[ZSW_SAMTEXT_INFO_CONSUMED] says where the rest begins. qual_forward:
+    // the QUAL of a FLAG 16 line is stored back to front, as sam_text() takes it. rname (empty: none): lines of another RNAME come
+    // back unmapped. ref_len: the ref_len of every alignment. A malformed line does not throw: report[ZSW_SAMTEXT_INFO_ERROR].
+    SamRecords parse_sam(const std::string& text, bool last = true, bool qual_forward = true, const std::string& rname = std::string(), uint32_t ref_len = 0) const {
+        const int flags = (last ? ZSW_SAMTEXT_FINAL : 0) | (qual_forward ? ZSW_SAMTEXT_QUAL_FORWARD : 0);
+        const uint8_t* bytes = reinterpret_cast<const uint8_t*>(text.data());
+        const char* rn = rname.empty() ? nullptr : rname.data();
+        SamRecords out;
+        zsw_sam_parse_out o{};
+        check(zsw_sam_parse_batch(ctx_, bytes, text.size(), ZSW_MEM_HOST, flags, rn, (uint32_t)rname.size(), ref_len, &o, out.report, nullptr));
+        const size_t records = (size_t)out.report[ZSW_SAMTEXT_INFO_RECORDS], n_bases = (size_t)out.report[ZSW_SAMTEXT_INFO_BASES];
+        const size_t n_names = (size_t)out.report[ZSW_SAMTEXT_INFO_NAME_BYTES], n_ciglets = (size_t)out.report[ZSW_SAMTEXT_INFO_CIGLETS];
+        std::vector<uint8_t> bases(n_bases + 1), quals(n_bases + 1), qnames(n_names + 1), status(records + 1), op(n_ciglets + 1);
+        std::vector<uint64_t> off(records + 1), noff(records + 1);
+        std::vector<zsw_alignment> aln(records + 1);
+        std::vector<uint32_t> inc(n_ciglets + 1);
+        out.strands.assign(records + 1, 0);
+        out.parsed.assign(records + 1, zsw_sam_parsed{});
+        o.bases = bases.data(), o.quals = quals.data(), o.base_cap = n_bases, o.offsets = off.data();
+        o.qnames = qnames.data(), o.name_cap = n_names, o.qname_offsets = noff.data();
+        o.aln = aln.data(), o.status = status.data(), o.inc = inc.data(), o.op = op.data(), o.ciglet_cap = n_ciglets;
+        o.strand = out.strands.data(), o.parsed = out.parsed.data(), o.record_cap = records;
+        check(zsw_sam_parse_batch(ctx_, bytes, text.size(), ZSW_MEM_HOST, flags, rn, (uint32_t)rname.size(), ref_len, &o, out.report, nullptr));
+        out.strands.resize(records);
+        out.parsed.resize(records);
+        out.alns.resize(records);
+        for (size_t i = 0; i < records; ++i) {
+            out.names.emplace_back(qnames.begin() + noff[i], qnames.begin() + noff[i + 1]);
+            out.reads.emplace_back(bases.begin() + off[i], bases.begin() + off[i + 1]);
+            out.quals.emplace_back(quals.begin() + off[i], quals.begin() + off[i + 1]);
+            out.alns[i].status = (Status)status[i];
+            if (status[i] != ZSW_STATUS_SOME) continue;
+            Alignment& a = out.alns[i].value;
+            a.score = aln[i].score;
+            a.ref_start = aln[i].ref_start, a.ref_end = aln[i].ref_end, a.query_start = aln[i].query_start, a.query_end = aln[i].query_end;
+            a.ref_len = aln[i].ref_len, a.query_len = aln[i].query_len;
+            for (uint32_t k = 0; k < aln[i].n_ciglets; ++k) a.states.push_back({inc[aln[i].ciglet_offset + k], op[aln[i].ciglet_offset + k]});
         }
         return out;
     }

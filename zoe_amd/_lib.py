@@ -55,6 +55,7 @@ SYMBOLS = [
     "zsw_group_align_3pass_batch_from",
     "zsw_set_complement", "zsw_score_strands_batch_from", "zsw_orient_batch", "zsw_align_3pass_strands_batch_from", "zsw_strand_counts", "zsw_debug_strand_records", "zsw_debug_score_launches",
     "zsw_min_score_counts", "zsw_annotate_batch", "zsw_sam_batch", "zsw_pileup_batch", "zsw_consensus_from_counts", "zsw_fastq_parse_batch",
+    "zsw_sam_parse_batch",
 ]
 
 
@@ -129,6 +130,32 @@ FASTQ_FINAL, FASTQ_NAME_TO_BLANK = 1, 2
  FASTQ_INVALID_QUALITY) = range(1, 9)
 (FASTQ_INFO_RECORDS, FASTQ_INFO_BASES, FASTQ_INFO_NAME_BYTES, FASTQ_INFO_CONSUMED, FASTQ_INFO_ERROR, FASTQ_INFO_ERROR_RECORD, FASTQ_INFO_ERROR_OFFSET,
  FASTQ_INFO_MIN_LEN, FASTQ_INFO_MAX_LEN, FASTQ_INFO_WORDS) = range(10)
+
+# zsw_sam_parse_batch: flags, the reader's codes (SAMTEXT_*), the conversion's codes and bits (SAMREC_*), the words of the report
+SAMTEXT_FINAL, SAMTEXT_QUAL_FORWARD = 1, 2
+(SAMTEXT_INVALID_UTF8, SAMTEXT_TOO_FEW_FIELDS, SAMTEXT_INVALID_FLAG, SAMTEXT_INVALID_POS, SAMTEXT_INVALID_MAPQ, SAMTEXT_INVALID_QUALITY) = range(1, 7)
+(SAMREC_SEQ_MISSING, SAMREC_CIGAR_INVALID_OP, SAMREC_CIGAR_MISSING_INC, SAMREC_CIGAR_INC_ZERO, SAMREC_CIGAR_INC_OVERFLOW, SAMREC_CIGAR_MISSING_OP,
+ SAMREC_CIGAR_MERGE_OVERFLOW, SAMREC_POS_ZERO, SAMREC_CLIPS_EXCEED_SEQ, SAMREC_TOO_LARGE) = range(1, 11)
+SAMREC_BIT_NO_SCORE, SAMREC_BIT_OTHER_RNAME, SAMREC_BIT_SEQ_MISSING, SAMREC_BIT_QUAL_MISSING, SAMREC_BIT_QUAL_LENGTH = 1, 2, 4, 8, 16
+(SAMTEXT_INFO_RECORDS, SAMTEXT_INFO_HEADERS, SAMTEXT_INFO_BASES, SAMTEXT_INFO_NAME_BYTES, SAMTEXT_INFO_CIGLETS, SAMTEXT_INFO_CONSUMED, SAMTEXT_INFO_ERROR,
+ SAMTEXT_INFO_ERROR_LINE, SAMTEXT_INFO_ERROR_OFFSET, SAMTEXT_INFO_MAPPED, SAMTEXT_INFO_CODED, SAMTEXT_INFO_MIN_LEN, SAMTEXT_INFO_MAX_LEN,
+ SAMTEXT_INFO_WORDS) = range(14)
+
+
+class ZswSamParsed(C.Structure):
+    """zsw_sam_parsed: what a delivered SAM line holds beside its zsw_alignment"""
+    _fields_ = [("pos", C.c_uint64), ("line", C.c_uint64), ("flag", C.c_uint16), ("mapq", C.c_uint8), ("code", C.c_uint8), ("bits", C.c_uint32)]
+
+
+class ZswSamParseOut(C.Structure):
+    """zsw_sam_parse_out: the output arrays of zsw_sam_parse_batch and their capacities, in entries"""
+    _fields_ = [
+        ("bases", C.c_void_p), ("quals", C.c_void_p), ("base_cap", C.c_uint64), ("offsets", C.c_void_p),
+        ("qnames", C.c_void_p), ("name_cap", C.c_uint64), ("qname_offsets", C.c_void_p),
+        ("aln", C.c_void_p), ("status", C.c_void_p),
+        ("inc", C.c_void_p), ("op", C.c_void_p), ("ciglet_cap", C.c_uint64),
+        ("strand", C.c_void_p), ("parsed", C.c_void_p), ("record_cap", C.c_uint64),
+    ]
 
 
 class ZswError(RuntimeError):
@@ -231,5 +258,6 @@ def load() -> C.CDLL:
     lib.zsw_pileup_batch.argtypes = [vp, C.POINTER(ZswBatch), C.c_int, vp, u8p, u32p, u8p, C.c_uint64, vp, vp, C.POINTER(C.c_uint64), vp]
     lib.zsw_consensus_from_counts.argtypes = [vp, vp, C.c_uint64, C.c_int, C.c_int, u8p, u8p, vp]
     lib.zsw_fastq_parse_batch.argtypes = [vp, u8p, C.c_uint64, C.c_int, C.c_int, u8p, u8p, C.c_uint64, u64p, u8p, C.c_uint64, u64p, C.c_uint64, C.POINTER(C.c_uint64), vp]
+    lib.zsw_sam_parse_batch.argtypes = [vp, u8p, C.c_uint64, C.c_int, C.c_int, C.c_char_p, C.c_uint32, C.c_uint32, C.POINTER(ZswSamParseOut), C.POINTER(C.c_uint64), vp]
     _lib = lib
     return lib

@@ -248,6 +248,37 @@ class SwContext:
         torch = _torch()
         return int(torch.cuda.current_stream(self.device).cuda_stream)
 
+    def parse_sam(self, d_text, n_bytes: Optional[int] = None, final: bool = True, qual_forward: bool = True, rname=None, ref_len: int = 0):
+        """zsw_sam_parse_batch over SAM text in device memory (a CUDA uint8 tensor): a sizing call, then the call with arrays of exactly
+        the reported sizes. -> (a dict of CUDA tensors: bases, quals, offsets, qnames, qname_offsets (int64), aln (uint8, ALN_DTYPE
+        records), status, inc (int32), op, strand, parsed (uint8, PARSED_DTYPE records); the report as numpy uint64). A reader error is
+        not raised here: report[SAMTEXT_INFO_ERROR]; the arrays hold the records in front of the failing line."""
+        torch = _torch()
+        n = int(d_text.numel() if n_bytes is None else n_bytes)
+        if not (d_text.is_cuda and d_text.dtype == torch.uint8 and d_text.is_contiguous() and d_text.numel() >= n):
+            raise ValueError("d_text: a contiguous CUDA uint8 tensor of at least n_bytes entries")
+        dev = d_text.device
+        flags = (_lib.SAMTEXT_FINAL if final else 0) | (_lib.SAMTEXT_QUAL_FORWARD if qual_forward else 0)
+        rname_b = None if rname is None else (rname.encode() if isinstance(rname, str) else bytes(rname))
+        info = (C.c_uint64 * _lib.SAMTEXT_INFO_WORDS)()
+        o = _lib.ZswSamParseOut()
+        head = (self.h, d_text.data_ptr() if n else None, n, _lib.MEM_DEVICE, flags, rname_b, len(rname_b) if rname_b else 0, int(ref_len))
+        self.check(self.lib.zsw_sam_parse_batch(*head, C.byref(o), info, self.stream()), profile_errors=False)
+        n_rec, n_bases, n_names, n_cig = (int(info[k]) for k in (_lib.SAMTEXT_INFO_RECORDS, _lib.SAMTEXT_INFO_BASES, _lib.SAMTEXT_INFO_NAME_BYTES,
+                                                                 _lib.SAMTEXT_INFO_CIGLETS))
+        new = lambda count, dt: torch.empty(max(count, 1), dtype=dt, device=dev)
+        t = {"bases": new(n_bases, torch.uint8), "quals": new(n_bases, torch.uint8), "offsets": new(n_rec + 1, torch.int64), "qnames": new(n_names, torch.uint8),
+             "qname_offsets": new(n_rec + 1, torch.int64), "aln": new(n_rec * ALN_DTYPE.itemsize, torch.uint8), "status": new(n_rec, torch.uint8),
+             "inc": new(n_cig, torch.int32), "op": new(n_cig, torch.uint8), "strand": new(n_rec, torch.uint8),
+             "parsed": new(n_rec * PARSED_DTYPE.itemsize, torch.uint8)}
+        for k, v in t.items():
+            setattr(o, k, v.data_ptr())
+        o.base_cap, o.name_cap, o.ciglet_cap, o.record_cap = n_bases, n_names, n_cig, n_rec
+        self.check(self.lib.zsw_sam_parse_batch(*head, C.byref(o), info, self.stream()), profile_errors=False)
+        sizes = {"bases": n_bases, "quals": n_bases, "offsets": n_rec + 1, "qnames": n_names, "qname_offsets": n_rec + 1, "aln": n_rec * ALN_DTYPE.itemsize,
+                 "status": n_rec, "inc": n_cig, "op": n_cig, "strand": n_rec, "parsed": n_rec * PARSED_DTYPE.itemsize}
+        return {k: v[:sizes[k]] for k, v in t.items()}, np.array(list(info), dtype=np.uint64)
+
     def selftest(self):
         self.check(self.lib.zsw_selftest(self.h), profile_errors=False)
 
@@ -583,6 +614,8 @@ ALN_DTYPE = np.dtype(
      ("ref_len", "<u4"), ("query_len", "<u4"), ("n_ciglets", "<u4"), ("ciglet_offset", "<u8")]
 )
 
+# zsw_sam_parsed: what zsw_sam_parse_batch keeps of a SAM line beside its record
+PARSED_DTYPE = np.dtype([("pos", "<u8"), ("line", "<u8"), ("flag", "<u2"), ("mapq", "u1"), ("code", "u1"), ("bits", "<u4")])
 
 # zsw_alignment_stats: what zsw_annotate_batch counts along one CIGAR (path_status: a _lib.PATH_* value)
 STATS_DTYPE = np.dtype([("matches", "<u4"), ("mismatches", "<u4"), ("ins_bases", "<u4"), ("del_bases", "<u4"), ("ins_runs", "<u4"), ("del_runs", "<u4"),

@@ -122,6 +122,9 @@ struct zsw_context {
     // zsw_fastq_parse_batch (zsw_fastq.hip): the tile counts and their sum, 8 bytes per newline, the per-record arrays and their
     // sums, the scans' scratch, the state block with the report, the staged text and outputs of a host call
     zsw::DevBuf fq_ws[16];
+    // zsw_sam_parse_batch (zsw_samtext.hip): the newline index as above, 120 bytes and six sums per line, the scans' scratch, the state
+    // block with the report, RNAME, the staged text and outputs of a host call
+    zsw::DevBuf samtext_ws[28];
 };
 
 namespace zsw {

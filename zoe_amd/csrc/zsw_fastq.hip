@@ -114,12 +114,6 @@ __device__ __forceinline__ uint32_t wave_sum(uint32_t x) {
     return x;
 }
 
-__global__ void fq_init_kernel(unsigned long long* state) {
-    for (int k = 0; k < ST_WORDS; ++k) state[k] = 0;
-    state[ST_FIRST_BAD] = ~0ull;
-    state[ST_MIN] = ~0ull;
-}
-
 // POSITIONS = false: tile_counts[t] = the newlines of tile t. POSITIONS = true: pos[rank] for every newline.
 template <bool POSITIONS>
 __global__ __launch_bounds__(TILE_BLOCK) void fq_newline_kernel(FqArgs a) {
@@ -154,6 +148,52 @@ __global__ __launch_bounds__(TILE_BLOCK) void fq_newline_kernel(FqArgs a) {
             }
         }
     }
+}
+
+__device__ __forceinline__ void wave_copy(uint8_t* dst, const uint8_t* src, uint64_t n, int lane) {
+    for (uint64_t j = (uint32_t)lane; j < n; j += FQ_G) dst[j] = src[j];
+}
+
+bool overlaps(const void* a, uint64_t na, const void* b, uint64_t nb) {
+    if (!a || !b || !na || !nb) return false;
+    const uintptr_t x = (uintptr_t)a, y = (uintptr_t)b;
+    return x < y + nb && y < x + na;
+}
+
+uint32_t grid_for(const zsw_context* ctx, uint64_t items, uint32_t per_block) {
+    const uint64_t want = (items + per_block - 1) / per_block;
+    return (uint32_t)std::max<uint64_t>(1, std::min<uint64_t>(want, (uint64_t)ctx->cu_count * 8u));
+}
+
+// The newline index of a.text (text, n_bytes, head, n_tiles, tile_counts, tile_base, pos, pos_cap of `a`) on `stream`: with `count`
+// the newlines per tile and their exclusive sum (a.tile_base[a.n_tiles] = how many there are), then the position of every newline
+// at its rank, as far as pos_cap reaches. scan_tmp: index_scan_bytes. A caller whose workspace for the positions was an estimate
+// finds tile_base[n_tiles] > pos_cap on the device, and calls once more without `count` and with the exact size.
+hipError_t index_scan_bytes(const FqArgs& a, size_t* bytes, hipStream_t stream) {
+    return hipcub::DeviceScan::ExclusiveSum(nullptr, *bytes, a.tile_counts, const_cast<uint64_t*>(a.tile_base), (int)(a.n_tiles + 1), stream);
+}
+hipError_t index_launch(const zsw_context* ctx, const FqArgs& a, bool count, void* scan_tmp, size_t scan_bytes, hipStream_t stream) {
+    if (!a.n_tiles) return hipSuccess;
+    const uint32_t tile_grid = grid_for(ctx, a.n_tiles, FQ_TILE_WAVES);
+    if (count) {
+        hipLaunchKernelGGL((fq_newline_kernel<false>), dim3(tile_grid), dim3(TILE_BLOCK), 0, stream, a);
+        hipError_t e = hipGetLastError();
+        if (e != hipSuccess) return e;
+        e = hipcub::DeviceScan::ExclusiveSum(scan_tmp, scan_bytes, a.tile_counts, const_cast<uint64_t*>(a.tile_base), (int)(a.n_tiles + 1), stream);
+        if (e != hipSuccess) return e;
+    }
+    hipLaunchKernelGGL((fq_newline_kernel<true>), dim3(tile_grid), dim3(TILE_BLOCK), 0, stream, a);
+    return hipGetLastError();
+}
+
+// zsw_samtext.hip includes this file for everything above (the wavefront behind the header's Io, the newline index) and defines
+// ZSW_FASTQ_INDEX_ONLY to leave out what follows: the FASTQ records and the entry point.
+#ifndef ZSW_FASTQ_INDEX_ONLY
+
+__global__ void fq_init_kernel(unsigned long long* state) {
+    for (int k = 0; k < ST_WORDS; ++k) state[k] = 0;
+    state[ST_FIRST_BAD] = ~0ull;
+    state[ST_MIN] = ~0ull;
 }
 
 // what every later launch first asks: how many newlines, how many records; false: the positions did not fit, nothing is done
@@ -207,10 +247,6 @@ struct DeliveredLength {
     __host__ __device__ __forceinline__ uint64_t operator()(uint64_t i) const { return i < *delivered ? len[i] : 0; }
 };
 typedef hipcub::TransformInputIterator<uint64_t, DeliveredLength, hipcub::CountingInputIterator<uint64_t>> LengthIter;
-
-__device__ __forceinline__ void wave_copy(uint8_t* dst, const uint8_t* src, uint64_t n, int lane) {
-    for (uint64_t j = (uint32_t)lane; j < n; j += FQ_G) dst[j] = src[j];
-}
 
 __global__ __launch_bounds__(REC_BLOCK) void fq_gather_kernel(FqArgs a) {
     const int lane = threadIdx.x & 63;
@@ -275,19 +311,11 @@ __global__ void fq_report_kernel(FqArgs a) {
     info[INFO_MAX_LEN] = a.state[ST_MAX];
 }
 
-bool overlaps(const void* a, uint64_t na, const void* b, uint64_t nb) {
-    if (!a || !b || !na || !nb) return false;
-    const uintptr_t x = (uintptr_t)a, y = (uintptr_t)b;
-    return x < y + nb && y < x + na;
-}
-
-uint32_t grid_for(const zsw_context* ctx, uint64_t items, uint32_t per_block) {
-    const uint64_t want = (items + per_block - 1) / per_block;
-    return (uint32_t)std::max<uint64_t>(1, std::min<uint64_t>(want, (uint64_t)ctx->cu_count * 8u));
-}
+#endif  // ZSW_FASTQ_INDEX_ONLY
 
 }  // namespace
 
+#ifndef ZSW_FASTQ_INDEX_ONLY
 extern "C" zsw_error zsw_fastq_parse_batch(zsw_context* ctx, const uint8_t* text, uint64_t n_bytes, zsw_mem mem, int flags, uint8_t* out_bases, uint8_t* out_quals,
                                            uint64_t base_cap, uint64_t* out_offsets, uint8_t* out_qnames, uint64_t name_cap, uint64_t* out_qname_offsets,
                                            uint64_t record_cap, uint64_t* out_info, void* stream_) {
@@ -386,20 +414,14 @@ extern "C" zsw_error zsw_fastq_parse_batch(zsw_context* ctx, const uint8_t* text
         const LengthIter name_in(hipcub::CountingInputIterator<uint64_t>(0), DeliveredLength{a.name_len, a.state + ST_DELIVERED});
         const LengthIter seq_in(hipcub::CountingInputIterator<uint64_t>(0), DeliveredLength{a.seq_len, a.state + ST_DELIVERED});
         size_t tmp_tiles = 0, tmp_names = 0, tmp_seqs = 0;
-        ZSW_HIP(ctx, hipcub::DeviceScan::ExclusiveSum(nullptr, tmp_tiles, a.tile_counts, ws[FW_TILE_BASE].as<uint64_t>(), (int)(a.n_tiles + 1), stream));
+        ZSW_HIP(ctx, index_scan_bytes(a, &tmp_tiles, stream));
         ZSW_HIP(ctx, hipcub::DeviceScan::ExclusiveSum(nullptr, tmp_names, name_in, name_off, scan_items, stream));
         ZSW_HIP(ctx, hipcub::DeviceScan::ExclusiveSum(nullptr, tmp_seqs, seq_in, seq_off, scan_items, stream));
         ZSW_HIP(ctx, ws[FW_SCAN_TMP].ensure(std::max(tmp_tiles, std::max(tmp_names, tmp_seqs)) + 16));
 
         hipLaunchKernelGGL(fq_init_kernel, dim3(1), dim3(1), 0, stream, a.state);
         if (a.n_tiles) {
-            const uint32_t tile_grid = grid_for(ctx, a.n_tiles, FQ_TILE_WAVES);
-            if (round == 0) {
-                hipLaunchKernelGGL((fq_newline_kernel<false>), dim3(tile_grid), dim3(TILE_BLOCK), 0, stream, a);
-                ZSW_HIP(ctx, hipGetLastError());
-                ZSW_HIP(ctx, hipcub::DeviceScan::ExclusiveSum(ws[FW_SCAN_TMP].p, tmp_tiles, a.tile_counts, ws[FW_TILE_BASE].as<uint64_t>(), (int)(a.n_tiles + 1), stream));
-            }
-            hipLaunchKernelGGL((fq_newline_kernel<true>), dim3(tile_grid), dim3(TILE_BLOCK), 0, stream, a);
+            ZSW_HIP(ctx, index_launch(ctx, a, round == 0, ws[FW_SCAN_TMP].p, tmp_tiles, stream));
             hipLaunchKernelGGL(fq_record_kernel, dim3(grid_for(ctx, a.rec_items, FQ_BLOCK_RECORDS)), dim3(REC_BLOCK), 0, stream, a);
         }
         hipLaunchKernelGGL(fq_plan_kernel, dim3(1), dim3(1), 0, stream, a);
@@ -431,3 +453,4 @@ extern "C" zsw_error zsw_fastq_parse_batch(zsw_context* ctx, const uint8_t* text
     }
     return ZSW_OK;
 }
+#endif  // ZSW_FASTQ_INDEX_ONLY

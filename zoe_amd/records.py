@@ -5,6 +5,10 @@ Mirrors, for exactly what the path needs:
     SamData::from_alignment src/data/records/sam/mod.rs:223-245   (POS = ref_range.start + 1, CIGAR = states, AS:i = score;
                             with the stats of `annotate` also NM:i = mismatches + inserted + deleted bases)
     Display for SamData     src/data/records/sam/std_traits.rs:3-44 (tab-separated, optional fields appended)
+    SAMReader               src/data/records/sam/reader.rs:189-286 (rows: a header line or a SamData; the same checks in the same order)
+    SamData::is_unmapped / to_alignment   sam/mod.rs:305-354, over the two ciglet iterators of src/data/types/cigar/iter.rs:52-99, 478-537
+                            and the merge of AlignmentStates::try_from (src/alignment/types/std_traits.rs:119-155)
+    SamOptRaw::get          sam/mod.rs:517-540, 581-633 (the optional fields, parsed lazily)
 """
 from __future__ import annotations
 
@@ -96,6 +100,100 @@ def batch_from_fastq(records: List[FastQ], device: int = 0) -> ReadBatch:
     return ReadBatch.from_sequences([r.sequence for r in records], device)
 
 
+_U64 = (1 << 64) - 1
+_CIGAR_OPS = b"MIDNSHPX="
+
+
+class SamError(ValueError):
+    """std::io::ErrorKind::InvalidData of the reference's SAM reader; `code` is the ZSW_SAMTEXT_* value of the failing check, `line`
+    the index of the line among all lines and `offset` its first byte, where the reader knows them."""
+
+    def __init__(self, code: int, message: str, line: Optional[int] = None, offset: Optional[int] = None):
+        super().__init__(message)
+        self.code, self.line, self.offset = code, line, offset
+
+
+class SamOptError(ValueError):
+    """the Err of SamOptRaw::get"""
+
+
+class SamRecordError(ValueError):
+    """the Err (or panic) of SamData::to_alignment; `code` is a ZSW_SAMREC_* value"""
+
+    def __init__(self, code: int):
+        super().__init__(f"SAM record cannot be converted (code {code})")
+        self.code = code
+
+
+@dataclass
+class SamAlignment:
+    """Alignment<u32> as to_alignment builds it; ciglets: (inc, op byte) with adjacent equal ops merged"""
+    score: int
+    ref_start: int
+    ref_end: int
+    query_start: int
+    query_end: int
+    ref_len: int
+    query_len: int
+    ciglets: list
+
+
+def _rust_parse_int(s: str, lo: int, hi: int, signed: bool = False) -> int:
+    """str::parse for an integer type with the range lo ..= hi: one optional '+' (for a signed type '+' or '-'), then at least one
+    ASCII digit and nothing else; ValueError where it returns Err"""
+    neg = False
+    if s[:1] == "+" or (signed and s[:1] == "-"):
+        neg = s[0] == "-"
+        s = s[1:]
+    if not s or any(c not in "0123456789" for c in s):
+        raise ValueError("invalid digit found in string" if s else "cannot parse integer from empty string")
+    v = -int(s) if neg else int(s)
+    if not lo <= v <= hi:
+        raise ValueError("number too large to fit in target type" if v > hi else "number too small to fit in target type")
+    return v
+
+
+def ciglets_unchecked(cigar: bytes):
+    """CigletIterator (cigar/iter.rs:52-99): (inc, op) left to right; ends silently at a byte that is neither digit nor op, at an op
+    without digits, at an inc beyond 64 bits and at the end (trailing digits are ignored); incs of 0 are yielded"""
+    num, digits = 0, 0
+    for b in cigar:
+        if 48 <= b <= 57:
+            num = num * 10 + (b - 48)
+            digits += 1
+            if num > _U64:
+                return
+        elif b in _CIGAR_OPS:
+            if digits == 0:
+                return
+            yield num, b
+            num, digits = 0, 0
+        else:
+            return
+
+
+def ciglets_checked(cigar: bytes):
+    """CigletIteratorChecked (cigar/iter.rs:478-537): (inc, op) left to right, SamRecordError at its first error"""
+    num, digits = 0, 0
+    for b in cigar:
+        if 48 <= b <= 57:
+            num = num * 10 + (b - 48)
+            digits += 1
+            if num > _U64:
+                raise SamRecordError(_lib.SAMREC_CIGAR_INC_OVERFLOW)
+        elif b in _CIGAR_OPS:
+            if digits == 0:
+                raise SamRecordError(_lib.SAMREC_CIGAR_MISSING_INC)
+            if num == 0:
+                raise SamRecordError(_lib.SAMREC_CIGAR_INC_ZERO)
+            yield num, b
+            num, digits = 0, 0
+        else:
+            raise SamRecordError(_lib.SAMREC_CIGAR_INVALID_OP)
+    if digits:
+        raise SamRecordError(_lib.SAMREC_CIGAR_MISSING_OP)
+
+
 @dataclass
 class SamData:
     qname: str
@@ -124,6 +222,85 @@ class SamData:
     @staticmethod
     def unmapped(qname: str, seq: bytes, qual: bytes) -> "SamData":
         return SamData(qname, 4, "*", 0, 0, "*", "*", 0, 0, seq, qual, [])
+
+    def opt_get(self, tag: str):
+        """SamOptRaw::get (sam/mod.rs:517-540): None, or (type character, value) of the first field with that tag — the value an int
+        for type 'i', else the text as it stands; SamOptError where the reference returns Err."""
+        for f in self.opt_fields:
+            if ":" not in f:
+                raise SamOptError(f"Invalid optional field {f}")
+            this_tag, rest = f.split(":", 1)
+            if this_tag != tag:
+                continue
+            if ":" not in rest:
+                raise SamOptError(f"Invalid optional field {f}")
+            type_text, value = rest.split(":", 1)
+            tb = this_tag.encode("utf-8")
+            if len(tb) != 2 or not (chr(tb[0]).isascii() and chr(tb[0]).isalpha()) or not (chr(tb[1]).isascii() and chr(tb[1]).isalnum()):
+                raise SamOptError(f"Invalid SAM optional tag: {this_tag}")
+            if len(type_text) != 1:
+                raise SamOptError("Missing optional field type" if not type_text else f"Invalid optional field type {type_text}")
+            if type_text == "i":
+                try:
+                    return "i", _rust_parse_int(value, -(1 << 63), (1 << 63) - 1, signed=True)
+                except ValueError as e:
+                    raise SamOptError(f"Failed to parse field '{f}' due to error: {e}") from e
+            return type_text, value
+        return None
+
+    def score(self):
+        """the AS tag as a score: opt_fields.get("AS") then .int(); None unless that is Ok(Some(v)) with 0 <= v <= 2^32 - 1"""
+        try:
+            got = self.opt_get("AS")
+        except SamOptError:
+            return None
+        if got is None or got[0] != "i" or not 0 <= got[1] <= 0xFFFFFFFF:
+            return None
+        return got[1]
+
+    def ref_len_in_alignment(self) -> int:
+        """LenInAlignment over the unchecked CigletIterator (cigar/mod.rs:398-402), the sum saturating at 64 bits"""
+        return min(sum(inc for inc, op in ciglets_unchecked(self.cigar.encode("utf-8")) if op in b"MDN=X"), _U64)
+
+    def is_unmapped(self) -> bool:
+        """sam/mod.rs:352-354"""
+        return bool(self.flag & 4) or self.ref_len_in_alignment() == 0
+
+    def to_alignment(self, score: int, ref_len: int):
+        """sam/mod.rs:305-344 -> None (MaybeAligned::Unmapped) or a SamAlignment; where the reference returns Err or panics, or where
+        a value leaves the 32-bit fields of zsw_alignment, SamRecordError with the first ZSW_SAMREC_* code in the order of
+        include/zoe_sw.h (the reference may name the other fault of a record with two)."""
+        if self.is_unmapped():
+            return None
+        cigar = self.cigar.encode("utf-8")
+        if self.seq in (b"", b"*"):
+            raise SamRecordError(_lib.SAMREC_SEQ_MISSING)
+        raw = list(ciglets_checked(cigar))  # raises the first ciglet error
+        merged: List[list] = []
+        for inc, op in raw:
+            if merged and merged[-1][1] == op:
+                merged[-1][0] += inc
+            else:
+                merged.append([inc, op])
+        if any(inc > _U64 for inc, _ in merged):
+            raise SamRecordError(_lib.SAMREC_CIGAR_MERGE_OVERFLOW)
+        if self.pos == 0:
+            raise SamRecordError(_lib.SAMREC_POS_ZERO)
+        rest = list(raw)  # next_ciglet_if_op / next_ciglet_back_if_op on the raw ciglets
+        if rest and rest[0][1] == ord("H"):
+            rest.pop(0)
+        front = rest.pop(0)[0] if rest and rest[0][1] == ord("S") else 0
+        if rest and rest[-1][1] == ord("H"):
+            rest.pop()
+        back = rest.pop()[0] if rest and rest[-1][1] == ord("S") else 0
+        query_len = len(self.seq)
+        if front + back > query_len:
+            raise SamRecordError(_lib.SAMREC_CLIPS_EXCEED_SEQ)
+        ref_start = self.pos - 1
+        ref_end = min(ref_start + self.ref_len_in_alignment(), _U64)
+        if any(inc > 0xFFFFFFFF for inc, _ in merged) or ref_end > 0xFFFFFFFF or query_len > 0xFFFFFFFF or len(merged) > 0xFFFFFFFF:
+            raise SamRecordError(_lib.SAMREC_TOO_LARGE)
+        return SamAlignment(score, ref_start, ref_end, front, front + (query_len - front - back), ref_len, query_len, [(i, o) for i, o in merged])
 
     def __str__(self) -> str:
         seq = self.seq.decode() if self.seq else "*"
@@ -175,6 +352,127 @@ def align_fastq_to_sam_text(records: List[FastQ], reference: bytes, rname: str, 
         aln = verbose if verbose_cigar else aln
         stats = stats if nm else None
     return profiles.to_sam_text(aln, qnames, [r.quality for r in records], rname, 255, stats=stats)
+
+
+class SAMReader:
+    """Iterator over the rows of SAM text (reader.rs:189-286): a `str` for a header line, a `SamData` for a data line, SamError where
+    the reference's iterator yields Err. Lines are BufRead::lines': a line ends at "\n", which is removed with one "\r" in front of it.
+    `line` counts the rows handed out so far and `offset` is the first byte of the next one."""
+
+    def __init__(self, inner: BinaryIO):
+        self._f = inner
+        self.line = 0
+        self.offset = 0
+
+    @staticmethod
+    def from_readable(inner: BinaryIO) -> "SAMReader":
+        buffered = inner if isinstance(inner, io.BufferedReader) else io.BufferedReader(inner)
+        if not buffered.peek(1):
+            raise SamError(0, "No SAM data was found!")
+        return SAMReader(buffered)
+
+    def __iter__(self):
+        return self
+
+    def __next__(self):
+        raw = self._f.readline()
+        if not raw:
+            raise StopIteration
+        at, index = self.offset, self.line
+        self.offset += len(raw)
+        self.line += 1
+        fail = lambda code, message: SamError(code, message, index, at)
+        try:
+            line = _chop_line_break(raw).decode("utf-8")
+        except UnicodeDecodeError as e:
+            raise fail(_lib.SAMTEXT_INVALID_UTF8, "stream did not contain valid UTF-8") from e
+        if line.startswith("@"):
+            return line
+        parts = line.split("\t")
+        if len(parts) < 11:
+            raise fail(_lib.SAMTEXT_TOO_FEW_FIELDS, "SAM file did not have at least 11 fields!")
+        try:
+            flag = _rust_parse_int(parts[1], 0, 0xFFFF)
+        except ValueError as e:
+            raise fail(_lib.SAMTEXT_INVALID_FLAG, f"Error: {e}, invalid SAM bit flag '{parts[1]}'") from e
+        try:
+            pos = _rust_parse_int(parts[3], 0, _U64)
+        except ValueError as e:
+            raise fail(_lib.SAMTEXT_INVALID_POS, f"Error: {e}, invalid SAM reference position '{parts[3]}'") from e
+        try:
+            mapq = _rust_parse_int(parts[4], 0, 0xFF)
+        except ValueError as e:
+            raise fail(_lib.SAMTEXT_INVALID_MAPQ, f"Error: {e}, invalid SAM mapq '{parts[4]}'") from e
+        cigar = parts[5].strip(" \t\n\x0c\r")  # trim_ascii
+        if cigar == "*":
+            cigar = ""
+        qual = b"" if parts[10] in ("", "*") else parts[10].encode("utf-8")
+        if any(c < 33 or c > 126 for c in qual):  # QualityScores: graphic ASCII
+            raise fail(_lib.SAMTEXT_INVALID_QUALITY, "Invalid quality score byte!")
+        return SamData(parts[0], flag, parts[2], pos, mapq, cigar, "*", 0, 0, parts[9].encode("utf-8"), qual, parts[11:])
+
+
+class SamDeviceBatch:
+    """What `sam_batch_from_text` returns: the data lines of SAM text as zsw_sam_parse_batch left them.
+
+    reads          the device-resident `ReadBatch` (SEQ back to back with offsets): the reads AS ALIGNED, which is what `annotate` and
+                   `pileup` of a profile batch over them walk
+    quals          CUDA uint8, laid out as the reads' bases (forward: QUAL back to front where FLAG & 16)
+    names          (CUDA uint8 names back to back, CUDA int64 n + 1 offsets): what `to_sam_text` takes as qnames
+    alignments     the `AlignmentBatch` (host arrays, as `annotate`, `pileup` and `to_sam_text` take them). Its `.strand` is None: the
+                   reads are oriented already, where the strand-aware alignment calls return alignments of reads still to be oriented
+    strand         numpy uint8 per record: FLAG & 16. `to_sam_text` of a profile batch over `original_reads()` with `strands=.strand`
+                   writes the lines back
+    parsed         numpy, alignment.PARSED_DTYPE: pos, line, flag, mapq, code, bits per record
+    report         the ZSW_SAMTEXT_INFO_* words; headers, consumed"""
+
+    def __init__(self, reads: ReadBatch, quals, names, alignments: AlignmentBatch, strand, parsed, report):
+        self.reads, self.quals, self.names, self.alignments, self.strand, self.parsed, self.report = reads, quals, names, alignments, strand, parsed, report
+        self.consumed = int(report[_lib.SAMTEXT_INFO_CONSUMED])
+        self.headers = int(report[_lib.SAMTEXT_INFO_HEADERS])
+
+    def __len__(self) -> int:
+        return self.reads.n_reads
+
+    def original_reads(self) -> ReadBatch:
+        """the reads as sequenced: those with FLAG & 16 reverse complemented back (zsw_orient_batch with the context's complement table)"""
+        import torch
+
+        from .alignment import SwContext
+
+        if self.reads.n_reads == 0:
+            return self.reads
+        return SwContext.get(self.reads.device_index).orient(self.reads, torch.from_numpy(self.strand.copy()).to(self.reads.bases.device))
+
+
+def sam_batch_from_text(text: bytes, rname=None, ref_len: int = 0, device: int = 0, final: bool = True, qual_forward: bool = True) -> SamDeviceBatch:
+    """Uploads SAM text once and parses it on the device (zsw_sam_parse_batch): the records, reads, qualities and names ready for
+    `annotate` / `pileup` / `to_sam_text` of a profile batch over `.reads`. rname: records of another RNAME are unmapped (the context
+    has one reference); ref_len: the `ref_len` of every record. A malformed line raises SamError with the message SAMReader gives."""
+    import numpy as np
+    import torch
+
+    from .alignment import ALN_DTYPE, PARSED_DTYPE, SwContext, _to_host
+
+    ctx = SwContext.get(device)
+    view = memoryview(text).cast("B")
+    n = len(view)
+    d_text = torch.frombuffer(bytearray(view) if n else bytearray(1), dtype=torch.uint8).to(torch.device("cuda", device))
+    t, report = ctx.parse_sam(d_text, n, final=final, qual_forward=qual_forward, rname=rname, ref_len=ref_len)
+    if report[_lib.SAMTEXT_INFO_ERROR]:
+        at, line = int(report[_lib.SAMTEXT_INFO_ERROR_OFFSET]), int(report[_lib.SAMTEXT_INFO_ERROR_LINE])
+        try:  # the reader's own message for that line
+            next(SAMReader(io.BytesIO(bytes(view[at:]))))
+        except SamError as e:
+            raise SamError(e.code, f"line {line}: {e}", line, at) from None
+        raise SamError(int(report[_lib.SAMTEXT_INFO_ERROR]), f"line {line} is malformed (code {int(report[_lib.SAMTEXT_INFO_ERROR])})", line, at)
+    n_rec = int(report[_lib.SAMTEXT_INFO_RECORDS])
+    aln, status, inc, op, strand, parsed = _to_host(t["aln"], t["status"], t["inc"], t["op"], t["strand"], t["parsed"])
+    batch = AlignmentBatch(status.copy(), aln.view(ALN_DTYPE).copy(), inc.view(np.uint32).copy(), op.copy())
+    reads = ReadBatch(t["bases"] if t["bases"].numel() else torch.zeros(1, dtype=torch.uint8, device=d_text.device), n_rec, offsets=t["offsets"],
+                      min_len=int(report[_lib.SAMTEXT_INFO_MIN_LEN]) if n_rec else None)
+    quals = t["quals"] if t["quals"].numel() else torch.zeros(1, dtype=torch.uint8, device=d_text.device)
+    return SamDeviceBatch(reads, quals, (t["qnames"], t["qname_offsets"]), batch, strand.copy(), parsed.view(PARSED_DTYPE).copy(), report)
 
 
 class FastQDeviceBatch:
