@@ -1,4 +1,4 @@
-// fastq_parse.cpp — host model of zsw_fastq_parse_batch: zoe_amd/csrc/zsw_fastq.hpp compiled for the host, the same text the
+// fastq_parse.cpp — host model of zsw_fastq_parse_batch: zoe_amd/csrc/zsw_fastq.hpp (and zsw_text.hpp beneath it) compiled for the host, the same text the
 // kernels compile, behind an Io that loops over the FQ_G lanes. The passes of zsw_fastq.hip in their order — newlines per tile, their
 // exclusive sum, positions by rank, the record pass, the lowest failing index, the offsets, the gather, the report — each array in a
 // heap block of its exact size, so that a host sanitizer sees every load and store that leaves one.

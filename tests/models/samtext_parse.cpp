@@ -1,4 +1,4 @@
-// samtext_parse.cpp — host model of zsw_sam_parse_batch: zoe_amd/csrc/zsw_samtext.hpp (and zsw_fastq.hpp beneath it) compiled for the
+// samtext_parse.cpp — host model of zsw_sam_parse_batch: zoe_amd/csrc/zsw_samtext.hpp (and zsw_text.hpp beneath it) compiled for the
 // host, the same text the kernels compile, behind an Io that loops over the FQ_G lanes. The passes of zsw_samtext.hip in their order
 // — the newline index, the line pass, the lowest failing index, the sums, the gather with the second CIGAR walk, the report — each
 // array in a heap block of its exact size, so that a host sanitizer sees every load and store that leaves one.

@@ -6,7 +6,8 @@ Every call gets output arrays of exactly the sizes the expectation has, between 
 pattern. Shapes are the smallest at which the kernels can go wrong: the case list in device and host memory under every flag set;
 texts of 0, 1, 15, 16, 17 bytes and one byte either side of a tile; the text at device addresses base + 1, 3, 15; one block of lines
 +- 1 and 3,000 mixed lines; a buffer cut at every byte of its last two lines without FINAL, and the chunked restart; a text with more
-newlines than the workspace estimate as the first call of a new context; the capacity protocol; NULL outputs; two runs; the argument
+newlines than the workspace estimate as the first call of a new context; FASTQ and SAM calls in turn on one context (they share the
+newline index's workspace); the capacity protocol; NULL outputs; two runs; the argument
 errors; a non-default stream; the identities against zsw_sam_batch, zsw_pileup_batch and zsw_annotate_batch; the Python layer."""
 import ctypes as C
 import os
@@ -273,6 +274,62 @@ def test_a_text_denser_than_the_workspace_estimate_on_a_new_context(env, text, d
         check(fresh, text[:len(text) // 2], sc.FINAL, device, shift=3 if device else 0, what="dense again")
     finally:
         env["lib"].zsw_destroy(fresh["h"])
+
+
+def fastq_call(env, text: bytes, device):
+    """zsw_fastq_parse_batch with exactly the capacities the expectation needs, checked as tests/test_gpu_fastq.py checks its
+    case list -> (the report, the arrays' bytes)"""
+    import fastq_cases as fc
+
+    recs, want_info, _ = fc.expect(text, fc.FINAL)
+    want = fc.arrays(recs)  # bases, qualities, offsets, names, name offsets
+    t = Text(text, device)
+    outs = [ah.Out(len(w), np.uint8 if isinstance(w, bytes) else np.uint64, device) for w in want]
+    info = (C.c_uint64 * 9)(*([PATTERN] * 9))
+    rc = env["lib"].zsw_fastq_parse_batch(env["h"], t.ptr, t.n, env["_lib"].MEM_DEVICE if device else env["_lib"].MEM_HOST, fc.FINAL, outs[0].ptr, outs[1].ptr,
+                                          len(want[0]), outs[2].ptr, outs[3].ptr, len(want[3]), outs[4].ptr, len(recs), info, None)
+    assert rc == 0, env["lib"].zsw_last_error_string(env["h"]).decode()
+    assert [int(x) for x in info] == want_info
+    assert all(o.guards_intact() for o in outs)
+    got = [o.data() for o in outs]
+    for g, w in zip(got, want):
+        assert (g.tobytes() == w) if isinstance(w, bytes) else np.array_equal(g, w)
+    return [int(x) for x in info], [g.tobytes() for g in got]
+
+
+def sam_call(env, text: bytes, device):
+    """check() -> (the report, the arrays' bytes)"""
+    e = sc.Expect(text, sc.FINAL)
+    i = e.info
+    p = Parse(env, Text(text, device), sc.FINAL, i[2], i[3], i[4], i[0])
+    assert p.call() == 0, p.msg()
+    assert p.report() == e.info, (dict(zip(sc.INFO, p.report())), dict(zip(sc.INFO, e.info)))
+    p.compare(e.arrays(), "shared index")
+    return p.report(), [o.data().tobytes() for o in p.outs()]
+
+
+@pytest.mark.parametrize("device", [True, False], ids=["device", "host"])
+def test_fastq_and_sam_calls_share_the_index_workspace_of_one_context(env, device):
+    """The two parse calls keep the staged text, the tile counts and the newline positions in one workspace of the context. A FASTQ
+    text of one tile and a byte, the dense SAM text (its second round grows the positions under the FASTQ call's sizes), the FASTQ
+    text again and a SAM text of one line, on one context: every call gives what it gives as the only call of a new context."""
+    import fastq_cases as fc
+
+    fastq = fc.mixed_file(60, 1, 400, seed=3)[:TILE + 1]
+    assert len(fastq) == TILE + 1 and DENSE[0].count(b"\n") > 2 * ((TILE + 1) // 16 + 64)  # more than the FASTQ call's positions and their slack
+    steps = [(fastq_call, fastq), (sam_call, DENSE[0]), (fastq_call, fastq), (sam_call, sc.good(0))]
+    new = lambda: dict(env, h=ah.new_context(env["_lib"], env["lib"], env["m"], GO, GE, None))
+    shared = new()
+    try:
+        for k, (call, text) in enumerate(steps):
+            got = call(shared, text, device)
+            fresh = new()
+            try:
+                assert got == call(fresh, text, device), k
+            finally:
+                env["lib"].zsw_destroy(fresh["h"])
+    finally:
+        env["lib"].zsw_destroy(shared["h"])
 
 
 # ---- NULL outputs, determinism, argument errors, streams ---------------------------------------------------------------------

@@ -5,7 +5,7 @@
 // One wavefront per alignment (ANN_G = 64 lanes), ANN_WAVES per block, blocks striding over the batch. Per sweep lane l loads byte l
 // of the read's and of the context sequence's window — consecutive lanes, consecutive bytes, as strand_orient_kernel —, a ballot
 // makes the match mask, and the =/X run boundaries, their places and their lengths are bit operations on that mask: every run of
-// a sweep is written by the lane it starts at. The record, its ciglets and the walk's cursors are wavefront-uniform. The context's
+// a sweep is written by the lane it starts at. The record, its ciglets and the walk's cursors are wavefront-uniform (uni(), zsw_wave.hpp). The context's
 // sequence, the index map and the weights are staged in LDS once per block (sequences beyond ANN_LDS_SEQ_MAX bytes: through L2);
 // a read's bases and ciglets pass through the wavefront's own LDS area, loaded together while the next read's record is in flight.
 //
@@ -16,10 +16,12 @@
 
 #include "zsw_annotate.hpp"
 #include "zsw_context.hpp"
+#include "zsw_wave.hpp"
 
 using namespace zsw;
 using namespace zsw::capi;
 using namespace zsw::ann;
+using namespace zsw::wave;
 
 static_assert(sizeof(zsw_alignment_stats) == 32 && sizeof(Stats) == 32, "zsw_alignment_stats is 32 bytes");
 static_assert(sizeof(zsw_alignment) == sizeof(Rec), "Rec mirrors zsw_alignment");
@@ -56,19 +58,6 @@ constexpr uint32_t ANN_BLOCK = 64 * ANN_WAVES;
 constexpr uint32_t ANN_READ_LDS = 512;  // bases of a read that go through the wavefront's LDS area (longer reads: from global memory)
 constexpr uint32_t WAVE_LDS = ANN_READ_LDS + 4 * ANN_G + ANN_G;  // ... and ANN_G ciglets: inc, op
 constexpr uint32_t LDS_FIXED = LDS_TABLES + ANN_WAVES * WAVE_LDS;
-
-// A value every lane of the wavefront holds, moved to a scalar register. The record, the ciglets and the offsets are loaded from
-// wavefront-uniform addresses, but by vector loads (the kernel writes memory, so the compiler cannot prove them invariant), and a
-// walk on vector registers pays a mask and a vector instruction for every scalar step and branch of its cursors.
-__device__ __forceinline__ uint32_t uni(uint32_t x) { return (uint32_t)__builtin_amdgcn_readfirstlane((int)x); }
-__device__ __forceinline__ uint64_t uni(uint64_t x) { return (uint64_t)uni((uint32_t)x) | ((uint64_t)uni((uint32_t)(x >> 32)) << 32); }
-
-// within a wavefront: what its lanes stored to LDS is there for every lane's loads behind this point
-__device__ __forceinline__ void wave_sync() {
-    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-    __builtin_amdgcn_wave_barrier();
-    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-}
 
 struct WaveIo {
     int lane;
@@ -266,12 +255,6 @@ hipError_t launch_annotate(const zsw_context* ctx, const AnnArgs& a, hipStream_t
 // the last entry of the counts (the exclusive sum needs n + 1 inputs for the total)
 __global__ void annotate_close_counts(uint64_t* counts, uint32_t n) { counts[n] = 0; }
 
-bool overlaps(const void* a, size_t na, const void* b, size_t nb) {
-    if (!a || !b || !na || !nb) return false;
-    const uintptr_t x = (uintptr_t)a, y = (uintptr_t)b;
-    return x < y + nb && y < x + na;
-}
-
 }  // namespace
 
 extern "C" zsw_error zsw_annotate_batch(zsw_context* ctx, const zsw_batch* reads, int flags, const zsw_alignment* aln, const uint8_t* status,
@@ -335,29 +318,8 @@ extern "C" zsw_error zsw_annotate_batch(zsw_context* ctx, const zsw_batch* reads
     a.stats = out_stats;
     if (host) {  // everything crosses once; the call returns when the results are back
         const size_t total = reads->offsets ? (size_t)reads->offsets[n] : (size_t)n * reads->fixed_len;
-        ZSW_HIP(ctx, ws[AN_BASES].ensure(total + 16));
-        ZSW_HIP(ctx, ws[AN_ALN].ensure(n * sizeof(zsw_alignment)));
-        ZSW_HIP(ctx, ws[AN_STATUS].ensure(n + 4));
-        ZSW_HIP(ctx, ws[AN_INC].ensure(n_ciglets * 4 + 4));
-        ZSW_HIP(ctx, ws[AN_OP].ensure(n_ciglets + 4));
+        if (zsw_error up = stage_up_records(ctx, ws + AN_BASES, reads->bases, total, &a, stream)) return up;
         ZSW_HIP(ctx, ws[AN_STATS].ensure(n * 32));
-        if (total) ZSW_HIP(ctx, hipMemcpyAsync(ws[AN_BASES].p, reads->bases, total, hipMemcpyHostToDevice, stream));
-        if (reads->offsets) {
-            ZSW_HIP(ctx, ws[AN_OFFSETS].ensure((n + 1) * 8));
-            ZSW_HIP(ctx, hipMemcpyAsync(ws[AN_OFFSETS].p, reads->offsets, (n + 1) * 8, hipMemcpyHostToDevice, stream));
-            a.offsets = ws[AN_OFFSETS].as<uint64_t>();
-        }
-        ZSW_HIP(ctx, hipMemcpyAsync(ws[AN_ALN].p, aln, n * sizeof(zsw_alignment), hipMemcpyHostToDevice, stream));
-        ZSW_HIP(ctx, hipMemcpyAsync(ws[AN_STATUS].p, status, n, hipMemcpyHostToDevice, stream));
-        if (n_ciglets) {
-            ZSW_HIP(ctx, hipMemcpyAsync(ws[AN_INC].p, inc, n_ciglets * 4, hipMemcpyHostToDevice, stream));
-            ZSW_HIP(ctx, hipMemcpyAsync(ws[AN_OP].p, op, n_ciglets, hipMemcpyHostToDevice, stream));
-        }
-        a.bases = ws[AN_BASES].as<uint8_t>();
-        a.aln = ws[AN_ALN].as<zsw_alignment>();
-        a.status = ws[AN_STATUS].as<uint8_t>();
-        a.inc = ws[AN_INC].as<uint32_t>();
-        a.op = ws[AN_OP].as<uint8_t>();
         a.stats = ws[AN_STATS].as<zsw_alignment_stats>();
     }
     if (out_aln) {
@@ -391,23 +353,15 @@ extern "C" zsw_error zsw_annotate_batch(zsw_context* ctx, const zsw_batch* reads
     a.out_aln = out_aln;
     a.out_inc = out_inc;
     a.out_op = out_op;
-    if (host) {
-        ZSW_HIP(ctx, ws[AN_OUT_ALN].ensure(n * sizeof(zsw_alignment)));
-        ZSW_HIP(ctx, ws[AN_OUT_INC].ensure(total * 4 + 4));
-        ZSW_HIP(ctx, ws[AN_OUT_OP].ensure(total + 4));
-        a.out_aln = ws[AN_OUT_ALN].as<zsw_alignment>();
-        a.out_inc = ws[AN_OUT_INC].as<uint32_t>();
-        a.out_op = ws[AN_OUT_OP].as<uint8_t>();
-    }
+    Down downs[3] = {{AN_OUT_ALN, n * sizeof(zsw_alignment), (void**)&a.out_aln}, {AN_OUT_INC, total * 4, (void**)&a.out_inc}, {AN_OUT_OP, total, (void**)&a.out_op}};
+    if (host)
+        if (zsw_error down = stage_down(ctx, ws, downs, 3)) return down;
     e = launch_annotate<true>(ctx, a, stream);
     if (e != hipSuccess) return fail(ctx, ZSW_ERR_HIP, "annotate write", e);
     if (host) {
         ZSW_HIP(ctx, hipMemcpyAsync(out_stats, a.stats, n * 32, hipMemcpyDeviceToHost, stream));
-        ZSW_HIP(ctx, hipMemcpyAsync(out_aln, a.out_aln, n * sizeof(zsw_alignment), hipMemcpyDeviceToHost, stream));
-        if (total) {
-            ZSW_HIP(ctx, hipMemcpyAsync(out_inc, a.out_inc, total * 4, hipMemcpyDeviceToHost, stream));
-            ZSW_HIP(ctx, hipMemcpyAsync(out_op, a.out_op, total, hipMemcpyDeviceToHost, stream));
-        }
+        const size_t used[3] = {n * sizeof(zsw_alignment), total * 4, total};
+        if (zsw_error down = copy_down(ctx, downs, used, 3, stream)) return down;
         ZSW_HIP(ctx, hipStreamSynchronize(stream));
     }
     return ZSW_OK;

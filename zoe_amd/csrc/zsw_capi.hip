@@ -1147,6 +1147,7 @@ void zsw_destroy(zsw_context* ctx) {
     for (DevBuf& b : ctx->an_ws) b.release();
     for (DevBuf& b : ctx->sam_ws) b.release();
     for (DevBuf& b : ctx->pu_ws) b.release();
+    for (DevBuf& b : ctx->text_ws) b.release();
     for (DevBuf& b : ctx->fq_ws) b.release();
     for (DevBuf& b : ctx->samtext_ws) b.release();
     seed_index_release(&ctx->seed);

@@ -1,5 +1,6 @@
 // zsw_context.hpp — the context behind the C ABI and the helpers its translation units share (zsw_capi.hip: the entry points
-// with the read as the profile; zsw_capi_shared.hip: the one-profile-many-sequences role). Not installed.
+// with the read as the profile; zsw_capi_shared.hip: the one-profile-many-sequences role; the staging tables of a host call's
+// arrays and the overlap checks of the record and text calls). Not installed.
 #pragma once
 #include <stdio.h>
 #include <string.h>
@@ -119,12 +120,15 @@ struct zsw_context {
     // zsw_pileup_batch / zsw_consensus_from_counts (zsw_pileup.hip): the accumulators (16 bytes per site), the scan's scratch, the
     // counter of malformed records, the staged arrays and tables of a host call
     zsw::DevBuf pu_ws[16];
-    // zsw_fastq_parse_batch (zsw_fastq.hip): the tile counts and their sum, 8 bytes per newline, the per-record arrays and their
-    // sums, the scans' scratch, the state block with the report, the staged text and outputs of a host call
-    zsw::DevBuf fq_ws[16];
-    // zsw_sam_parse_batch (zsw_samtext.hip): the newline index as above, 120 bytes and six sums per line, the scans' scratch, the state
-    // block with the report, RNAME, the staged text and outputs of a host call
-    zsw::DevBuf samtext_ws[28];
+    // the newline index of the two parse calls (zsw_text.hip): the staged text of a host call, the tile counts and their sum, 8 bytes
+    // per newline. One set for both calls: the context keeps the larger workspace
+    zsw::DevBuf text_ws[4];
+    // zsw_fastq_parse_batch (zsw_fastq.hip): the per-record arrays and their sums, the scans' scratch, the state block with the
+    // report, the staged outputs of a host call
+    zsw::DevBuf fq_ws[12];
+    // zsw_sam_parse_batch (zsw_samtext.hip): 120 bytes and six sums per line, the scans' scratch, the state block with the report,
+    // RNAME, the staged outputs of a host call
+    zsw::DevBuf samtext_ws[24];
 };
 
 namespace zsw {
@@ -167,6 +171,75 @@ struct DeviceGuard {
         hipError_t _e = (call);                                                \
         if (_e != hipSuccess) return fail(ctx, ZSW_ERR_HIP, #call, _e);        \
     } while (0)
+
+// ---- host calls: staging by table -------------------------------------------------------------------------------------------
+// An input array of a host call: `bytes` at `src` go to ws[slot], and *dev points there. An absent array (src == nullptr) stays
+// absent; an array of zero bytes gets its place and no copy.
+struct Up {
+    int slot;
+    const void* src;
+    size_t bytes;
+    const void** dev;
+};
+inline zsw_error stage_up(zsw_context* ctx, DevBuf* ws, const Up* ups, int n, hipStream_t stream) {
+    for (const Up* u = ups; u < ups + n; ++u) {
+        if (!u->src) continue;
+        ZSW_HIP(ctx, ws[u->slot].ensure(u->bytes + 16));
+        if (u->bytes) ZSW_HIP(ctx, hipMemcpyAsync(ws[u->slot].p, u->src, u->bytes, hipMemcpyHostToDevice, stream));
+        *u->dev = ws[u->slot].p;
+    }
+    return ZSW_OK;
+}
+// The six arrays every alignment call returns, as the kernels' arguments hold them (a->bases, offsets, aln, status, inc, op; a->n,
+// a->n_ciglets), to ws[0 .. 5]. bases: null = not wanted on the device.
+template <class Args>
+zsw_error stage_up_records(zsw_context* ctx, DevBuf* ws, const uint8_t* bases, size_t base_bytes, Args* a, hipStream_t stream) {
+    const size_t n = a->n;
+    const Up ups[6] = {{0, bases, base_bytes, (const void**)&a->bases},           {1, a->offsets, (n + 1) * 8, (const void**)&a->offsets},
+                       {2, a->aln, n * sizeof(zsw_alignment), (const void**)&a->aln}, {3, a->status, n, (const void**)&a->status},
+                       {4, a->inc, (size_t)a->n_ciglets * 4, (const void**)&a->inc},  {5, a->op, (size_t)a->n_ciglets, (const void**)&a->op}};
+    return stage_up(ctx, ws, ups, 6, stream);
+}
+// An output array of a host call: before the launches *dev (the caller's array; absent stays absent) is redirected to ws[slot] with
+// room for `bytes`; after them copy_down() copies what was used to the caller's array (nothing for zero bytes).
+struct Down {
+    int slot;
+    size_t bytes;
+    void** dev;
+    void* dst;  // set by stage_down
+};
+inline zsw_error stage_down(zsw_context* ctx, DevBuf* ws, Down* downs, int n) {
+    for (Down* d = downs; d < downs + n; ++d) {
+        d->dst = *d->dev;
+        if (!d->dst) continue;
+        ZSW_HIP(ctx, ws[d->slot].ensure(d->bytes + 16));
+        *d->dev = ws[d->slot].p;
+    }
+    return ZSW_OK;
+}
+inline zsw_error copy_down(zsw_context* ctx, const Down* downs, const size_t* used, int n, hipStream_t stream) {
+    for (int k = 0; k < n; ++k)
+        if (downs[k].dst && used[k]) ZSW_HIP(ctx, hipMemcpyAsync(downs[k].dst, *downs[k].dev, used[k], hipMemcpyDeviceToHost, stream));
+    return ZSW_OK;
+}
+
+// do [a, a + na) and [b, b + nb) share a byte? An absent or empty array overlaps nothing
+inline bool overlaps(const void* a, uint64_t na, const void* b, uint64_t nb) {
+    if (!a || !b || !na || !nb) return false;
+    const uintptr_t x = (uintptr_t)a, y = (uintptr_t)b;
+    return x < y + nb && y < x + na;
+}
+struct Span {
+    const void* p;
+    uint64_t bytes;
+};
+// the lowest i for which s[i] overlaps a later span; -1: none does
+inline int first_overlap(const Span* s, int n) {
+    for (int i = 0; i < n; ++i)
+        for (int k = i + 1; k < n; ++k)
+            if (overlaps(s[i].p, s[i].bytes, s[k].p, s[k].bytes)) return i;
+    return -1;
+}
 
 inline bool valid_lanes(int lanes) { return lanes == 2 || lanes == 4 || lanes == 8 || lanes == 16 || lanes == 32 || lanes == 64; }
 

@@ -19,10 +19,12 @@
 
 #include "zsw_context.hpp"
 #include "zsw_pileup.hpp"
+#include "zsw_wave.hpp"
 
 using namespace zsw;
 using namespace zsw::capi;
 using namespace zsw::pile;
+using namespace zsw::wave;
 
 static_assert(sizeof(zsw_site_counts) == 32 && sizeof(zsw_site_insertions) == 8, "the tables' entries");
 static_assert(sizeof(zsw_alignment) == sizeof(Rec), "Rec mirrors zsw_alignment");
@@ -55,9 +57,6 @@ struct PileArgs {
 
 constexpr uint32_t PILEUP_BLOCK = 64 * PILEUP_WAVES;
 constexpr uint32_t LDS_TABLE = 256;  // bin_of() of every byte
-
-__device__ __forceinline__ uint32_t uni(uint32_t x) { return (uint32_t)__builtin_amdgcn_readfirstlane((int)x); }
-__device__ __forceinline__ uint64_t uni(uint64_t x) { return (uint64_t)uni((uint32_t)x) | ((uint64_t)uni((uint32_t)(x >> 32)) << 32); }
 
 // LDS_ACC: acc and seq_bins point into the block's LDS; else acc is the global workspace and the sequence's bytes are read through L2
 template <bool LDS_ACC>
@@ -214,12 +213,6 @@ hipError_t launch_pileup(const zsw_context* ctx, const PileArgs& a, hipStream_t 
     return hipGetLastError();
 }
 
-bool overlaps(const void* a, size_t na, const void* b, size_t nb) {
-    if (!a || !b || !na || !nb) return false;
-    const uintptr_t x = (uintptr_t)a, y = (uintptr_t)b;
-    return x < y + nb && y < x + na;
-}
-
 }  // namespace
 
 extern "C" zsw_error zsw_pileup_batch(zsw_context* ctx, const zsw_batch* reads, int flags, const zsw_alignment* aln, const uint8_t* status,
@@ -301,34 +294,13 @@ extern "C" zsw_error zsw_pileup_batch(zsw_context* ctx, const zsw_batch* reads, 
     ZSW_HIP(ctx, hipMemsetAsync(a.n_bad, 0, 8, stream));
     if (host) {  // everything crosses once, the tables both ways; the call returns when they are back
         const size_t total = reads->offsets ? (size_t)reads->offsets[n] : (size_t)n * reads->fixed_len;
-        ZSW_HIP(ctx, ws[PU_BASES].ensure(total + 16));
-        ZSW_HIP(ctx, ws[PU_ALN].ensure(n * sizeof(zsw_alignment)));
-        ZSW_HIP(ctx, ws[PU_STATUS].ensure(n + 4));
-        ZSW_HIP(ctx, ws[PU_INC].ensure(n_ciglets * 4 + 4));
-        ZSW_HIP(ctx, ws[PU_OP].ensure(n_ciglets + 4));
+        if (zsw_error up = stage_up_records(ctx, ws + PU_BASES, reads->bases, total, &a, stream)) return up;
         ZSW_HIP(ctx, ws[PU_COUNTS].ensure(counts_bytes + 32));
         if (ins) ZSW_HIP(ctx, ws[PU_INS].ensure(ins_bytes));
-        if (total) ZSW_HIP(ctx, hipMemcpyAsync(ws[PU_BASES].p, reads->bases, total, hipMemcpyHostToDevice, stream));
-        if (reads->offsets) {
-            ZSW_HIP(ctx, ws[PU_OFFSETS].ensure((n + 1) * 8));
-            ZSW_HIP(ctx, hipMemcpyAsync(ws[PU_OFFSETS].p, reads->offsets, (n + 1) * 8, hipMemcpyHostToDevice, stream));
-            a.offsets = ws[PU_OFFSETS].as<uint64_t>();
-        }
-        ZSW_HIP(ctx, hipMemcpyAsync(ws[PU_ALN].p, aln, n * sizeof(zsw_alignment), hipMemcpyHostToDevice, stream));
-        ZSW_HIP(ctx, hipMemcpyAsync(ws[PU_STATUS].p, status, n, hipMemcpyHostToDevice, stream));
-        if (n_ciglets) {
-            ZSW_HIP(ctx, hipMemcpyAsync(ws[PU_INC].p, inc, n_ciglets * 4, hipMemcpyHostToDevice, stream));
-            ZSW_HIP(ctx, hipMemcpyAsync(ws[PU_OP].p, op, n_ciglets, hipMemcpyHostToDevice, stream));
-        }
         if (!clear) {
             if (counts_bytes) ZSW_HIP(ctx, hipMemcpyAsync(ws[PU_COUNTS].p, counts, counts_bytes, hipMemcpyHostToDevice, stream));
             if (ins) ZSW_HIP(ctx, hipMemcpyAsync(ws[PU_INS].p, ins, ins_bytes, hipMemcpyHostToDevice, stream));
         }
-        a.bases = ws[PU_BASES].as<uint8_t>();
-        a.aln = ws[PU_ALN].as<zsw_alignment>();
-        a.status = ws[PU_STATUS].as<uint8_t>();
-        a.inc = ws[PU_INC].as<uint32_t>();
-        a.op = ws[PU_OP].as<uint8_t>();
         a.counts = ws[PU_COUNTS].as<uint32_t>();
         if (ins) a.ins = ws[PU_INS].as<uint32_t>();
     }

@@ -7,7 +7,7 @@
 // run (the one atomic counts the malformed records).
 //
 // One wavefront per line (SAM_G = 64 lanes), SAM_BLOCK_LINES per block, blocks striding over the batch; the record, the offsets
-// and the line's start are wavefront-uniform and held in scalar registers (uni(), as zsw_annotate.hip); the next line's record is
+// and the line's start are wavefront-uniform and held in scalar registers (uni(), zsw_wave.hpp); the next line's record is
 // loaded before this one is written. A line of up to SAM_LDS_LINE bytes is assembled in the wavefront's own LDS area, shifted by
 // the low four bits of its address in the text, so that a 16-byte granule of the area is a 16-byte granule of the text. The flush
 // writes a granule that lies wholly inside the line as one 16-byte store; the granule a line shares with its neighbour, and the
@@ -21,10 +21,12 @@
 
 #include "zsw_context.hpp"
 #include "zsw_sam.hpp"
+#include "zsw_wave.hpp"
 
 using namespace zsw;
 using namespace zsw::capi;
 using namespace zsw::sam;
+using namespace zsw::wave;
 
 static_assert(sizeof(zsw_alignment) == sizeof(Rec), "Rec mirrors zsw_alignment");
 static_assert(sizeof(zsw_alignment_stats) == 32, "zsw_alignment_stats is 32 bytes");
@@ -64,19 +66,6 @@ constexpr uint32_t SAM_BLOCK = SAM_G * SAM_BLOCK_LINES;
 constexpr uint32_t WAVE_LDS = SAM_LDS_LINE + 16;  // the line shifted by up to 15 bytes
 static_assert(WAVE_LDS % 16 == 0, "the wavefronts' LDS areas are 16-byte granules");
 
-typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
-typedef u32x4 __attribute__((may_alias)) u32x4_alias;
-
-// see zsw_annotate.hip: wavefront-uniform values loaded by vector loads, moved to scalar registers
-__device__ __forceinline__ uint32_t uni(uint32_t x) { return (uint32_t)__builtin_amdgcn_readfirstlane((int)x); }
-__device__ __forceinline__ uint64_t uni(uint64_t x) { return (uint64_t)uni((uint32_t)x) | ((uint64_t)uni((uint32_t)(x >> 32)) << 32); }
-
-__device__ __forceinline__ void wave_sync() {
-    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-    __builtin_amdgcn_wave_barrier();
-    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-}
-
 // The wavefront behind the walk. tgt: byte 0 of the line, in the wavefront's LDS area or in the text; len: the bytes the scan gave
 // the line — no store at or beyond it.
 struct WaveIo {
@@ -114,12 +103,7 @@ struct WaveIo {
             ch = ok ? ciglet_chars(i) : 0u;
         }
         if (__ballot(!ok)) *bad = true;
-        uint32_t x = ch;  // inclusive prefix sum across the lanes
-#pragma unroll
-        for (int d = 1; d < SAM_G; d <<= 1) {
-            const uint32_t y = __shfl_up(x, d, SAM_G);
-            if (lane >= d) x += y;
-        }
+        const uint32_t x = lane_prefix_sum(ch, lane);
         if (WRITE && lane < nv && ok) put_ciglet(*this, pos + (x - ch), i, o);
         return uni((uint32_t)__shfl(x, SAM_G - 1, SAM_G));
     }
@@ -232,12 +216,6 @@ hipError_t launch_sam(const zsw_context* ctx, const SamArgs& a, hipStream_t stre
 
 __global__ void sam_empty_starts(uint64_t* starts) { starts[0] = 0; }
 
-bool overlaps(const void* a, size_t na, const void* b, size_t nb) {
-    if (!a || !b || !na || !nb) return false;
-    const uintptr_t x = (uintptr_t)a, y = (uintptr_t)b;
-    return x < y + nb && y < x + na;
-}
-
 }  // namespace
 
 extern "C" zsw_error zsw_sam_batch(zsw_context* ctx, const zsw_batch* reads, const void* fields_, int flags, const zsw_alignment* aln, const uint8_t* status,
@@ -331,31 +309,16 @@ extern "C" zsw_error zsw_sam_batch(zsw_context* ctx, const zsw_batch* reads, con
     a.kind = ws[SM_KIND].as<uint8_t>();
     a.n_bad = ws[SM_BAD].as<unsigned long long>();
     if (host) {  // everything crosses once; the call returns when the text is back
-        struct Up {
-            int slot;
-            const void* src;
-            size_t bytes;
-            const void** dev;
-        };
+        // the bases are not read under ZSW_SAM_OMIT_SEQ
+        if (zsw_error up = stage_up_records(ctx, ws + SM_BASES, omit_seq ? nullptr : reads->bases, base_bytes, &a, stream)) return up;
         const Up ups[] = {
-            {SM_BASES, omit_seq ? nullptr : reads->bases, base_bytes, (const void**)&a.bases},  // not read under ZSW_SAM_OMIT_SEQ
-            {SM_OFFSETS, reads->offsets, (n + 1) * 8, (const void**)&a.offsets},
-            {SM_ALN, aln, n * sizeof(zsw_alignment), (const void**)&a.aln},
-            {SM_STATUS, status, n, (const void**)&a.status},
-            {SM_INC, inc, n_ciglets * 4, (const void**)&a.inc},
-            {SM_OP, op, n_ciglets, (const void**)&a.op},
             {SM_QNAMES, f->qnames, name_bytes, (const void**)&a.qnames},
             {SM_QOFF, f->qnames ? f->qname_offsets : nullptr, (n + 1) * 8, (const void**)&a.qoff},
             {SM_QUALS, f->quals, base_bytes, (const void**)&a.quals},
             {SM_STRAND, f->strand, n, (const void**)&a.strand},
             {SM_STATS, f->stats, n * 32, (const void**)&a.stats},
         };
-        for (const Up& u : ups) {
-            if (!u.src) continue;  // an absent array stays absent
-            ZSW_HIP(ctx, ws[u.slot].ensure(u.bytes + 16));
-            if (u.bytes) ZSW_HIP(ctx, hipMemcpyAsync(ws[u.slot].p, u.src, u.bytes, hipMemcpyHostToDevice, stream));
-            *u.dev = ws[u.slot].p;
-        }
+        if (zsw_error up = stage_up(ctx, ws, ups, 5, stream)) return up;
     }
     hipError_t e = launch_sam<false>(ctx, a, stream);
     if (e != hipSuccess) return fail(ctx, ZSW_ERR_HIP, "sam length", e);

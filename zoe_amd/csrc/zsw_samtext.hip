@@ -1,11 +1,12 @@
 // zsw_samtext.hip — zsw_sam_parse_batch (include/zoe_sw.h): SAM text in device memory to the arrays zsw_annotate_batch,
 // zsw_sam_batch and zsw_pileup_batch take — records with status and ciglets, and the reads as bases / quals / names with offsets.
-// The rules are zsw_samtext.hpp (shared with tests/models/samtext_parse.cpp); the newline index and the wavefront behind the Io are
-// zsw_fastq.hip's, included below; this file adds the members of the Io the SAM rules need, the launches and the entry point.
+// The rules are zsw_samtext.hpp (shared with tests/models/samtext_parse.cpp); the newline index is zsw_text.hip; the state block, the
+// init and plan kernels, the sums and the rounds are zsw_text_dev.hpp. This file is the lines: the wavefront behind the header's Io
+// with the members the SAM rules need, their launches and the entry point.
 //
 // Launches, all on the caller's stream, with no host step between them:
 //   init      the state block (lowest failing line, min / max length)
-//   index     zsw_fastq.hip: newlines per tile, their exclusive sum, the position of every newline at its rank
+//   index     zsw_text.hip: newlines per tile, their exclusive sum, the position of every newline at its rank
 //   lines     one wavefront per line, the line's first SAM_WINDOW bytes staged in LDS: parse_line -> the line's record
 //             (zsw_samtext.hpp, Line); an atomicMin of the lowest failing index
 //   plan      one thread: delivered lines = min(lines, lowest failing index)
@@ -15,10 +16,12 @@
 //   report    one thread: the words of out_info
 // then one copy of the report and one synchronisation. A minimum and a min / max are the only atomics. The workspace for the newline
 // positions is sized for a line per 64 bytes; a denser text repeats the launches from the positions on, as in zsw_fastq.hip.
-#define ZSW_FASTQ_INDEX_ONLY
-#include "zsw_fastq.hip"
+#include "zsw_text_dev.hpp"
+
 #include "zsw_samtext.hpp"
 
+using namespace zsw;
+using namespace zsw::capi;
 using namespace zsw::samtext;
 
 static_assert(ZSW_SAMTEXT_FINAL == SF_FINAL && ZSW_SAMTEXT_QUAL_FORWARD == SF_QUAL_FORWARD, "zsw_samtext.hpp mirrors the header's flags");
@@ -32,15 +35,15 @@ static_assert((uint32_t)ZSW_STATUS_SOME == ST_SOME && (uint32_t)ZSW_STATUS_UNMAP
 
 namespace {
 
-enum { SW_TEXT = 0, SW_TILE_COUNTS, SW_TILE_BASE, SW_POS, SW_LINES, SW_REC_OFF, SW_SEQ_OFF, SW_NAME_OFF, SW_CIG_OFF, SW_MAP_OFF, SW_CODE_OFF, SW_SCAN_TMP, SW_STATE,
+enum { SW_LINES = 0, SW_REC_OFF, SW_SEQ_OFF, SW_NAME_OFF, SW_CIG_OFF, SW_MAP_OFF, SW_CODE_OFF, SW_SCAN_TMP, SW_STATE,
        SW_RNAME, SW_BASES, SW_QUALS, SW_OFFSETS, SW_QNAMES, SW_QOFF, SW_ALN, SW_STATUS, SW_INC, SW_OP, SW_STRAND, SW_PARSED, SW_N };
 
-enum { SS_FIRST_BAD = 0, SS_MIN, SS_MAX, SS_DELIVERED, SS_NEWLINES, SS_OVERFLOW, SS_WRITTEN, SS_INFO, SS_WORDS = SS_INFO + SI_WORDS };
+constexpr int ST_WORDS = ST_INFO + SI_WORDS;
 
 enum { SUM_RECORDS = 0, SUM_BASES, SUM_NAMES, SUM_CIGLETS, SUM_MAPPED, SUM_CODED, SUM_N };
 
 struct SamArgs {
-    FqArgs ix;                // the newline index: text, n_bytes, head, tiles, pos, pos_cap
+    IndexArgs ix;             // the newline index: text, n_bytes, head, tiles, pos, pos_cap
     int flags;
     uint32_t rname_len, ref_len;
     const uint8_t* rname;     // device copy of the caller's RNAME, rname_len bytes
@@ -65,7 +68,8 @@ typedef __attribute__((address_space(3))) uint8_t lds_u8;
 // The wavefront behind the walk of zsw_samtext.hpp. The walk reads most bytes of a line one at a time, each load waiting for the
 // one before it; stage() copies the head of the line into the wavefront's LDS window with consecutive lanes on consecutive bytes,
 // and byte() answers from there. Bytes outside the window (a line longer than SAM_WINDOW, or no window at all) come from the text.
-struct SamIo {
+// newline(), sweep_utf8, sweep_quality and the first match by ballot are WaveSweeps' (zsw_text_dev.hpp), over this byte().
+struct SamIo : WaveSweeps<SamIo> {
     int lane;
     const uint8_t* text;
     const uint64_t* pos_in;
@@ -90,28 +94,10 @@ struct SamIo {
         win_lo = lo;
         win_n = n;
     }
-    __device__ __forceinline__ uint64_t newline(uint64_t rank) const { return uni(pos_in[rank]); }
-    __device__ __forceinline__ bool sweep_utf8(uint64_t lo, uint64_t n) const {
-        bool bad = false;
-        for (uint64_t j = (uint32_t)lane; j < n; j += FQ_G) bad |= utf8_bad_at(*this, lo, n, j);
-        return __ballot(bad) != 0;
-    }
-    __device__ __forceinline__ bool sweep_quality(uint64_t lo, uint64_t n) const {
-        bool bad = false;
-        for (uint64_t j = (uint32_t)lane; j < n; j += FQ_G) bad |= !quality_ok(byte(lo + j));
-        return __ballot(bad) != 0;
-    }
     __device__ __forceinline__ unsigned long long mask_byte(uint64_t lo, uint64_t n, uint8_t c) const {
         return __ballot((uint64_t)(uint32_t)lane < n && byte(lo + (uint32_t)lane) == c);
     }
-    __device__ __forceinline__ uint64_t sweep_byte(uint64_t lo, uint64_t n, uint8_t c) const {
-        for (uint64_t j0 = 0; j0 < n; j0 += FQ_G) {
-            const uint64_t j = j0 + (uint32_t)lane;
-            const unsigned long long m = __ballot(j < n && byte(lo + j) == c);
-            if (m) return j0 + (uint64_t)__builtin_ctzll(m);
-        }
-        return n;
-    }
+    __device__ __forceinline__ uint64_t sweep_byte(uint64_t lo, uint64_t n, uint8_t c) const { return sweep_first(lo, n, [c](uint8_t b) { return b == c; }); }
     __device__ __forceinline__ bool sweep_differs(uint64_t lo, uint64_t n) const {
         bool bad = false;
         for (uint64_t j = (uint32_t)lane; j < n; j += FQ_G) bad |= byte(lo + j) != rname[j];
@@ -143,22 +129,7 @@ __device__ __forceinline__ SamIo sam_io(const SamArgs& a, int lane, uint8_t* win
     return io;
 }
 
-__global__ void st_init_kernel(unsigned long long* state) {
-    for (int k = 0; k < SS_WORDS; ++k) state[k] = 0;
-    state[SS_FIRST_BAD] = ~0ull;
-    state[SS_MIN] = ~0ull;
-}
-
-// how many newlines, how many lines; false: the positions did not fit, nothing is done
-__device__ __forceinline__ bool st_text(const SamArgs& a, Text* t, uint64_t* lines) {
-    t->n_bytes = a.ix.n_bytes;
-    t->n_newlines = a.ix.n_tiles ? uni(a.ix.tile_base[a.ix.n_tiles]) : 0;
-    t->flags = a.flags;
-    if (t->n_newlines > a.ix.pos_cap) return false;
-    const bool last_nl = a.ix.n_bytes ? uni((uint32_t)a.ix.text[a.ix.n_bytes - 1]) == '\n' : true;
-    *lines = n_lines(*t, last_nl);
-    return *lines <= a.line_items;  // holds by the sizes the entry point gives the arrays
-}
+__device__ __forceinline__ bool st_text(const SamArgs& a, Text* t, uint64_t* lines) { return text_of<n_lines>(a.ix, a.flags, a.line_items, t, lines); }
 
 // Four waves per SIMD: the pass is bound by the latency of its dependent loads (15.6 ms at two waves, 10.6 ms at four, 2 M lines;
 // DESIGN.md 4.11), and 128 registers cost 96 bytes of spills per lane.
@@ -176,20 +147,7 @@ __global__ __launch_bounds__(LINE_BLOCK) __attribute__((amdgpu_waves_per_eu(4, 4
         if (lane == 0) a.lines[L] = R;
         if (R.code && L < first_bad) first_bad = L;
     }
-    if (lane == 0 && first_bad != ~0ull) atomicMin(&a.state[SS_FIRST_BAD], (unsigned long long)first_bad);
-}
-
-__global__ void st_plan_kernel(SamArgs a) {
-    Text t;
-    uint64_t lines;
-    a.state[SS_NEWLINES] = a.ix.n_tiles ? a.ix.tile_base[a.ix.n_tiles] : 0;
-    if (!st_text(a, &t, &lines)) {
-        a.state[SS_OVERFLOW] = 1;
-        a.state[SS_DELIVERED] = 0;
-        return;
-    }
-    const uint64_t fb = a.state[SS_FIRST_BAD];
-    a.state[SS_DELIVERED] = fb < lines ? fb : lines;
+    if (lane == 0 && first_bad != ~0ull) atomicMin(&a.state[ST_FIRST_BAD], (unsigned long long)first_bad);
 }
 
 // what a delivered line adds to sum `which`, 0 behind the delivered lines and for header lines
@@ -211,7 +169,6 @@ struct LineTerm {
         }
     }
 };
-typedef hipcub::TransformInputIterator<uint64_t, LineTerm, hipcub::CountingInputIterator<uint64_t>> TermIter;
 
 struct WriteSink {
     uint32_t* inc;
@@ -228,11 +185,11 @@ struct WriteSink {
 
 __global__ __launch_bounds__(LINE_BLOCK) void st_gather_kernel(SamArgs a) {
     const int lane = threadIdx.x & 63;
-    if (a.state[SS_OVERFLOW]) return;
+    if (a.state[ST_OVERFLOW]) return;
     Text t;
     uint64_t lines;
     if (!st_text(a, &t, &lines)) return;
-    const uint64_t d = uni((uint64_t)a.state[SS_DELIVERED]);
+    const uint64_t d = uni((uint64_t)a.state[ST_DELIVERED]);
     const uint64_t records = uni(a.sum[SUM_RECORDS][d]), bases = uni(a.sum[SUM_BASES][d]), names = uni(a.sum[SUM_NAMES][d]), ciglets = uni(a.sum[SUM_CIGLETS][d]);
     const bool want_names = a.out_qnames != nullptr;
     const bool write = a.write && records <= a.record_cap && bases <= a.base_cap && (!want_names || names <= a.name_cap) && ciglets <= a.ciglet_cap;
@@ -241,7 +198,7 @@ __global__ __launch_bounds__(LINE_BLOCK) void st_gather_kernel(SamArgs a) {
     if (write && blockIdx.x == 0 && wave == 0 && lane == 0) {
         a.out_offsets[records] = bases;
         if (want_names) a.out_qname_offsets[records] = names;
-        a.state[SS_WRITTEN] = 1;
+        a.state[ST_WRITTEN] = 1;
     }
     const uint64_t stride = (uint64_t)gridDim.x * SAM_BLOCK_LINES;
     uint64_t lo = ~0ull, hi = 0;
@@ -306,18 +263,18 @@ __global__ __launch_bounds__(LINE_BLOCK) void st_gather_kernel(SamArgs a) {
         }
     }
     if (lane == 0 && any) {
-        atomicMin(&a.state[SS_MIN], (unsigned long long)lo);
-        atomicMax(&a.state[SS_MAX], (unsigned long long)hi);
+        atomicMin(&a.state[ST_MIN], (unsigned long long)lo);
+        atomicMax(&a.state[ST_MAX], (unsigned long long)hi);
     }
 }
 
 __global__ void st_report_kernel(SamArgs a) {
-    unsigned long long* info = a.state + SS_INFO;
+    unsigned long long* info = a.state + ST_INFO;
     Text t;
     uint64_t lines;
-    if (a.state[SS_OVERFLOW] || !st_text(a, &t, &lines)) return;
+    if (a.state[ST_OVERFLOW] || !st_text(a, &t, &lines)) return;
     SamIo io = sam_io(a, 0);
-    const uint64_t d = a.state[SS_DELIVERED];
+    const uint64_t d = a.state[ST_DELIVERED];
     const uint64_t records = a.sum[SUM_RECORDS][d];
     info[SI_RECORDS] = records;
     info[SI_HEADERS] = d - records;
@@ -332,8 +289,8 @@ __global__ void st_report_kernel(SamArgs a) {
     }
     info[SI_MAPPED] = a.sum[SUM_MAPPED][d];
     info[SI_CODED] = a.sum[SUM_CODED][d];
-    info[SI_MIN_LEN] = records ? a.state[SS_MIN] : 0;
-    info[SI_MAX_LEN] = a.state[SS_MAX];
+    info[SI_MIN_LEN] = records ? a.state[ST_MIN] : 0;
+    info[SI_MAX_LEN] = a.state[ST_MAX];
 }
 
 }  // namespace
@@ -357,23 +314,16 @@ extern "C" zsw_error zsw_sam_parse_batch(zsw_context* ctx, const uint8_t* text, 
     if (o.record_cap >= (1ull << 56) || o.ciglet_cap >= (1ull << 60)) return fail(ctx, ZSW_ERR_INVALID_ARGUMENT, "record_cap / ciglet_cap");
     const bool want_names = o.qnames != nullptr;
     const uint64_t name_cap = want_names ? o.name_cap : 0;
-    {
-        const void* p[12] = {text, o.bases, o.quals, o.offsets, o.qnames, o.qname_offsets, o.aln, o.status, o.inc, o.op, o.strand, o.parsed};
-        const uint64_t b[12] = {n_bytes, o.base_cap, o.base_cap, (o.record_cap + 1) * 8, name_cap, (o.record_cap + 1) * 8, o.record_cap * sizeof(zsw_alignment), o.record_cap,
-                                o.ciglet_cap * 4, o.ciglet_cap, o.record_cap, o.record_cap * sizeof(zsw_sam_parsed)};
-        for (int i = 0; i < 12; ++i)
-            for (int k = i + 1; k < 12; ++k)
-                if (overlaps(p[i], b[i], p[k], b[k])) return fail(ctx, ZSW_ERR_INVALID_ARGUMENT, i ? "output arrays overlap" : "an output array overlaps the text");
-    }
+    const Span spans[12] = {{text, n_bytes}, {o.bases, o.base_cap}, {o.quals, o.base_cap}, {o.offsets, (o.record_cap + 1) * 8}, {o.qnames, name_cap},
+                            {o.qname_offsets, (o.record_cap + 1) * 8}, {o.aln, o.record_cap * sizeof(zsw_alignment)}, {o.status, o.record_cap}, {o.inc, o.ciglet_cap * 4},
+                            {o.op, o.ciglet_cap}, {o.strand, o.record_cap}, {o.parsed, o.record_cap * sizeof(zsw_sam_parsed)}};
+    if (const int i = first_overlap(spans, 12); i >= 0) return fail(ctx, ZSW_ERR_INVALID_ARGUMENT, i ? "output arrays overlap" : "an output array overlaps the text");
     const bool host = mem == ZSW_MEM_HOST;
     ZSW_HIP(ctx, hipSetDevice(ctx->device));
     DevBuf* ws = ctx->samtext_ws;
     static_assert(SW_N <= sizeof(ctx->samtext_ws) / sizeof(ctx->samtext_ws[0]), "zsw_context::samtext_ws holds every buffer");
     SamArgs a{};
-    a.ix.text = text;
-    a.ix.n_bytes = n_bytes;
     a.flags = flags;
-    a.ix.flags = flags;
     a.rname_len = rname_len;
     a.ref_len = ref_len;
     a.out_bases = o.bases;
@@ -397,123 +347,64 @@ extern "C" zsw_error zsw_sam_parse_batch(zsw_context* ctx, const uint8_t* text, 
         ZSW_HIP(ctx, hipMemcpyAsync(ws[SW_RNAME].p, rname, rname_len, hipMemcpyHostToDevice, stream));
         a.rname = ws[SW_RNAME].as<uint8_t>();
     }
-    if (host) {  // the text crosses once; the outputs are formed in workspace no larger than the bounds that always suffice
-        ZSW_HIP(ctx, ws[SW_TEXT].ensure(n_bytes + 16));
-        if (n_bytes) ZSW_HIP(ctx, hipMemcpyAsync(ws[SW_TEXT].p, text, n_bytes, hipMemcpyHostToDevice, stream));
-        a.ix.text = ws[SW_TEXT].as<uint8_t>();
-        if (!sizing) {
-            a.base_cap = std::min<uint64_t>(o.base_cap, n_bytes);
-            a.name_cap = std::min<uint64_t>(name_cap, n_bytes);
-            a.ciglet_cap = std::min<uint64_t>(o.ciglet_cap, n_bytes / 2);
-            a.record_cap = std::min<uint64_t>(o.record_cap, n_bytes / 14 + 1);
-            ZSW_HIP(ctx, ws[SW_BASES].ensure(a.base_cap + 16));
-            ZSW_HIP(ctx, ws[SW_OFFSETS].ensure((a.record_cap + 1) * 8));
-            ZSW_HIP(ctx, ws[SW_ALN].ensure((a.record_cap + 1) * sizeof(zsw_alignment)));
-            ZSW_HIP(ctx, ws[SW_STATUS].ensure(a.record_cap + 16));
-            ZSW_HIP(ctx, ws[SW_INC].ensure((a.ciglet_cap + 4) * 4));
-            ZSW_HIP(ctx, ws[SW_OP].ensure(a.ciglet_cap + 16));
-            a.out_bases = ws[SW_BASES].as<uint8_t>();
-            a.out_offsets = ws[SW_OFFSETS].as<uint64_t>();
-            a.out_aln = ws[SW_ALN].as<zsw_alignment>();
-            a.out_status = ws[SW_STATUS].as<uint8_t>();
-            a.out_inc = ws[SW_INC].as<uint32_t>();
-            a.out_op = ws[SW_OP].as<uint8_t>();
-            if (o.quals) {
-                ZSW_HIP(ctx, ws[SW_QUALS].ensure(a.base_cap + 16));
-                a.out_quals = ws[SW_QUALS].as<uint8_t>();
-            }
-            if (want_names) {
-                ZSW_HIP(ctx, ws[SW_QNAMES].ensure(a.name_cap + 16));
-                ZSW_HIP(ctx, ws[SW_QOFF].ensure((a.record_cap + 1) * 8));
-                a.out_qnames = ws[SW_QNAMES].as<uint8_t>();
-                a.out_qname_offsets = ws[SW_QOFF].as<uint64_t>();
-            }
-            if (o.strand) {
-                ZSW_HIP(ctx, ws[SW_STRAND].ensure(a.record_cap + 16));
-                a.out_strand = ws[SW_STRAND].as<uint8_t>();
-            }
-            if (o.parsed) {
-                ZSW_HIP(ctx, ws[SW_PARSED].ensure((a.record_cap + 1) * sizeof(zsw_sam_parsed)));
-                a.out_parsed = ws[SW_PARSED].as<zsw_sam_parsed>();
-            }
-        }
+    if (zsw_error e = index_prepare(ctx, &a.ix, text, n_bytes, host, stream)) return e;
+    const bool staged = host && !sizing;  // the outputs are formed in workspace no larger than the bounds that always suffice
+    if (staged) {
+        a.base_cap = std::min<uint64_t>(o.base_cap, n_bytes);
+        a.name_cap = std::min<uint64_t>(name_cap, n_bytes);
+        a.ciglet_cap = std::min<uint64_t>(o.ciglet_cap, n_bytes / 2);
+        a.record_cap = std::min<uint64_t>(o.record_cap, n_bytes / 14 + 1);
     }
-    a.ix.head = (uint32_t)(reinterpret_cast<uintptr_t>(a.ix.text) & 15u);
-    a.ix.n_tiles = tiles_of(a.ix.head, n_bytes);
-    ZSW_HIP(ctx, ws[SW_TILE_COUNTS].ensure((a.ix.n_tiles + 1) * 8));
-    ZSW_HIP(ctx, ws[SW_TILE_BASE].ensure((a.ix.n_tiles + 1) * 8));
-    ZSW_HIP(ctx, ws[SW_STATE].ensure(SS_WORDS * 8));
-    a.ix.tile_counts = ws[SW_TILE_COUNTS].as<uint64_t>();
-    a.ix.tile_base = ws[SW_TILE_BASE].as<uint64_t>();
+    constexpr int N_DOWN = 11;
+    Down downs[N_DOWN] = {{SW_BASES, a.base_cap, (void**)&a.out_bases}, {SW_QUALS, a.base_cap, (void**)&a.out_quals}, {SW_OFFSETS, (a.record_cap + 1) * 8, (void**)&a.out_offsets},
+                          {SW_QNAMES, a.name_cap, (void**)&a.out_qnames}, {SW_QOFF, (a.record_cap + 1) * 8, (void**)&a.out_qname_offsets},
+                          {SW_ALN, (a.record_cap + 1) * sizeof(zsw_alignment), (void**)&a.out_aln}, {SW_STATUS, a.record_cap, (void**)&a.out_status},
+                          {SW_STRAND, a.record_cap, (void**)&a.out_strand}, {SW_PARSED, (a.record_cap + 1) * sizeof(zsw_sam_parsed), (void**)&a.out_parsed},
+                          {SW_INC, a.ciglet_cap * 4, (void**)&a.out_inc}, {SW_OP, a.ciglet_cap, (void**)&a.out_op}};
+    if (staged)
+        if (zsw_error e = stage_down(ctx, ws, downs, N_DOWN)) return e;
+    ZSW_HIP(ctx, ws[SW_STATE].ensure(ST_WORDS * 8));
     a.state = ws[SW_STATE].as<unsigned long long>();
-    unsigned long long state[SS_WORDS] = {};
-    uint64_t want_pos = std::max<uint64_t>(n_bytes / 64 + 64, ws[SW_POS].cap / 8);
-    for (int round = 0; round < 2; ++round) {
-        ZSW_HIP(ctx, ws[SW_POS].ensure(want_pos * 8));
-        a.ix.pos = ws[SW_POS].as<uint64_t>();
-        a.ix.pos_cap = want_pos;
-        a.line_items = want_pos + 1;  // the lines that want_pos newlines can make
+    unsigned long long state[ST_WORDS] = {};
+    uint64_t* sums[SUM_N];
+    LineTerm terms[SUM_N];
+    size_t tmp_sums = 0;
+    const auto size = [&](size_t tmp_tiles, void** scan_tmp) -> zsw_error {
+        a.line_items = a.ix.pos_cap + 1;  // the lines that pos_cap newlines can make
         // hipcub counts its items in an int
         if (a.line_items + 1 > (uint64_t)INT_MAX) return fail(ctx, ZSW_ERR_UNSUPPORTED, "sam text: more than 2^31 lines per call: parse the file in chunks");
         ZSW_HIP(ctx, ws[SW_LINES].ensure(a.line_items * sizeof(Line)));
         a.lines = ws[SW_LINES].as<Line>();
-        uint64_t* sums[SUM_N];
         for (int k = 0; k < SUM_N; ++k) {
             ZSW_HIP(ctx, ws[SW_REC_OFF + k].ensure((a.line_items + 1) * 8));
-            sums[k] = ws[SW_REC_OFF + k].as<uint64_t>();
-            a.sum[k] = sums[k];
+            a.sum[k] = sums[k] = ws[SW_REC_OFF + k].as<uint64_t>();
+            terms[k] = LineTerm{a.lines, a.state + ST_DELIVERED, k};
         }
-        const int scan_items = (int)(a.line_items + 1);
-        size_t tmp_tiles = 0, tmp_terms = 0;
-        ZSW_HIP(ctx, index_scan_bytes(a.ix, &tmp_tiles, stream));
-        {
-            const TermIter in(hipcub::CountingInputIterator<uint64_t>(0), LineTerm{a.lines, a.state + SS_DELIVERED, 0});
-            ZSW_HIP(ctx, hipcub::DeviceScan::ExclusiveSum(nullptr, tmp_terms, in, sums[0], scan_items, stream));
-        }
-        ZSW_HIP(ctx, ws[SW_SCAN_TMP].ensure(std::max(tmp_tiles, tmp_terms) + 16));
-
-        hipLaunchKernelGGL(st_init_kernel, dim3(1), dim3(1), 0, stream, a.state);
-        if (a.ix.n_tiles) {
-            ZSW_HIP(ctx, index_launch(ctx, a.ix, round == 0, ws[SW_SCAN_TMP].p, tmp_tiles, stream));
-            hipLaunchKernelGGL(st_line_kernel, dim3(grid_for(ctx, a.line_items, SAM_BLOCK_LINES)), dim3(LINE_BLOCK), 0, stream, a);
-        }
-        hipLaunchKernelGGL(st_plan_kernel, dim3(1), dim3(1), 0, stream, a);
+        tmp_sums = 0;
+        ZSW_HIP(ctx, delivered_sums(nullptr, &tmp_sums, terms, sums, SUM_N, (int)(a.line_items + 1), stream));
+        ZSW_HIP(ctx, ws[SW_SCAN_TMP].ensure(std::max(tmp_tiles, tmp_sums) + 16));
+        *scan_tmp = ws[SW_SCAN_TMP].p;
+        return ZSW_OK;
+    };
+    const auto launch = [&](void* scan_tmp) -> zsw_error {
+        const dim3 grid(grid_for(ctx, a.line_items, SAM_BLOCK_LINES));
+        if (a.ix.n_tiles) hipLaunchKernelGGL(st_line_kernel, grid, dim3(LINE_BLOCK), 0, stream, a);
+        hipLaunchKernelGGL(plan_kernel<n_lines>, dim3(1), dim3(1), 0, stream, a.ix, a.flags, a.line_items, a.state);
         ZSW_HIP(ctx, hipGetLastError());
-        for (int k = 0; k < SUM_N; ++k) {
-            const TermIter in(hipcub::CountingInputIterator<uint64_t>(0), LineTerm{a.lines, a.state + SS_DELIVERED, k});
-            ZSW_HIP(ctx, hipcub::DeviceScan::ExclusiveSum(ws[SW_SCAN_TMP].p, tmp_terms, in, sums[k], scan_items, stream));
-        }
-        hipLaunchKernelGGL(st_gather_kernel, dim3(grid_for(ctx, a.line_items, SAM_BLOCK_LINES)), dim3(LINE_BLOCK), 0, stream, a);
+        ZSW_HIP(ctx, delivered_sums(scan_tmp, &tmp_sums, terms, sums, SUM_N, (int)(a.line_items + 1), stream));
+        hipLaunchKernelGGL(st_gather_kernel, grid, dim3(LINE_BLOCK), 0, stream, a);
         hipLaunchKernelGGL(st_report_kernel, dim3(1), dim3(1), 0, stream, a);
         ZSW_HIP(ctx, hipGetLastError());
-        ZSW_HIP(ctx, hipMemcpyAsync(state, a.state, sizeof(state), hipMemcpyDeviceToHost, stream));
-        ZSW_HIP(ctx, hipStreamSynchronize(stream));  // the one synchronisation of a device call
-        if (!state[SS_OVERFLOW]) break;
-        if (round == 1) return fail(ctx, ZSW_ERR_HIP, "sam text: the newline positions did not fit twice");
-        want_pos = state[SS_NEWLINES] + 64;  // a text denser than a line per 64 bytes: once more, from the positions on
-    }
-    for (int k = 0; k < SI_WORDS; ++k) out_info[k] = state[SS_INFO + k];
+        return ZSW_OK;
+    };
+    if (zsw_error e = run_rounds<ST_WORDS>(ctx, &a.ix, 64, a.state, state, "sam text: the newline positions did not fit twice", size, launch, stream)) return e;
+    for (int k = 0; k < SI_WORDS; ++k) out_info[k] = state[ST_INFO + k];
     if (sizing) return ZSW_OK;
-    if (!state[SS_WRITTEN]) return fail(ctx, ZSW_ERR_INVALID_ARGUMENT, "a capacity is too small; required sizes returned in out_info");
+    if (!state[ST_WRITTEN]) return fail(ctx, ZSW_ERR_INVALID_ARGUMENT, "a capacity is too small; required sizes returned in out_info");
     if (host) {
-        const uint64_t n = out_info[SI_RECORDS], nb = out_info[SI_BASES], nn = out_info[SI_NAME_BYTES], nc = out_info[SI_CIGLETS];
-        if (nb) ZSW_HIP(ctx, hipMemcpyAsync(o.bases, a.out_bases, nb, hipMemcpyDeviceToHost, stream));
-        if (o.quals && nb) ZSW_HIP(ctx, hipMemcpyAsync(o.quals, a.out_quals, nb, hipMemcpyDeviceToHost, stream));
-        ZSW_HIP(ctx, hipMemcpyAsync(o.offsets, a.out_offsets, (n + 1) * 8, hipMemcpyDeviceToHost, stream));
-        if (want_names) {
-            if (nn) ZSW_HIP(ctx, hipMemcpyAsync(o.qnames, a.out_qnames, nn, hipMemcpyDeviceToHost, stream));
-            ZSW_HIP(ctx, hipMemcpyAsync(o.qname_offsets, a.out_qname_offsets, (n + 1) * 8, hipMemcpyDeviceToHost, stream));
-        }
-        if (n) {
-            ZSW_HIP(ctx, hipMemcpyAsync(o.aln, a.out_aln, n * sizeof(zsw_alignment), hipMemcpyDeviceToHost, stream));
-            ZSW_HIP(ctx, hipMemcpyAsync(o.status, a.out_status, n, hipMemcpyDeviceToHost, stream));
-            if (o.strand) ZSW_HIP(ctx, hipMemcpyAsync(o.strand, a.out_strand, n, hipMemcpyDeviceToHost, stream));
-            if (o.parsed) ZSW_HIP(ctx, hipMemcpyAsync(o.parsed, a.out_parsed, n * sizeof(zsw_sam_parsed), hipMemcpyDeviceToHost, stream));
-        }
-        if (nc) {
-            ZSW_HIP(ctx, hipMemcpyAsync(o.inc, a.out_inc, nc * 4, hipMemcpyDeviceToHost, stream));
-            ZSW_HIP(ctx, hipMemcpyAsync(o.op, a.out_op, nc, hipMemcpyDeviceToHost, stream));
-        }
+        const size_t n = out_info[SI_RECORDS], nb = out_info[SI_BASES], nc = out_info[SI_CIGLETS], off_bytes = (n + 1) * 8;
+        const size_t used[N_DOWN] = {nb, nb, off_bytes, (size_t)out_info[SI_NAME_BYTES], off_bytes, n * sizeof(zsw_alignment), n, n, n * sizeof(zsw_sam_parsed), nc * 4, nc};
+        if (zsw_error e = copy_down(ctx, downs, used, N_DOWN, stream)) return e;
         ZSW_HIP(ctx, hipStreamSynchronize(stream));
     }
     return ZSW_OK;

@@ -1,7 +1,7 @@
 // zsw_samtext.hpp — the rules of zsw_sam_parse_batch (include/zoe_sw.h), shared as text by the kernels (zsw_samtext.hip) and the host
 // model (tests/models/samtext_parse.cpp): what SAMReader (src/data/records/sam/reader.rs:189-286) yields for a buffer of SAM text and
 // what SamData::is_unmapped / to_alignment (sam/mod.rs:305-354) make of each data line, as arithmetic on the positions of the
-// buffer's newlines. The newline index, the line bounds, chop_line_break and the UTF-8 rule are zsw_fastq.hpp's.
+// buffer's newlines. The newline index, the line bounds, chop_line_break and the UTF-8 rule are zsw_text.hpp's.
 //
 // Parts: (1) the Rust integer parsers (str::parse::<u16 / usize / u8 / i64>); (2) the first eleven fields of a line from ballots of
 // its tabs; (3) the CIGAR: every non-digit byte's lane parses the digits in front of it (cig_lane), one uniform walk over those lanes
@@ -10,8 +10,8 @@
 // two and the last two raw ciglets for the clips; (4) the AS lookup (SamOptRaw::get + parse_value, sam/mod.rs:517-540, 581-633);
 // (5) parse_line: the reader's checks in the reader's order, then the conversion.
 //
-// As in zsw_fastq.hpp every lane of a group of FQ_G lanes executes the walk with the same values; what the lanes do apart sits behind
-// the Io. Beside the members zsw_fastq.hpp names:
+// As in zsw_text.hpp every lane of a group of FQ_G lanes executes the walk with the same values; what the lanes do apart sits behind
+// the Io. Beside the members zsw_text.hpp names:
 //   io.mask_byte(lo, n, c)       n <= FQ_G: bit j set iff byte(lo + j) == c
 //   io.sweep_byte(lo, n, c)      the lowest j < n with byte(lo + j) == c, else n
 //   io.sweep_differs(lo, n)      true if byte(lo + j) != rname[j] for some j < n
@@ -20,12 +20,12 @@
 //   io.stage(lo, hi)             the walk is about to read line [lo, hi): an Io may copy it nearer (nothing the rules depend on)
 // Every position is 64-bit; every position is inside the line, which is inside the text, before a load uses it.
 #pragma once
-#include "zsw_fastq.hpp"
+#include "zsw_text.hpp"
 
 namespace zsw {
 namespace samtext {
 
-using namespace zsw::fastq;
+using namespace zsw::text;
 
 enum : int { SF_FINAL = 1, SF_QUAL_FORWARD = 2, SF_ALL = 3 };  // ZSW_SAMTEXT_*
 // the reader's errors: the first failing check of a line
@@ -42,21 +42,21 @@ constexpr uint32_t SAM_FIELDS = 11;
 constexpr uint32_t SAM_BLOCK_LINES = 4;  // wavefronts, i.e. lines in flight, per block
 constexpr uint64_t U32_MAX = 0xffffffffull;
 
-ZSW_FASTQ_HD uint64_t n_lines(const Text& t, bool last_is_newline) {
+ZSW_TEXT_HD uint64_t n_lines(const Text& t, bool last_is_newline) {
     return t.n_newlines + (((t.flags & SF_FINAL) && t.n_bytes && !last_is_newline) ? 1u : 0u);
 }
-ZSW_FASTQ_HD uint64_t sat_add(uint64_t a, uint64_t b) { return a + b < a ? ~0ull : a + b; }
-ZSW_FASTQ_HD bool is_digit(uint8_t c) { return c >= '0' && c <= '9'; }
-ZSW_FASTQ_HD bool is_ascii_space(uint8_t c) { return c == ' ' || c == '\t' || c == '\n' || c == '\x0c' || c == '\r'; }  // u8::is_ascii_whitespace
-ZSW_FASTQ_HD bool is_cigar_op(uint8_t c) {
+ZSW_TEXT_HD uint64_t sat_add(uint64_t a, uint64_t b) { return a + b < a ? ~0ull : a + b; }
+ZSW_TEXT_HD bool is_digit(uint8_t c) { return c >= '0' && c <= '9'; }
+ZSW_TEXT_HD bool is_ascii_space(uint8_t c) { return c == ' ' || c == '\t' || c == '\n' || c == '\x0c' || c == '\r'; }  // u8::is_ascii_whitespace
+ZSW_TEXT_HD bool is_cigar_op(uint8_t c) {
     return c == 'M' || c == 'I' || c == 'D' || c == 'N' || c == 'S' || c == 'H' || c == 'P' || c == 'X' || c == '=';
 }
-ZSW_FASTQ_HD bool op_takes_ref(uint8_t c) { return c == 'M' || c == 'D' || c == 'N' || c == '=' || c == 'X'; }
+ZSW_TEXT_HD bool op_takes_ref(uint8_t c) { return c == 'M' || c == 'D' || c == 'N' || c == '=' || c == 'X'; }
 
 // ---- the integer parsers ----
 // str::parse for an unsigned type with the largest value `max`: one optional '+', then at least one digit and nothing else
 template <class Io>
-ZSW_FASTQ_HD bool parse_unsigned(Io& io, uint64_t lo, uint64_t n, uint64_t max, uint64_t* out) {
+ZSW_TEXT_HD bool parse_unsigned(Io& io, uint64_t lo, uint64_t n, uint64_t max, uint64_t* out) {
     uint64_t j = (n && io.byte(lo) == '+') ? 1u : 0u, x = 0;
     if (j == n) return false;
     for (; j < n; ++j) {
@@ -71,7 +71,7 @@ ZSW_FASTQ_HD bool parse_unsigned(Io& io, uint64_t lo, uint64_t n, uint64_t max, 
 }
 // str::parse::<i64> narrowed to what the score takes: true iff the value parses AND lies in 0 ..= 2^32 - 1 ("-0" is 0)
 template <class Io>
-ZSW_FASTQ_HD bool parse_score(Io& io, uint64_t lo, uint64_t n, uint32_t* out) {
+ZSW_TEXT_HD bool parse_score(Io& io, uint64_t lo, uint64_t n, uint32_t* out) {
     uint64_t x = 0;
     if (n && io.byte(lo) == '-') {
         if (n == 1u) return false;
@@ -87,7 +87,7 @@ ZSW_FASTQ_HD bool parse_score(Io& io, uint64_t lo, uint64_t n, uint32_t* out) {
 // The first eleven fields of line [lo, hi): field k is [f[k], e[k]). -> how many there are (at most eleven); *more: an eleventh tab
 // ends field 10 and optional fields start behind it.
 template <class Io>
-ZSW_FASTQ_HD uint32_t split_fields(Io& io, uint64_t lo, uint64_t hi, uint64_t f[SAM_FIELDS], uint64_t e[SAM_FIELDS], bool* more) {
+ZSW_TEXT_HD uint32_t split_fields(Io& io, uint64_t lo, uint64_t hi, uint64_t f[SAM_FIELDS], uint64_t e[SAM_FIELDS], bool* more) {
     uint32_t k = 0;
     const uint64_t n = hi - lo;
     f[0] = lo;
@@ -113,7 +113,7 @@ struct CigLane {
 };
 // what the lane of the non-digit byte at p finds: the digits in front of it back to the CIGAR's start or the non-digit before them
 template <class Io>
-ZSW_FASTQ_HD CigLane cig_lane(Io& io, uint64_t c_lo, uint64_t p) {
+ZSW_TEXT_HD CigLane cig_lane(Io& io, uint64_t c_lo, uint64_t p) {
     uint64_t s = p;
     while (s > c_lo && is_digit(io.byte(s - 1u))) --s;
     CigLane L{0, io.byte(p)};
@@ -145,12 +145,12 @@ struct Cigar {
     uint64_t n_merged;       // ciglets after the merge (meaningful without an error)
 };
 struct NoSink {
-    ZSW_FASTQ_HD void put(uint64_t, uint64_t, uint32_t) const {}
+    ZSW_TEXT_HD void put(uint64_t, uint64_t, uint32_t) const {}
 };
 
 // One walk over the CIGAR [c_lo, c_hi); sink.put(k, inc, op) receives merged ciglet k as soon as it is complete.
 template <class Io, class Sink>
-ZSW_FASTQ_HD Cigar walk_cigar(Io& io, uint64_t c_lo, uint64_t c_hi, Sink& sink) {
+ZSW_TEXT_HD Cigar walk_cigar(Io& io, uint64_t c_lo, uint64_t c_hi, Sink& sink) {
     Cigar C{};
     const uint64_t n = c_hi - c_lo;
     uint64_t cur_inc = 0, tail = c_lo;  // tail: one behind the last non-digit
@@ -212,7 +212,7 @@ ZSW_FASTQ_HD Cigar walk_cigar(Io& io, uint64_t c_lo, uint64_t c_hi, Sink& sink) 
 }
 
 // to_alignment's clips on the raw ciglets: from the front one optional H, then one optional S; from the back the same among the rest
-ZSW_FASTQ_HD void soft_clips(const Cigar& C, uint64_t* front, uint64_t* back) {
+ZSW_TEXT_HD void soft_clips(const Cigar& C, uint64_t* front, uint64_t* back) {
     uint64_t i = 0, j = C.n_raw;
     *front = *back = 0;
     if (i < j && C.first0.op == 'H') ++i;
@@ -233,7 +233,7 @@ ZSW_FASTQ_HD void soft_clips(const Cigar& C, uint64_t* front, uint64_t* back) {
 // ---- AS ----
 // opt_fields.get("AS") then .int() over the optional fields [lo, hi): true and the score iff Ok(Some(v)) with 0 <= v <= 2^32 - 1
 template <class Io>
-ZSW_FASTQ_HD bool find_score(Io& io, uint64_t lo, uint64_t hi, uint32_t* score) {
+ZSW_TEXT_HD bool find_score(Io& io, uint64_t lo, uint64_t hi, uint32_t* score) {
     for (;;) {
         const uint64_t f_hi = lo + io.sweep_byte(lo, hi - lo, '\t');
         const uint64_t c1 = io.sweep_byte(lo, f_hi - lo, ':');
@@ -260,7 +260,7 @@ struct Line {
 
 // rname_len == 0: no RNAME to compare with
 template <class Io>
-ZSW_FASTQ_HD Line parse_line(Io& io, const Text& t, uint64_t L, uint32_t rname_len) {
+ZSW_TEXT_HD Line parse_line(Io& io, const Text& t, uint64_t L, uint32_t rname_len) {
     Line R{};
     const uint64_t lo = line_start(io, t, L);
     uint64_t hi = line_start(io, t, L + 1u);
