@@ -178,6 +178,41 @@ pub struct FastqBatch {
     pub report:       [u64; ZSW_FASTQ_INFO_WORDS],
 }
 
+/// flags of `zsw_fasta_parse_batch`: the buffer ends the file; names end in front of the first space or tab; the buffer starts at
+/// the '>' of a record that is not the file's first
+pub const ZSW_FASTA_FINAL: i32 = 1;
+pub const ZSW_FASTA_NAME_TO_BLANK: i32 = 2;
+pub const ZSW_FASTA_CONTINUED: i32 = 4;
+/// the first failing check (`report[ZSW_FASTA_INFO_ERROR]`), as `FastaReader` makes them
+pub const ZSW_FASTA_NO_DATA: u64 = 1;
+pub const ZSW_FASTA_MISSING_GT: u64 = 2;
+pub const ZSW_FASTA_MISSING_HEADER: u64 = 3;
+pub const ZSW_FASTA_GT_IN_HEADER: u64 = 4;
+pub const ZSW_FASTA_MISSING_SEQUENCE: u64 = 5;
+pub const ZSW_FASTA_GT_IN_SEQUENCE: u64 = 6;
+/// the words of the report, those of `zsw_fastq_parse_batch`
+pub const ZSW_FASTA_INFO_RECORDS: usize = 0;
+pub const ZSW_FASTA_INFO_BASES: usize = 1;
+pub const ZSW_FASTA_INFO_NAME_BYTES: usize = 2;
+pub const ZSW_FASTA_INFO_CONSUMED: usize = 3;
+pub const ZSW_FASTA_INFO_ERROR: usize = 4;
+pub const ZSW_FASTA_INFO_ERROR_RECORD: usize = 5;
+pub const ZSW_FASTA_INFO_ERROR_OFFSET: usize = 6;
+pub const ZSW_FASTA_INFO_MIN_LEN: usize = 7;
+pub const ZSW_FASTA_INFO_MAX_LEN: usize = 8;
+pub const ZSW_FASTA_INFO_WORDS: usize = 9;
+
+/// What `fasta_parse_batch` returns: record i has the sequence `bases[offsets[i]..offsets[i + 1]]` and the name
+/// `names[name_offsets[i]..name_offsets[i + 1]]` (raw header bytes: `String::from_utf8_lossy` gives the reader's name).
+#[derive(Clone, Debug, Default)]
+pub struct FastaBatch {
+    pub bases:        Vec<u8>,
+    pub offsets:      Vec<u64>,
+    pub names:        Vec<u8>,
+    pub name_offsets: Vec<u64>,
+    pub report:       [u64; ZSW_FASTA_INFO_WORDS],
+}
+
 /// flags of `zsw_sam_parse_batch`: the buffer ends the file; the QUAL of a record with FLAG & 16 is stored back to front
 pub const ZSW_SAMTEXT_FINAL: i32 = 1;
 pub const ZSW_SAMTEXT_QUAL_FORWARD: i32 = 2;
@@ -367,6 +402,7 @@ unsafe extern "C" {
     fn zsw_pileup_batch(ctx: *mut ZswContext, reads: *const ZswBatch, flags: i32, aln: *const ZswAlignment, status: *const u8, inc: *const u32, op: *const u8, n_ciglets: u64, counts: *mut c_void, ins: *mut c_void, out_n_bad: *mut u64, stream: *mut c_void) -> i32;
     fn zsw_consensus_from_counts(ctx: *mut ZswContext, counts: *const c_void, len: u64, mem: i32, flags: i32, fallback: *const u8, out_seq: *mut u8, stream: *mut c_void) -> i32;
     fn zsw_sam_batch(ctx: *mut ZswContext, reads: *const ZswBatch, fields: *const c_void, flags: i32, aln: *const ZswAlignment, status: *const u8, inc: *const u32, op: *const u8, n_ciglets: u64, out_text: *mut u8, text_cap: u64, out_n_bytes: *mut u64, out_line_offsets: *mut u64, out_n_bad: *mut u64, stream: *mut c_void) -> i32;
+    fn zsw_fasta_parse_batch(ctx: *mut ZswContext, text: *const u8, n_bytes: u64, mem: i32, flags: i32, out_bases: *mut u8, base_cap: u64, out_offsets: *mut u64, out_names: *mut u8, name_cap: u64, out_name_offsets: *mut u64, record_cap: u64, out_info: *mut u64, stream: *mut c_void) -> i32;
     fn zsw_fastq_parse_batch(ctx: *mut ZswContext, text: *const u8, n_bytes: u64, mem: i32, flags: i32, out_bases: *mut u8, out_quals: *mut u8, base_cap: u64, out_offsets: *mut u64, out_qnames: *mut u8, name_cap: u64, out_qname_offsets: *mut u64, record_cap: u64, out_info: *mut u64, stream: *mut c_void) -> i32;
     fn zsw_sam_parse_batch(ctx: *mut ZswContext, text: *const u8, n_bytes: u64, mem: i32, flags: i32, rname: *const c_char, rname_len: u32, ref_len: u32, out: *const c_void, out_info: *mut u64, stream: *mut c_void) -> i32;
 }
@@ -1126,6 +1162,36 @@ impl GpuContext {
         out.bases.truncate(out.report[ZSW_FASTQ_INFO_BASES] as usize);
         out.quals.truncate(out.report[ZSW_FASTQ_INFO_BASES] as usize);
         out.names.truncate(out.report[ZSW_FASTQ_INFO_NAME_BYTES] as usize);
+        out.offsets.truncate(records + 1);
+        out.name_offsets.truncate(records + 1);
+        Ok(out)
+    }
+
+    /// `zsw_fasta_parse_batch` over FASTA bytes in host memory: the records `FastaReader` yields in front of its first error, as
+    /// names and sequences back to back with their offsets, and the report (`ZSW_FASTA_INFO_*`). `last`: the buffer ends the file
+    /// (`ZSW_FASTA_FINAL`); otherwise the record at the last '>' waits: parse on from `report[ZSW_FASTA_INFO_CONSUMED]` with the next
+    /// chunk appended and `continued` set. `name_to_blank`: names end in front of the first space or tab. The capacities are the
+    /// bounds that always suffice.
+    pub fn fasta_parse_batch(&self, text: &[u8], last: bool, name_to_blank: bool, continued: bool) -> Result<FastaBatch, GpuError> {
+        let n = text.len() as u64;
+        let flags = if last { ZSW_FASTA_FINAL } else { 0 } | if name_to_blank { ZSW_FASTA_NAME_TO_BLANK } else { 0 } | if continued { ZSW_FASTA_CONTINUED } else { 0 };
+        let (base_cap, name_cap, record_cap) = (n, n, n / 4 + 1);
+        let mut out = FastaBatch {
+            bases: vec![0u8; base_cap as usize],
+            offsets: vec![0u64; record_cap as usize + 1],
+            names: vec![0u8; name_cap as usize],
+            name_offsets: vec![0u64; record_cap as usize + 1],
+            report: [0u64; ZSW_FASTA_INFO_WORDS],
+        };
+        // SAFETY: every array holds the capacity it is declared with; the report holds ZSW_FASTA_INFO_WORDS entries
+        let code = unsafe {
+            zsw_fasta_parse_batch(self.raw, text.as_ptr(), n, ZSW_MEM_HOST, flags, out.bases.as_mut_ptr(), base_cap, out.offsets.as_mut_ptr(), out.names.as_mut_ptr(), name_cap,
+                                  out.name_offsets.as_mut_ptr(), record_cap, out.report.as_mut_ptr(), ptr::null_mut())
+        };
+        self.check(code, 0, 0)?;
+        let records = out.report[ZSW_FASTA_INFO_RECORDS] as usize;
+        out.bases.truncate(out.report[ZSW_FASTA_INFO_BASES] as usize);
+        out.names.truncate(out.report[ZSW_FASTA_INFO_NAME_BYTES] as usize);
         out.offsets.truncate(records + 1);
         out.name_offsets.truncate(records + 1);
         Ok(out)

@@ -5,7 +5,7 @@
 //
 //   g++ -O2 -std=c++17 -Iinclude examples/zsw_driver.cpp -o examples/zsw_driver -Lzoe_amd -lzoe_sw_hip -Wl,-rpath,$PWD/zoe_amd
 //   ./examples/zsw_driver reference.txt reads.fastq [--score-only | --3pass | --both-strands] [--min-score T] [--nm] [--verbose-cigar] [--device-sam]
-//                         [--consensus FILE] [--device-fastq] [--from-sam FILE]
+//                         [--consensus FILE] [--device-fastq] [--from-sam FILE] [--device-fasta] [--ref-record K] [--fasta-reads]
 // --both-strands: every read is aligned on whichever strand scores higher (sw_align_strands_from_i8_3pass); a read answered by
 // its reverse complement gets flag 16, SEQ reverse complemented and QUAL reversed, and POS / CIGAR are those of that sequence.
 // --min-score T (with --3pass or --score-only, the calls ZSW_OPTION_MIN_SCORE covers): a read that scores less than T is written as
@@ -25,6 +25,12 @@
 // ZSW_SAMTEXT_FINAL | ZSW_SAMTEXT_QUAL_FORWARD, the loaded reference's name as RNAME and its length as ref_len); the reads argument is
 // not opened (pass -). --nm, --verbose-cigar, --device-sam and --consensus work on these records as on aligned ones: run on a file the
 // driver wrote, --device-sam writes that file again. A line the reader rejects ends the driver with exit status 1, naming the line.
+// --device-fasta: the reference file is read with one fread and parsed on the GPU (zsw_fasta_parse_batch with ZSW_FASTA_FINAL |
+// ZSW_FASTA_NAME_TO_BLANK) instead of by the getline loop, which glues the records of a multi-record file together and reports no
+// malformed file. Record --ref-record K (default 0) is the reference and its name RNAME. A malformed file ends the driver with exit
+// status 1 and a message naming the code and the record. On a one-record file the output is the same as without the flag.
+// --fasta-reads: the reads argument is FASTA (contigs, consensus sequences, reads without qualities), parsed on the GPU the same way;
+// QUAL is `*`. It does not go with --device-fastq or --from-sam. Without either flag, code path and output are what they were.
 #include <algorithm>
 #include <cstdio>
 #include <cstdlib>
@@ -68,11 +74,11 @@ static std::string read_whole(const std::string& path) {
 
 int main(int argc, char** argv) {
     if (argc < 3) {
-        std::cerr << "usage: zsw_driver reference.(fa|txt) reads.fastq [--score-only | --3pass | --both-strands] [--min-score T] [--nm] [--verbose-cigar] [--device-sam] [--consensus FILE] [--device-fastq] [--from-sam FILE]\n";
+        std::cerr << "usage: zsw_driver reference.(fa|txt) reads.fastq [--score-only | --3pass | --both-strands] [--min-score T] [--nm] [--verbose-cigar] [--device-sam] [--consensus FILE] [--device-fastq] [--from-sam FILE] [--device-fasta] [--ref-record K] [--fasta-reads]\n";
         return 2;
     }
-    bool score_only = false, three_pass = false, both_strands = false, nm = false, verbose_cigar = false, device_sam = false, device_fastq = false;
-    long long min_score = 0;
+    bool score_only = false, three_pass = false, both_strands = false, nm = false, verbose_cigar = false, device_sam = false, device_fastq = false, device_fasta = false, fasta_reads = false;
+    long long min_score = 0, ref_record = 0;
     std::string consensus_path, from_sam;
     for (int k = 3; k < argc; ++k) {
         if (!std::strcmp(argv[k], "--score-only")) score_only = true;
@@ -83,6 +89,9 @@ int main(int argc, char** argv) {
         else if (!std::strcmp(argv[k], "--verbose-cigar")) verbose_cigar = true;
         else if (!std::strcmp(argv[k], "--device-sam")) device_sam = true;
         else if (!std::strcmp(argv[k], "--device-fastq")) device_fastq = true;
+        else if (!std::strcmp(argv[k], "--device-fasta")) device_fasta = true;
+        else if (!std::strcmp(argv[k], "--fasta-reads")) fasta_reads = true;
+        else if (!std::strcmp(argv[k], "--ref-record") && k + 1 < argc) ref_record = std::atoll(argv[++k]);
         else if (!std::strcmp(argv[k], "--consensus") && k + 1 < argc) consensus_path = argv[++k];
         else if (!std::strcmp(argv[k], "--from-sam") && k + 1 < argc) from_sam = argv[++k];
         else {
@@ -102,11 +111,38 @@ int main(int argc, char** argv) {
         std::cerr << "zsw_driver: --from-sam takes its records from the file; it goes with --nm, --verbose-cigar, --device-sam and --consensus only\n";
         return 2;
     }
+    if (fasta_reads && (device_fastq || !from_sam.empty())) {
+        std::cerr << "zsw_driver: --fasta-reads does not go with --device-fastq or --from-sam\n";
+        return 2;
+    }
+    if (ref_record < 0 || (ref_record > 0 && !device_fasta)) {
+        std::cerr << "zsw_driver: --ref-record takes an index from 0 and goes with --device-fasta\n";
+        return 2;
+    }
     try {
         std::string ref_name;
-        const std::string reference = read_reference(argv[1], &ref_name);
-        std::vector<std::string> names, reads, quals;
         std::unique_ptr<zoe::GpuContext> ctx_holder;
+        // a FASTA file with one fread, its records from zsw_fasta_parse_batch; a malformed file is an error that names code and record
+        const auto parse_fasta_file = [&](const char* path) {
+            if (!ctx_holder) ctx_holder.reset(new zoe::GpuContext(0));
+            zoe::FastaRecords fa = ctx_holder->parse_fasta(read_whole(path), true, true);
+            if (fa.error())
+                throw std::runtime_error(std::string("malformed FASTA ") + path + ": code " + std::to_string(fa.error()) + " at record " +
+                                         std::to_string(fa.report[ZSW_FASTA_INFO_ERROR_RECORD]) + " (byte " + std::to_string(fa.report[ZSW_FASTA_INFO_ERROR_OFFSET]) + "): " +
+                                         zoe::FastaRecords::error_text(fa.error()));
+            return fa;
+        };
+        std::string reference;
+        if (device_fasta) {
+            zoe::FastaRecords fa = parse_fasta_file(argv[1]);
+            if ((size_t)ref_record >= fa.sequences.size())
+                throw std::runtime_error("--ref-record " + std::to_string(ref_record) + ": the file has " + std::to_string(fa.sequences.size()) + " records");
+            reference = std::move(fa.sequences[(size_t)ref_record]);
+            ref_name = std::move(fa.names[(size_t)ref_record]);
+        } else {
+            reference = read_reference(argv[1], &ref_name);
+        }
+        std::vector<std::string> names, reads, quals;
         std::vector<zoe::MaybeAligned<zoe::Alignment>> sam_alns;
         std::vector<uint8_t> sam_strands;
         if (!from_sam.empty()) {  // the whole file with one fread, records and reads from zsw_sam_parse_batch
@@ -134,6 +170,11 @@ int main(int argc, char** argv) {
             names = std::move(fastq.names);
             reads = std::move(fastq.reads);
             quals = std::move(fastq.quals);
+        } else if (fasta_reads) {
+            zoe::FastaRecords fa = parse_fasta_file(argv[2]);
+            names = std::move(fa.names);
+            reads = std::move(fa.sequences);
+            quals.assign(reads.size(), "*");  // there are no qualities
         } else {
             std::ifstream fq(argv[2]);
             if (!fq) throw std::runtime_error(std::string("cannot open ") + argv[2]);
@@ -172,7 +213,7 @@ int main(int argc, char** argv) {
         if (nm || verbose_cigar) ann = profiles.annotate(alns, reference, false, false, verbose_cigar, strands);
         if (device_sam) {  // the body from zsw_sam_batch: SEQ oriented, QUAL reversed and the decimals written on the device
             std::cout << "@HD\tVN:1.6\n@SQ\tSN:" << ref_name << "\tLN:" << reference.size() << '\n' << std::flush;
-            const std::string text = profiles.sam_text(verbose_cigar ? ann.verbose : alns, names, quals, ref_name, 255, strands, nm ? &ann : nullptr);
+            const std::string text = profiles.sam_text(verbose_cigar ? ann.verbose : alns, names, fasta_reads ? std::vector<std::string>() : quals, ref_name, 255, strands, nm ? &ann : nullptr);
             std::fwrite(text.data(), 1, text.size(), stdout);
             return 0;
         }

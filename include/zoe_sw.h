@@ -503,6 +503,76 @@ zsw_error zsw_fastq_parse_batch(zsw_context* ctx, const uint8_t* text, uint64_t 
                                 uint8_t* out_quals, uint64_t base_cap, uint64_t* out_offsets, uint8_t* out_qnames, uint64_t name_cap,
                                 uint64_t* out_qname_offsets, uint64_t record_cap, uint64_t* out_info, void* stream);
 
+/* ---- FASTA parsed on the device --------------------------------------------------------------------- */
+/* zsw_fasta_parse_batch turns a buffer of FASTA into the arrays zsw_batch and zsw_sam_fields take, and into sequences that
+ * zsw_set_reference(.., ZSW_MEM_DEVICE) takes where they lie: the sequences of all records back to back with out_offsets, the names
+ * back to back with out_name_offsets. There are no qualities (zsw_sam_fields.quals == NULL prints QUAL '*'). The semantics are
+ * FastaReader's (src/data/records/fasta/mod.rs:241-410), restated on the positions of the buffer's '>' bytes:
+ *   Start of the file. Lines end at '\n'. Lines that hold nothing but ASCII whitespace (space, \t, \n, \x0c, \r; not \x0b), an
+ *   unterminated last one too, are skipped; the first other line must have '>' as its first byte, else MISSING_GT; a text without
+ *   such a line is NO_DATA.
+ *   Records. EVERY '>' byte delimits: the region of a record runs from behind its '>' to the next '>' anywhere, or to the end.
+ *   Header of the file's first record: to the end of its line, then chop_line_break (one '\n', then one '\r'; a '\r' elsewhere in
+ *   it stays in the name). Empty after the chop: MISSING_HEADER; a '>' in that line: GT_IN_HEADER.
+ *   Header of every later record: it ends in front of the first '\n' OR '\r' of the region, so a lone '\r' ends it and what follows
+ *   is sequence. Empty, or the text ends right behind the '>': MISSING_HEADER. No line break in a region that ends at '>' (">>"
+ *   too): GT_IN_HEADER; none in one that ends the text: MISSING_SEQUENCE.
+ *   Sequence: the rest of the region with every '\n' and every '\r' removed, wherever they stand; every other byte stays (blanks,
+ *   lower case, '\0', bytes >= 0x80). Empty: MISSING_SEQUENCE — with one exception the reader has: a later record that ends at
+ *   '>' and whose region holds no '\n' at all (">b\r>c") is GT_IN_HEADER. Not empty, and the region ends at a '>' whose preceding
+ *   byte is not '\n' ("\r>" too): GT_IN_SEQUENCE.
+ *   1 ZSW_FASTA_NO_DATA   2 ZSW_FASTA_MISSING_GT   3 ZSW_FASTA_MISSING_HEADER   4 ZSW_FASTA_GT_IN_HEADER
+ *   5 ZSW_FASTA_MISSING_SEQUENCE   6 ZSW_FASTA_GT_IN_SEQUENCE
+ * Names are the raw header bytes: the reader makes a String of them with from_utf8_lossy, so no byte is an error, and nothing is
+ * replaced here. With ZSW_FASTA_NAME_TO_BLANK a name ends in front of its first space or tab; the emptiness check covers the whole
+ * header.
+ * ZSW_FASTA_FINAL: the buffer ends the file. Without it the record that starts at the last '>' of the buffer is neither parsed nor
+ * an error and CONSUMED is the offset of that '>'; a buffer without '>' that is all whitespace consumes its terminated lines;
+ * NO_DATA is not reported; MISSING_GT is, as soon as a byte that is not whitespace stands in front of the first '>' at a line
+ * start; and every error that a following '>' proves is reported as with FINAL.
+ * ZSW_FASTA_CONTINUED: the buffer starts at the '>' of a record that is not the file's first — what a caller that restarts at
+ * CONSUMED passes. The start-of-file rules do not apply and record 0 takes the later-record header rule. A first byte other than
+ * '>' (an empty buffer too): ZSW_ERR_INVALID_ARGUMENT, no output written.
+ * Taken unchanged from zsw_fastq_parse_batch: the meaning of the nine report words — RECORDS delivered, their BASES and
+ * NAME_BYTES, CONSUMED = the offset one past the last delivered record (the '>' of the first record not delivered, or n_bytes),
+ * ERROR = 0 or a code with ERROR_RECORD the failing record's index and ERROR_OFFSET the offset of its '>', MIN_LEN / MAX_LEN over
+ * the delivered sequences —; here NO_DATA and MISSING_GT concern record 0, leave CONSUMED 0, and ERROR_OFFSET is 0 for NO_DATA and
+ * the first byte that is not whitespace for MISSING_GT. The records in front of the failing record with the lowest index are
+ * delivered; that index is a minimum, not an order of arrival; no atomic decides a place, a minimum and a maximum are the only
+ * atomics, and outputs and report are identical on every run. A malformed text is ZSW_OK and a report, never a fault: every
+ * position taken from memory is clamped into the text, in 64-bit arithmetic, before a load uses it. n_bytes == 0 is ZSW_OK with zero
+ * records (NO_DATA with FINAL). text and every output array live where `mem` says, at any byte address; out_info is host memory,
+ * ZSW_FASTA_INFO_WORDS entries. out_offsets and out_name_offsets hold record_cap + 1 entries. out_names together with
+ * out_name_offsets may be NULL: names are not written (name_cap is ignored, NAME_BYTES still reported).
+ * Capacity protocol: RECORDS > record_cap, BASES > base_cap or NAME_BYTES > name_cap is ZSW_ERR_INVALID_ARGUMENT with the needed
+ * sizes in out_info and no byte of any output array written; every output NULL with every capacity 0 is the sizing call (ZSW_OK).
+ * Bounds that always suffice, so that a caller can do without the sizing call:
+ *   base_cap = n_bytes,  name_cap = n_bytes,  record_cap = n_bytes / 4 + 1  (the shortest record is ">a\nA" at the file's end)
+ * No byte at or beyond out_bases[BASES], out_names[NAME_BYTES] or entry RECORDS + 1 of the offsets is written.
+ * Unknown flag bits, a null required pointer (ctx, out_info; text with n_bytes > 0; out_bases and out_offsets outside the sizing
+ * call; one of out_names / out_name_offsets without the other), an unknown mem, or an output that overlaps the text or another
+ * output: ZSW_ERR_INVALID_ARGUMENT, nothing written, out_info included. More than 2^36 bytes, or about 2^31 '>', per call:
+ * ZSW_ERR_UNSUPPORTED.
+ * The launches — none does work that grows with the length of one record, so ten million short records and one wrapped chromosome
+ * cost the same per byte: the index of zsw_fastq_parse_batch made over '>' (count per tile, exclusive sum, position at rank); a
+ * record pass (one wavefront per record: the header, the line breaks that open the body, every code); an exclusive sum for the name
+ * offsets; the sequence pass over tiles of the text (kept bytes per tile, exclusive sum, every kept byte written at its rank, the
+ * lane that meets a '>' writes that record's offset); a gather for the names. Device calls synchronise the stream once, for the
+ * report; one case aside: the workspace for the '>' positions is sized for one per 64 bytes before the count is known, and a denser
+ * text makes the call repeat its later launches once with the exact size. Host calls are staged and synchronous. The call needs
+ * neither scoring nor a reference, ZSW_OPTION_* do not matter, and zsw_group_* does not cover it. Workspace, kept by the context
+ * until zsw_destroy: 41 bytes per '>' (for one '>' per 64 bytes of text at least), 32 bytes per tile, the scans' scratch, and the staged text and
+ * outputs of a host call. Tile and block constants: zoe_amd/csrc/zsw_text.hpp, zsw_fasta.hpp. */
+enum { ZSW_FASTA_FINAL = 1, ZSW_FASTA_NAME_TO_BLANK = 2, ZSW_FASTA_CONTINUED = 4 };
+enum { ZSW_FASTA_NO_DATA = 1, ZSW_FASTA_MISSING_GT = 2, ZSW_FASTA_MISSING_HEADER = 3, ZSW_FASTA_GT_IN_HEADER = 4,
+       ZSW_FASTA_MISSING_SEQUENCE = 5, ZSW_FASTA_GT_IN_SEQUENCE = 6 };
+enum { ZSW_FASTA_INFO_RECORDS = 0, ZSW_FASTA_INFO_BASES = 1, ZSW_FASTA_INFO_NAME_BYTES = 2, ZSW_FASTA_INFO_CONSUMED = 3,
+       ZSW_FASTA_INFO_ERROR = 4, ZSW_FASTA_INFO_ERROR_RECORD = 5, ZSW_FASTA_INFO_ERROR_OFFSET = 6,
+       ZSW_FASTA_INFO_MIN_LEN = 7, ZSW_FASTA_INFO_MAX_LEN = 8, ZSW_FASTA_INFO_WORDS = 9 };
+zsw_error zsw_fasta_parse_batch(zsw_context* ctx, const uint8_t* text, uint64_t n_bytes, zsw_mem mem, int flags, uint8_t* out_bases,
+                                uint64_t base_cap, uint64_t* out_offsets, uint8_t* out_names, uint64_t name_cap,
+                                uint64_t* out_name_offsets, uint64_t record_cap, uint64_t* out_info, void* stream);
+
 /* ---- SAM parsed on the device ----------------------------------------------------------------------- */
 /* zsw_sam_parse_batch turns a buffer of SAM text into the arrays zsw_annotate_batch, zsw_sam_batch, zsw_pileup_batch and (through
  * the pile-up) zsw_consensus_from_counts take: per data line a zsw_alignment with its status and its ciglets in inc / op, and the

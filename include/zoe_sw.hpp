@@ -173,6 +173,26 @@ struct FastqRecords {
     uint64_t error() const { return report[ZSW_FASTQ_INFO_ERROR]; }
 };
 
+// What GpuContext::parse_fasta returns (zsw_fasta_parse_batch): the records in front of the first malformed one — names as the raw
+// header bytes, sequences with their line breaks removed — and the report (ZSW_FASTA_INFO_*, the words of ZSW_FASTQ_INFO_*)
+struct FastaRecords {
+    std::vector<std::string> names, sequences;
+    uint64_t report[ZSW_FASTA_INFO_WORDS] = {};
+    uint64_t error() const { return report[ZSW_FASTA_INFO_ERROR]; }
+    // the reader's words for a ZSW_FASTA_* code
+    static const char* error_text(uint64_t code) {
+        switch (code) {
+            case ZSW_FASTA_NO_DATA: return "No FASTA data found!";
+            case ZSW_FASTA_MISSING_GT: return "The FASTA file must start with a '>' symbol!";
+            case ZSW_FASTA_MISSING_HEADER: return "Missing FASTA header!";
+            case ZSW_FASTA_GT_IN_HEADER: return "FASTA records must start with the '>' symbol on a newline, and no other '>' symbols can occur in a header!";
+            case ZSW_FASTA_MISSING_SEQUENCE: return "Missing FASTA sequence!";
+            case ZSW_FASTA_GT_IN_SEQUENCE: return "FASTA records must start with the '>' symbol on a newline, and no other '>' symbols can occur in a sequence!";
+        }
+        return "";
+    }
+};
+
 // What GpuContext::parse_sam returns (zsw_sam_parse_batch): the data lines in front of the first malformed line — names, the reads
 // as aligned (SEQ), qualities, the alignments as SamData::to_alignment builds them (Status::Unmapped for unmapped lines, lines of
 // another RNAME and lines with a conversion code), FLAG & 16 per record, the rest of each line — and the report (ZSW_SAMTEXT_INFO_*)
@@ -327,6 +347,27 @@ class GpuContext {
             out.names.emplace_back(qnames.begin() + noff[i], qnames.begin() + noff[i + 1]);
             out.reads.emplace_back(bases.begin() + off[i], bases.begin() + off[i + 1]);
             out.quals.emplace_back(quals.begin() + off[i], quals.begin() + off[i + 1]);
+        }
+        return out;
+    }
+    // zsw_fasta_parse_batch over the bytes of a FASTA buffer (host memory): the records FastaReader yields in front of its first
+    // error, as names and sequences, and the report. last: the buffer ends the file (ZSW_FASTA_FINAL); without it the record at the
+    // last '>' is left for the next call, which starts at report[ZSW_FASTA_INFO_CONSUMED] with `continued`. name_to_blank: names end
+    // in front of the first space or tab. A malformed record does not throw: report[ZSW_FASTA_INFO_ERROR].
+    FastaRecords parse_fasta(const std::string& text, bool last = true, bool name_to_blank = false, bool continued = false) const {
+        const uint64_t n = text.size(), base_cap = n, name_cap = n, record_cap = n / 4 + 1;  // the bounds that always suffice
+        std::vector<uint8_t> bases(base_cap + 1), names(name_cap + 1);
+        std::vector<uint64_t> off(record_cap + 1), noff(record_cap + 1);
+        FastaRecords out;
+        const int flags = (last ? ZSW_FASTA_FINAL : 0) | (name_to_blank ? ZSW_FASTA_NAME_TO_BLANK : 0) | (continued ? ZSW_FASTA_CONTINUED : 0);
+        check(zsw_fasta_parse_batch(ctx_, reinterpret_cast<const uint8_t*>(text.data()), n, ZSW_MEM_HOST, flags, bases.data(), base_cap, off.data(), names.data(), name_cap,
+                                    noff.data(), record_cap, out.report, nullptr));
+        const size_t records = (size_t)out.report[ZSW_FASTA_INFO_RECORDS];
+        out.names.reserve(records);
+        out.sequences.reserve(records);
+        for (size_t i = 0; i < records; ++i) {
+            out.names.emplace_back(names.begin() + noff[i], names.begin() + noff[i + 1]);
+            out.sequences.emplace_back(bases.begin() + off[i], bases.begin() + off[i + 1]);
         }
         return out;
     }

@@ -55,7 +55,7 @@ SYMBOLS = [
     "zsw_group_align_3pass_batch_from",
     "zsw_set_complement", "zsw_score_strands_batch_from", "zsw_orient_batch", "zsw_align_3pass_strands_batch_from", "zsw_strand_counts", "zsw_debug_strand_records", "zsw_debug_score_launches",
     "zsw_min_score_counts", "zsw_annotate_batch", "zsw_sam_batch", "zsw_pileup_batch", "zsw_consensus_from_counts", "zsw_fastq_parse_batch",
-    "zsw_sam_parse_batch",
+    "zsw_sam_parse_batch", "zsw_fasta_parse_batch",
 ]
 
 
@@ -130,6 +130,12 @@ FASTQ_FINAL, FASTQ_NAME_TO_BLANK = 1, 2
  FASTQ_INVALID_QUALITY) = range(1, 9)
 (FASTQ_INFO_RECORDS, FASTQ_INFO_BASES, FASTQ_INFO_NAME_BYTES, FASTQ_INFO_CONSUMED, FASTQ_INFO_ERROR, FASTQ_INFO_ERROR_RECORD, FASTQ_INFO_ERROR_OFFSET,
  FASTQ_INFO_MIN_LEN, FASTQ_INFO_MAX_LEN, FASTQ_INFO_WORDS) = range(10)
+
+# zsw_fasta_parse_batch: flags, the codes of the first failing check, the words of the report (those of zsw_fastq_parse_batch)
+FASTA_FINAL, FASTA_NAME_TO_BLANK, FASTA_CONTINUED = 1, 2, 4
+(FASTA_NO_DATA, FASTA_MISSING_GT, FASTA_MISSING_HEADER, FASTA_GT_IN_HEADER, FASTA_MISSING_SEQUENCE, FASTA_GT_IN_SEQUENCE) = range(1, 7)
+(FASTA_INFO_RECORDS, FASTA_INFO_BASES, FASTA_INFO_NAME_BYTES, FASTA_INFO_CONSUMED, FASTA_INFO_ERROR, FASTA_INFO_ERROR_RECORD, FASTA_INFO_ERROR_OFFSET,
+ FASTA_INFO_MIN_LEN, FASTA_INFO_MAX_LEN, FASTA_INFO_WORDS) = range(10)
 
 # zsw_sam_parse_batch: flags, the reader's codes (SAMTEXT_*), the conversion's codes and bits (SAMREC_*), the words of the report
 SAMTEXT_FINAL, SAMTEXT_QUAL_FORWARD = 1, 2
@@ -259,5 +265,6 @@ def load() -> C.CDLL:
     lib.zsw_consensus_from_counts.argtypes = [vp, vp, C.c_uint64, C.c_int, C.c_int, u8p, u8p, vp]
     lib.zsw_fastq_parse_batch.argtypes = [vp, u8p, C.c_uint64, C.c_int, C.c_int, u8p, u8p, C.c_uint64, u64p, u8p, C.c_uint64, u64p, C.c_uint64, C.POINTER(C.c_uint64), vp]
     lib.zsw_sam_parse_batch.argtypes = [vp, u8p, C.c_uint64, C.c_int, C.c_int, C.c_char_p, C.c_uint32, C.c_uint32, C.POINTER(ZswSamParseOut), C.POINTER(C.c_uint64), vp]
+    lib.zsw_fasta_parse_batch.argtypes = [vp, u8p, C.c_uint64, C.c_int, C.c_int, u8p, C.c_uint64, u64p, u8p, C.c_uint64, u64p, C.c_uint64, C.POINTER(C.c_uint64), vp]
     _lib = lib
     return lib

@@ -120,8 +120,8 @@ struct zsw_context {
     // zsw_pileup_batch / zsw_consensus_from_counts (zsw_pileup.hip): the accumulators (16 bytes per site), the scan's scratch, the
     // counter of malformed records, the staged arrays and tables of a host call
     zsw::DevBuf pu_ws[16];
-    // the newline index of the two parse calls (zsw_text.hip): the staged text of a host call, the tile counts and their sum, 8 bytes
-    // per newline. One set for both calls: the context keeps the larger workspace
+    // the newline (for FASTA: '>') index of the parse calls (zsw_text.hip): the staged text of a host call, the tile counts and their sum, 8 bytes
+    // per newline. One set for all of them: the context keeps the larger workspace
     zsw::DevBuf text_ws[4];
     // zsw_fastq_parse_batch (zsw_fastq.hip): the per-record arrays and their sums, the scans' scratch, the state block with the
     // report, the staged outputs of a host call
@@ -129,6 +129,9 @@ struct zsw_context {
     // zsw_sam_parse_batch (zsw_samtext.hip): 120 bytes and six sums per line, the scans' scratch, the state block with the report,
     // RNAME, the staged outputs of a host call
     zsw::DevBuf samtext_ws[24];
+    // zsw_fasta_parse_batch (zsw_fasta.hip): 25 bytes and one sum per '>', 16 bytes per tile for the kept bytes, the scans' scratch,
+    // the state block with the report, the staged outputs of a host call. The '>' index uses text_ws
+    zsw::DevBuf fa_ws[14];
 };
 
 namespace zsw {

@@ -1,4 +1,5 @@
-// zsw_text.hip — the newline index of zsw_fastq_parse_batch and zsw_sam_parse_batch (declared in zsw_text_dev.hpp; the rules are
+// zsw_text.hip — the newline index of zsw_fastq_parse_batch and zsw_sam_parse_batch, and the same index over '>' for
+// zsw_fasta_parse_batch (declared in zsw_text_dev.hpp; the rules are
 // zsw_text.hpp, shared with the host models):
 //   count     newlines per tile of FQ_TILE bytes: 16-byte loads, the head and the tail granule peeled byte by byte
 //   scan      hipcub's exclusive sum over the tile counts; its last entry is the number of newlines
@@ -37,8 +38,8 @@ __device__ __forceinline__ uint32_t wave_sum(uint32_t x) {
     return x;
 }
 
-// POSITIONS = false: tile_counts[t] = the newlines of tile t. POSITIONS = true: pos[rank] for every newline.
-template <bool POSITIONS>
+// POSITIONS = false: tile_counts[t] = the newlines of tile t. POSITIONS = true: pos[rank] for every newline. BYTE: what counts as one.
+template <bool POSITIONS, uint8_t BYTE>
 __global__ __launch_bounds__(TILE_BLOCK) void newline_kernel(IndexArgs a) {
     const int lane = threadIdx.x & 63;
     const uint64_t wave = (uint64_t)blockIdx.x * FQ_TILE_WAVES + (threadIdx.x >> 6);
@@ -52,16 +53,16 @@ __global__ __launch_bounds__(TILE_BLOCK) void newline_kernel(IndexArgs a) {
         if (!POSITIONS) {
             uint32_t c = 0;
 #pragma unroll
-            for (uint32_t s = 0; s < FQ_TILE_SWEEPS; ++s) c += words_newlines(w[s]);
+            for (uint32_t s = 0; s < FQ_TILE_SWEEPS; ++s) c += words_newlines<BYTE>(w[s]);
             c = wave_sum(c);
             if (lane == 0) a.tile_counts[t] = c;
         } else {
             uint64_t base = uni(a.tile_base[t]);
 #pragma unroll
             for (uint32_t s = 0; s < FQ_TILE_SWEEPS; ++s) {
-                const uint32_t c = words_newlines(w[s]);
+                const uint32_t c = words_newlines<BYTE>(w[s]);
                 const uint32_t x = lane_prefix_sum(c, lane);
-                if (c) put_newlines(io, w[s], a.head, (t * FQ_TILE_SWEEPS + s) * FQ_G + (uint32_t)lane, base + (x - c), a.pos_cap);
+                if (c) put_newlines<BYTE>(io, w[s], a.head, (t * FQ_TILE_SWEEPS + s) * FQ_G + (uint32_t)lane, base + (x - c), a.pos_cap);
                 base += uni((uint32_t)__shfl(x, FQ_G - 1, FQ_G));
             }
         }
@@ -98,18 +99,23 @@ hipError_t index_scan_bytes(const IndexArgs& ix, size_t* bytes, hipStream_t stre
     return hipcub::DeviceScan::ExclusiveSum(nullptr, *bytes, ix.tile_counts, const_cast<uint64_t*>(ix.tile_base), (int)(ix.n_tiles + 1), stream);
 }
 
-hipError_t index_launch(const zsw_context* ctx, const IndexArgs& ix, bool count, void* scan_tmp, size_t scan_bytes, hipStream_t stream) {
+template <uint8_t BYTE>
+hipError_t index_launch_of(const zsw_context* ctx, const IndexArgs& ix, bool count, void* scan_tmp, size_t scan_bytes, hipStream_t stream) {
     if (!ix.n_tiles) return hipSuccess;
     const uint32_t tile_grid = grid_for(ctx, ix.n_tiles, FQ_TILE_WAVES);
     if (count) {
-        hipLaunchKernelGGL((newline_kernel<false>), dim3(tile_grid), dim3(TILE_BLOCK), 0, stream, ix);
+        hipLaunchKernelGGL((newline_kernel<false, BYTE>), dim3(tile_grid), dim3(TILE_BLOCK), 0, stream, ix);
         hipError_t e = hipGetLastError();
         if (e != hipSuccess) return e;
         e = hipcub::DeviceScan::ExclusiveSum(scan_tmp, scan_bytes, ix.tile_counts, const_cast<uint64_t*>(ix.tile_base), (int)(ix.n_tiles + 1), stream);
         if (e != hipSuccess) return e;
     }
-    hipLaunchKernelGGL((newline_kernel<true>), dim3(tile_grid), dim3(TILE_BLOCK), 0, stream, ix);
+    hipLaunchKernelGGL((newline_kernel<true, BYTE>), dim3(tile_grid), dim3(TILE_BLOCK), 0, stream, ix);
     return hipGetLastError();
+}
+
+hipError_t index_launch(const zsw_context* ctx, const IndexArgs& ix, bool count, void* scan_tmp, size_t scan_bytes, hipStream_t stream, uint8_t byte) {
+    return byte == '>' ? index_launch_of<'>'>(ctx, ix, count, scan_tmp, scan_bytes, stream) : index_launch_of<'\n'>(ctx, ix, count, scan_tmp, scan_bytes, stream);
 }
 
 }  // namespace text

@@ -37,9 +37,11 @@ constexpr uint32_t FQ_TILE_WAVES = 4;         // tiles in flight per block of th
 static_assert(FQ_TILE == 16u * FQ_G * FQ_TILE_SWEEPS, "a tile is FQ_TILE_SWEEPS sweeps of FQ_G granules");
 
 // ---- newlines ----
-// 0x80 in every byte of w that is '\n' (exact: no carry leaves a byte)
+// 0x80 in every byte of w that is BYTE — '\n', or the byte another index is made of ('>' for zsw_fasta.hpp) (exact: no carry
+// leaves a byte)
+template <uint8_t BYTE = '\n'>
 ZSW_TEXT_HD uint32_t nl_mask(uint32_t w) {
-    const uint32_t x = w ^ 0x0a0a0a0au;
+    const uint32_t x = w ^ (0x01010101u * BYTE);
     return ~(((x & 0x7f7f7f7fu) + 0x7f7f7f7fu) | x | 0x7f7f7f7fu);
 }
 ZSW_TEXT_HD uint32_t popcount32(uint32_t v) {
@@ -63,15 +65,16 @@ ZSW_TEXT_HD void granule_words(Io& io, uint64_t head, uint64_t n_bytes, uint64_t
         if (v >= lo && v < hi) w[b >> 2] |= (uint32_t)io.byte(v - head) << (8u * (b & 3u));
     }
 }
+template <uint8_t BYTE = '\n'>
 ZSW_TEXT_HD uint32_t words_newlines(const uint32_t w[4]) {
-    return popcount32(nl_mask(w[0]) | (nl_mask(w[1]) >> 1) | (nl_mask(w[2]) >> 2) | (nl_mask(w[3]) >> 3));
+    return popcount32(nl_mask<BYTE>(w[0]) | (nl_mask<BYTE>(w[1]) >> 1) | (nl_mask<BYTE>(w[2]) >> 2) | (nl_mask<BYTE>(w[3]) >> 3));
 }
 // the positions of the newlines of granule g, in order, to out[rank], out[rank + 1], .. as far as rank < cap -> how many there are
-template <class Io>
+template <uint8_t BYTE = '\n', class Io>
 ZSW_TEXT_HD uint32_t put_newlines(Io& io, const uint32_t w[4], uint64_t head, uint64_t g, uint64_t rank, uint64_t cap) {
     uint32_t c = 0;
     for (uint32_t i = 0; i < 4u; ++i) {
-        uint32_t m = nl_mask(w[i]);
+        uint32_t m = nl_mask<BYTE>(w[i]);
         for (uint32_t b = 0; b < 4u; ++b, m >>= 8)
             if (m & 0x80u) {
                 if (rank + c < cap) io.put_position(rank + c, g * 16u + 4u * i + b - head);

@@ -39,7 +39,8 @@ zsw_error index_prepare(zsw_context* ctx, IndexArgs* ix, const uint8_t* text, ui
 // caller whose workspace for the positions was an estimate finds tile_base[n_tiles] > pos_cap on the device, and calls once more
 // without `count` and with the exact size (run_rounds).
 hipError_t index_scan_bytes(const IndexArgs& ix, size_t* bytes, hipStream_t stream);
-hipError_t index_launch(const zsw_context* ctx, const IndexArgs& ix, bool count, void* scan_tmp, size_t scan_bytes, hipStream_t stream);
+// byte: '\n', or '>' for the index of zsw_fasta_parse_batch's record delimiters (the same sweep, instantiated for that byte).
+hipError_t index_launch(const zsw_context* ctx, const IndexArgs& ix, bool count, void* scan_tmp, size_t scan_bytes, hipStream_t stream, uint8_t byte = '\n');
 
 using namespace zsw::wave;
 
@@ -135,7 +136,7 @@ hipError_t delivered_sums(void* tmp, size_t* tmp_bytes, const Term* terms, uint6
 // on, with the exact size. twice: the error text of a second overflow.
 template <int WORDS, class Size, class Launch>
 zsw_error run_rounds(zsw_context* ctx, IndexArgs* ix, uint64_t pos_per_bytes, unsigned long long* d_state, unsigned long long* state, const char* twice, Size size,
-                     Launch launch, hipStream_t stream) {
+                     Launch launch, hipStream_t stream, uint8_t byte = '\n') {
     using namespace zsw::capi;
     DevBuf& pos = ctx->text_ws[TW_POS];
     uint64_t want_pos = std::max<uint64_t>(ix->n_bytes / pos_per_bytes + 64, pos.cap / 8);
@@ -149,7 +150,7 @@ zsw_error run_rounds(zsw_context* ctx, IndexArgs* ix, uint64_t pos_per_bytes, un
         zsw_error err = size(tiles_tmp, &scan_tmp);
         if (err != ZSW_OK) return err;
         hipLaunchKernelGGL(state_init_kernel<WORDS>, dim3(1), dim3(1), 0, stream, d_state);
-        ZSW_HIP(ctx, index_launch(ctx, *ix, round == 0, scan_tmp, tiles_tmp, stream));
+        ZSW_HIP(ctx, index_launch(ctx, *ix, round == 0, scan_tmp, tiles_tmp, stream, byte));
         err = launch(scan_tmp);
         if (err != ZSW_OK) return err;
         ZSW_HIP(ctx, hipMemcpyAsync(state, d_state, WORDS * 8, hipMemcpyDeviceToHost, stream));

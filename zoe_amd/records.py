@@ -2,6 +2,7 @@
 
 Mirrors, for exactly what the path needs:
     FastQReader            src/data/records/fastq/reader.rs:17-187 (single-line FASTQ; same validation and messages)
+    FastaReader            src/data/records/fasta/mod.rs:241-410 (multi-line FASTA; the same statements, checks and messages)
     SamData::from_alignment src/data/records/sam/mod.rs:223-245   (POS = ref_range.start + 1, CIGAR = states, AS:i = score;
                             with the stats of `annotate` also NM:i = mismatches + inserted + deleted bases)
     Display for SamData     src/data/records/sam/std_traits.rs:3-44 (tab-separated, optional fields appended)
@@ -13,6 +14,7 @@ Mirrors, for exactly what the path needs:
 from __future__ import annotations
 
 import io
+import re
 from dataclasses import dataclass, field
 from typing import BinaryIO, Iterator, List, Optional
 
@@ -93,6 +95,146 @@ class FastQReader:
         if any(c < 33 or c > 126 for c in qual):  # QualityScores: graphic ASCII
             raise FastQError(f"Invalid quality score byte! See: {header_s}")
         return FastQ(header_s, seq, qual)
+
+
+class FastaError(ValueError):
+    """std::io::ErrorKind::InvalidData of the reference's FASTA reader; `code` is the ZSW_FASTA_* value of the failing check and `offset`
+    where zsw_fasta_parse_batch points for it: the record's '>', or the first byte that is not whitespace for MISSING_GT."""
+
+    def __init__(self, code: int, message: str, offset: int = 0):
+        super().__init__(message)
+        self.code, self.offset = code, offset
+
+
+@dataclass
+class Fasta:
+    name: bytes  # the raw header bytes (the reference makes a String of them with from_utf8_lossy; nothing is an error)
+    sequence: bytes
+
+
+_ASCII_WHITESPACE = b" \t\n\x0c\r"  # u8::is_ascii_whitespace: no \x0b
+_GT_HEADER = "FASTA records must start with the '>' symbol on a newline, and no other '>' symbols can occur in a header!"
+_GT_SEQUENCE = "FASTA records must start with the '>' symbol on a newline, and no other '>' symbols can occur in a sequence!"
+
+
+def _lines_ascii(b: bytes) -> List[bytes]:
+    """SplitByByte2 over '\\n' and '\\r' (src/search/bytes/search.rs:23-79): nothing for an empty haystack, else one piece more than
+    there are line-break bytes"""
+    return re.split(b"[\n\r]", b) if b else []
+
+
+class FastaReader:
+    """Iterator over FASTA records (fasta/mod.rs:255-412), statement by statement: `read_first_record` for the file's first record,
+    `next` for the others, both over `read_until`. `start` is the offset of the '>' of the record being read. continued: the stream
+    starts at the '>' of a record that is not the file's first (what a caller that restarts at CONSUMED holds)."""
+
+    def __init__(self, inner: BinaryIO, continued: bool = False):
+        self._f = inner
+        self._pending = b""
+        self.offset = 0  # bytes read so far
+        self.start = 0
+        self.buffer = bytearray()
+        self.first_record = True
+        if continued:
+            if self._read_until(b">", bytearray()) != 1:
+                raise ValueError("a continued FASTA stream starts at '>'")
+            self.first_record = False
+            self.buffer = bytearray(b">")
+
+    @staticmethod
+    def from_readable(inner: BinaryIO) -> "FastaReader":
+        buffered = inner if isinstance(inner, io.BufferedReader) else io.BufferedReader(inner)
+        if not buffered.peek(1):
+            raise FastaError(_lib.FASTA_NO_DATA, "No FASTA data was found!")
+        return FastaReader(buffered)
+
+    def _read_until(self, delim: bytes, buf: bytearray) -> int:
+        """BufRead::read_until: appends up to and including `delim`, or to the end -> the bytes read"""
+        n = 0
+        while True:
+            if not self._pending:
+                self._pending = self._f.read(1 << 16)
+                if not self._pending:
+                    break
+            i = self._pending.find(delim)
+            take = len(self._pending) if i < 0 else i + 1
+            buf += self._pending[:take]
+            self._pending = self._pending[take:]
+            n += take
+            if i >= 0:
+                break
+        self.offset += n
+        return n
+
+    def __iter__(self) -> Iterator[Fasta]:
+        return self
+
+    def _error(self, code: int, msg: str, header: Optional[bytes] = None, offset: Optional[int] = None) -> FastaError:
+        if header is not None:
+            msg = f"{msg} See header: {header.decode('utf-8', 'replace')}"
+        return FastaError(code, msg, self.start if offset is None else offset)
+
+    def _read_first_record(self) -> Fasta:
+        self.first_record = False
+        while True:
+            self.start = self.offset
+            n = self._read_until(b"\n", self.buffer)
+            if n == 0:
+                self.buffer.clear()  # the iterator ends behind this error
+                raise self._error(_lib.FASTA_NO_DATA, "No FASTA data found!", offset=0)
+            if self.buffer.startswith(b">"):
+                header = _chop_line_break(bytes(self.buffer[1:]))
+                if not header:
+                    raise self._error(_lib.FASTA_MISSING_HEADER, "Missing FASTA header!")
+                if b">" in header:
+                    raise self._error(_lib.FASTA_GT_IN_HEADER, _GT_HEADER, header)
+                self.buffer.clear()
+                self._read_until(b">", self.buffer)
+                sequence = bytearray(b"".join(_lines_ascii(bytes(self.buffer))))
+                if sequence.endswith(b">"):
+                    sequence.pop()
+                if not sequence:
+                    raise self._error(_lib.FASTA_MISSING_SEQUENCE, "Missing FASTA sequence!", header)
+                if not self.buffer.endswith(b"\n>"):
+                    if self.buffer.endswith(b">"):
+                        raise self._error(_lib.FASTA_GT_IN_SEQUENCE, _GT_SEQUENCE, header)
+                    self.buffer.clear()
+                return Fasta(header, bytes(sequence))
+            elif all(c in _ASCII_WHITESPACE for c in self.buffer):
+                self.buffer.clear()
+            else:
+                first = next(k for k, c in enumerate(self.buffer) if c not in _ASCII_WHITESPACE)
+                raise self._error(_lib.FASTA_MISSING_GT, "The FASTA file must start with a '>' symbol!", offset=self.start + first)
+
+    def __next__(self) -> Fasta:
+        if self.first_record:
+            return self._read_first_record()
+        if not self.buffer:
+            raise StopIteration
+        self.start = self.offset - 1  # the '>' that ended the last read
+        self.buffer.clear()
+        self._read_until(b">", self.buffer)
+        split = _lines_ascii(bytes(self.buffer))
+        if not split:
+            raise self._error(_lib.FASTA_MISSING_HEADER, "Missing FASTA header!")
+        name = split[0]
+        if not name:
+            raise self._error(_lib.FASTA_MISSING_HEADER, "Missing FASTA header!")
+        sequence = bytearray(b"".join(split[1:]))
+        if sequence.endswith(b">"):
+            sequence.pop()
+        if not sequence:
+            if self.buffer.endswith(b">"):
+                if b"\n" in self.buffer:
+                    raise self._error(_lib.FASTA_MISSING_SEQUENCE, "Missing FASTA sequence!", name)
+                self._read_until(b"\n", self.buffer)
+                raise self._error(_lib.FASTA_GT_IN_HEADER, _GT_HEADER, _chop_line_break(bytes(self.buffer)))
+            raise self._error(_lib.FASTA_MISSING_SEQUENCE, "Missing FASTA sequence!", name)
+        if not self.buffer.endswith(b"\n>"):
+            if self.buffer.endswith(b">"):
+                raise self._error(_lib.FASTA_GT_IN_SEQUENCE, _GT_SEQUENCE, name)
+            self.buffer.clear()
+        return Fasta(name, bytes(sequence))
 
 
 def batch_from_fastq(records: List[FastQ], device: int = 0) -> ReadBatch:
@@ -542,6 +684,91 @@ def fastq_batch_from_text(text: bytes, device: int = 0, final: bool = True, name
     n_rec, n_bases, n_names = (int(report[k]) for k in (_lib.FASTQ_INFO_RECORDS, _lib.FASTQ_INFO_BASES, _lib.FASTQ_INFO_NAME_BYTES))
     reads = ReadBatch(d_bases[:max(n_bases, 1)], n_rec, offsets=d_off[:n_rec + 1], min_len=int(report[_lib.FASTQ_INFO_MIN_LEN]) if n_rec else None)
     return FastQDeviceBatch(reads, d_quals[:max(n_bases, 1)], d_names[:max(n_names, 1)], d_noff[:n_rec + 1], report)
+
+
+class FastaDeviceBatch:
+    """What `fasta_batch_from_text` returns: the records of a FASTA buffer as zsw_fasta_parse_batch left them in device memory.
+
+    bases          CUDA uint8, the sequences back to back (line breaks removed)
+    offsets        CUDA int64, n + 1 entries
+    names          CUDA uint8, the names back to back (raw header bytes)
+    name_offsets   CUDA int64, n + 1 entries
+    consumed       the offset one past the last record (a caller that reads a file in chunks restarts there, with continued=True)
+    report         the ZSW_FASTA_INFO_* words"""
+
+    def __init__(self, bases, offsets, names, name_offsets, report):
+        self.bases, self.offsets, self.names, self.name_offsets, self.report = bases, offsets, names, name_offsets, report
+        self.n_records = int(report[_lib.FASTA_INFO_RECORDS])
+        self.consumed = int(report[_lib.FASTA_INFO_CONSUMED])
+        self._host_offsets = None
+
+    def __len__(self) -> int:
+        return self.n_records
+
+    def as_read_batch(self) -> ReadBatch:
+        """the records as reads for the profile classes (there are no qualities: `to_sam_text` with quals=None prints '*')"""
+        n = self.n_records
+        return ReadBatch(self.bases, n, offsets=self.offsets, min_len=int(self.report[_lib.FASTA_INFO_MIN_LEN]) if n else None)
+
+    def sequence(self, r: int):
+        """record r's sequence as a view of the device array: what `SwContext.set_reference` takes without a copy"""
+        if not 0 <= r < self.n_records:
+            raise IndexError(f"record {r} of {self.n_records}")
+        if self._host_offsets is None:
+            self._host_offsets = self.offsets.cpu().numpy()
+        return self.bases[int(self._host_offsets[r]):int(self._host_offsets[r + 1])]
+
+    def records(self) -> List[Fasta]:
+        """the `List[Fasta]` a FastaReader over the same bytes yields (with name_to_blank: `name` ends at the first blank)"""
+        from .alignment import _to_host
+
+        n = self.n_records
+        if n == 0:
+            return []
+        bases, off, names, noff = _to_host(self.bases, self.offsets, self.names, self.name_offsets)
+        b, nm = bases.tobytes(), names.tobytes()
+        return [Fasta(nm[noff[i]:noff[i + 1]], b[off[i]:off[i + 1]]) for i in range(n)]
+
+
+def fasta_batch_from_text(text: bytes, device: int = 0, final: bool = True, name_to_blank: bool = False, continued: bool = False) -> FastaDeviceBatch:
+    """Uploads the bytes of a FASTA buffer once and parses them on the device (zsw_fasta_parse_batch, with the capacities that always
+    suffice). final: the buffer ends the file; otherwise the record that starts at the buffer's last '>' is left, and `.consumed` is
+    the offset of that '>'. continued: the buffer starts at the '>' of a record that is not the file's first. name_to_blank: names end
+    in front of the first space or tab. A malformed text raises FastaError with the message FastaReader gives for it."""
+    import ctypes as C
+
+    import numpy as np
+    import torch
+
+    from .alignment import SwContext
+
+    ctx = SwContext.get(device)
+    dev = torch.device("cuda", device)
+    view = memoryview(text).cast("B")
+    n = len(view)
+    d_text = torch.frombuffer(bytearray(view) if n else bytearray(1), dtype=torch.uint8).to(dev)
+    base_cap, name_cap, record_cap = n, n, n // 4 + 1
+    d_bases = torch.empty(max(base_cap, 1), dtype=torch.uint8, device=dev)
+    d_names = torch.empty(max(name_cap, 1), dtype=torch.uint8, device=dev)
+    d_off = torch.empty(record_cap + 1, dtype=torch.int64, device=dev)
+    d_noff = torch.empty(record_cap + 1, dtype=torch.int64, device=dev)
+    info = (C.c_uint64 * _lib.FASTA_INFO_WORDS)()
+    flags = (_lib.FASTA_FINAL if final else 0) | (_lib.FASTA_NAME_TO_BLANK if name_to_blank else 0) | (_lib.FASTA_CONTINUED if continued else 0)
+    ctx.check(ctx.lib.zsw_fasta_parse_batch(ctx.h, d_text.data_ptr(), n, _lib.MEM_DEVICE, flags, d_bases.data_ptr(), base_cap, d_off.data_ptr(), d_names.data_ptr(), name_cap,
+                                            d_noff.data_ptr(), record_cap, info, ctx.stream()), profile_errors=False)
+    report = np.array(list(info), dtype=np.uint64)
+    code = int(report[_lib.FASTA_INFO_ERROR])
+    if code:
+        index = int(report[_lib.FASTA_INFO_ERROR_RECORD])
+        try:  # the reader's own message: the records in front of the failing one are read again on the host
+            for _ in FastaReader(io.BytesIO(bytes(view)), continued=continued):
+                pass
+        except FastaError as e:
+            if e.code == code:
+                raise FastaError(code, f"record {index}: {e}", int(report[_lib.FASTA_INFO_ERROR_OFFSET])) from None
+        raise FastaError(code, f"FASTA record {index} is malformed (code {code})", int(report[_lib.FASTA_INFO_ERROR_OFFSET]))
+    n_rec, n_bases, n_names = (int(report[k]) for k in (_lib.FASTA_INFO_RECORDS, _lib.FASTA_INFO_BASES, _lib.FASTA_INFO_NAME_BYTES))
+    return FastaDeviceBatch(d_bases[:max(n_bases, 1)], d_off[:n_rec + 1], d_names[:max(n_names, 1)], d_noff[:n_rec + 1], report)
 
 
 def align_fastq_text_to_sam_text(text: bytes, reference: bytes, rname: str, matrix, gap_open: int, gap_extend: int,
