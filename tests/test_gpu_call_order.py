@@ -1,11 +1,13 @@
 """A call's result does not depend on what the context did before.
 
-A zsw_context keeps state between calls: the staging and workspace buffers only grow, `seed_ready` / `chunk_ready` /
-`prune_chunk` / `shared_call` are set per call, the k-mer indices are rebuilt lazily after a change of reference or matrix, the
-shared role swaps the reference length for the length of a call. One long-lived context runs a fixed list of calls in which each
-pair that could leak stands next to each other (large then small, fixed then ragged, host then device, shared then read role,
+A zsw_context keeps state between calls: the staging and workspace buffers only grow (and keep the tails of larger calls), the
+k-mer indices of the reference and of the profile sequence are built lazily and rebuilt after a change of sequence or matrix, and
+the last-call record says whether the counters behind zsw_prune_rescored / zsw_min_score_counts belong to the last call. What a
+call decides for itself (its target, the passes its batch takes, its result arrays) travels in values of that call, not on the
+context. One long-lived context runs a fixed list of calls in which each pair that could leak stands next to each other (large then small, fixed then ragged, host then device, shared then read role,
 option and debug bits on then off, a long reference then the short one, a 25-letter matrix then DNA, debug records on then off, a
-failing call then a good one, certificate alignment / 3-pass / certificate alignment). After every call the same call is made on
+failing call then a good one — also one that fails inside a shared-role call —, certificate alignment / 3-pass / certificate
+alignment, a shared seeded pass directly before a read-role seeded reverse pass). After every call the same call is made on
 a context created for it, and every output array and zsw_prune_rescored must be equal. No oracle here: test_gpu_abi_matrix.py
 and the rest of the suite tie the results of a fresh context to it."""
 import ctypes as C
@@ -64,6 +66,10 @@ STEPS = [
     ({}, "offsets", "zsw_score_batch_from", "ragged_small", "host-ragged"),
     ({}, "capacity", "zsw_align_batch_from", "small", "host-fixed"),
     ({}, None, "zsw_score_batch_from", "big", "host-fixed"),
+    ({}, "shared_offsets", "zsw_score_batch_from", "ragged_small", "host-ragged"),  # a shared-role call that fails while its batch is staged
+    ({}, "shared_capacity", "zsw_align_batch_from", "small", "host-fixed"),         # ... and one that fails when it delivers
+    ({}, None, "zsw_score_ends_shared_batch", "small", "device-fixed"),             # a shared seeded pass ...
+    ({}, None, "zsw_score_ranges_batch_from", "small", "device-fixed"),             # ... then the read role's seeded reverse pass
 ]
 
 
@@ -151,17 +157,21 @@ def fail_first(w, h, kind, p):
     msg = lambda: lib.zsw_last_error_string(h).decode()
     if kind == "bad_lanes":
         assert lib.zsw_score_batch(h, p.ref(), 1, 3, score.ctypes.data, status.ctypes.data, None) == -1 and "lanes" in msg()
-    elif kind == "offsets":
+    elif kind in ("offsets", "shared_offsets"):
         bad = p.rs.offsets.copy()
         bad[n // 2] = bad[n // 2 + 1] + 40  # goes backwards after this entry, inside the buffer
         b = _lib.ZswBatch()
         b.bases, b.offsets, b.fixed_len, b.n_reads, b.mem = p.rs.bases.ctypes.data, bad.ctypes.data, 0, n, _lib.MEM_HOST
-        assert lib.zsw_score_batch_from(h, C.byref(b), 8, 256, score.ctypes.data, status.ctypes.data, None, None) == -1 and "monotone" in msg()
-    elif kind == "capacity":
+        fn = lib.zsw_score_batch_from if kind == "offsets" else lib.zsw_score_shared_batch_from
+        assert fn(h, C.byref(b), 8, 256, score.ctypes.data, status.ctypes.data, None, None) == -1 and "monotone" in msg()
+    elif kind in ("capacity", "shared_capacity"):
         aln = np.zeros(n, dtype=ah.ALN_DTYPE)
         inc, op, total = np.zeros(1, dtype=np.uint32), np.zeros(1, dtype=np.uint8), C.c_uint64(0)
-        rc = lib.zsw_align_batch_from(h, p.ref(), 8, 256, 0, aln.ctypes.data, status.ctypes.data, None, inc.ctypes.data, op.ctypes.data, 1, C.byref(total), None)
+        fn, invert = (lib.zsw_align_batch_from, 0) if kind == "capacity" else (lib.zsw_align_shared_batch_from, 1)
+        rc = fn(h, p.ref(), 8, 256, invert, aln.ctypes.data, status.ctypes.data, None, inc.ctypes.data, op.ctypes.data, 1, C.byref(total), None)
         assert rc == -1 and total.value > 1 and "capacity" in msg()
+    else:
+        raise AssertionError(kind)
 
 
 def rescored(w, h):

@@ -52,7 +52,6 @@ __global__ void selftest_kernel(uint32_t* out) {
 
 
 
-// Brings a batch to the device (or validates device pointers), finds the longest read and sizes the workspace.
 // ZSW_ENCODING_PACKED4: two residue indices per byte -> one byte per base (byte_of[index]: a byte the context's map sends to it)
 struct Unpack4 {
     uint8_t byte_of[16];
@@ -86,13 +85,10 @@ hipError_t copy_packed_chunk(zsw_context* ctx, const zsw_batch* reads, size_t fi
     return hipGetLastError();
 }
 
-zsw_error stage(zsw_context* ctx, const zsw_batch* reads, hipStream_t stream, bool want_tier, bool want_ends,
-                uint32_t* out_score, uint8_t* out_status, uint8_t* out_tier, uint32_t* out_rend, uint32_t* out_qend,
-                Staged* st, bool defer_bases_copy) {
-    if (!ctx) return ZSW_ERR_INVALID_ARGUMENT;
-    ctx->score_launches.clear();  // zsw_debug_score_launches reports the launches of this call
-    if (!ctx->scoring_set || !ctx->reference_set) return fail(ctx, ZSW_ERR_NOT_CONFIGURED, "scoring/reference not set");
-    if (!reads || !out_score || !out_status) return fail(ctx, ZSW_ERR_INVALID_ARGUMENT, "null argument");
+// stage(), step 1: the arguments of the call
+static zsw_error check_batch(zsw_context* ctx, const Against& t, const zsw_batch* reads, const ScoreDest* dest) {
+    if (!ctx->scoring_set || !t.set) return fail(ctx, ZSW_ERR_NOT_CONFIGURED, "scoring/reference not set");
+    if (!reads || (dest && (!dest->score || !dest->status))) return fail(ctx, ZSW_ERR_INVALID_ARGUMENT, "null argument");
     if (reads->n_reads > 0x7fffffffull) return fail(ctx, ZSW_ERR_INVALID_ARGUMENT, "n_reads > 2^31-1 per call");
     if (reads->n_reads && !reads->bases) return fail(ctx, ZSW_ERR_INVALID_ARGUMENT, "null bases");
     if (!reads->offsets && reads->fixed_len == 0 && reads->n_reads) return ZSW_ERR_EMPTY_SEQUENCE;
@@ -100,68 +96,68 @@ zsw_error stage(zsw_context* ctx, const zsw_batch* reads, hipStream_t stream, bo
     if (reads->encoding != ZSW_ENCODING_BYTES && !packed) return fail(ctx, ZSW_ERR_INVALID_ARGUMENT, "unknown zsw_batch.encoding");
     if (packed && (reads->mem != ZSW_MEM_HOST || reads->offsets || ctx->h_sc.S > 16))
         return fail(ctx, ZSW_ERR_INVALID_ARGUMENT, "ZSW_ENCODING_PACKED4: fixed-length host batches, alphabets of up to 16 letters");
-    const uint32_t n = (uint32_t)reads->n_reads;
-    ZSW_HIP(ctx, hipSetDevice(ctx->device));
-    st->b.n_reads = n;
-    st->b.n_items = n;
-    st->b.items = nullptr;
-    st->b.fixed_len = reads->fixed_len;
-    if (reads->mem == ZSW_MEM_HOST) {
-        size_t total = reads->offsets ? (size_t)reads->offsets[n] : (size_t)n * reads->fixed_len;
-        ZSW_HIP(ctx, ctx->s_bases.ensure(total + 16));
-        if (packed) {  // half the bytes cross PCIe; the device spells them out as bytes again (one representative byte per residue index)
-            ZSW_HIP(ctx, ctx->s_packed.ensure((size_t)n * ((reads->fixed_len + 1) / 2) + 16));
-            if (!defer_bases_copy) ZSW_HIP(ctx, copy_packed_chunk(ctx, reads, 0, n, stream));
-        } else if (!defer_bases_copy) ZSW_HIP(ctx, hipMemcpyAsync(ctx->s_bases.p, reads->bases, total, hipMemcpyHostToDevice, stream));
-        st->b.bases = ctx->s_bases.as<uint8_t>();
-        st->b.offsets = nullptr;
-        st->max_len = reads->fixed_len;
-        if (reads->offsets) {
-            ZSW_HIP(ctx, ctx->s_offsets.ensure((size_t)(n + 1) * 8));
-            ZSW_HIP(ctx, hipMemcpyAsync(ctx->s_offsets.p, reads->offsets, (size_t)(n + 1) * 8, hipMemcpyHostToDevice, stream));
-            st->b.offsets = ctx->s_offsets.as<uint64_t>();
-            uint32_t m = 0;
-            for (uint32_t i = 0; i < n; ++i) {
-                if (reads->offsets[i + 1] < reads->offsets[i]) return fail(ctx, ZSW_ERR_INVALID_ARGUMENT, "offsets not monotone");
-                m = std::max<uint32_t>(m, (uint32_t)(reads->offsets[i + 1] - reads->offsets[i]));
-            }
-            st->max_len = m;
-        }
-        ZSW_HIP(ctx, ctx->s_score.ensure((size_t)n * 4 + 4));
-        ZSW_HIP(ctx, ctx->s_status.ensure((size_t)n + 4));
-        st->d_score = ctx->s_score.as<uint32_t>();
-        st->d_status = ctx->s_status.as<uint8_t>();
-        if (want_tier && out_tier) {
-            ZSW_HIP(ctx, ctx->s_tier.ensure((size_t)n + 4));
-            st->d_tier = ctx->s_tier.as<uint8_t>();
-        }
-        if (want_ends) {
-            ZSW_HIP(ctx, ctx->s_rend.ensure((size_t)n * 4 + 4));
-            ZSW_HIP(ctx, ctx->s_qend.ensure((size_t)n * 4 + 4));
-            st->d_rend = ctx->s_rend.as<uint32_t>();
-            st->d_qend = ctx->s_qend.as<uint32_t>();
-        }
-    } else {
-        st->b.bases = reads->bases;
-        st->b.offsets = reads->offsets;
-        st->max_len = reads->fixed_len;
-        if (reads->offsets && n) {
-            ZSW_HIP(ctx, ctx->d_maxlen.ensure(4));
-            ZSW_HIP(ctx, hipMemsetAsync(ctx->d_maxlen.p, 0, 4, stream));
-            hipLaunchKernelGGL(maxlen_kernel, dim3(std::min<uint32_t>(1024, (n + 255) / 256)), dim3(256), 0, stream,
-                               reads->offsets, n, ctx->d_maxlen.as<uint32_t>());
-            uint32_t m = 0;
-            ZSW_HIP(ctx, hipMemcpyAsync(&m, ctx->d_maxlen.p, 4, hipMemcpyDeviceToHost, stream));
-            ZSW_HIP(ctx, hipStreamSynchronize(stream));
-            st->max_len = m;
-        }
-        st->d_score = out_score;
-        st->d_status = out_status;
-        st->d_tier = want_tier ? out_tier : nullptr;
-        st->d_rend = out_rend;
-        st->d_qend = out_qend;
+    return ZSW_OK;
+}
+
+// step 2, a host batch: bases and offsets to the staging buffers, the longest read, staging for the results the caller wants
+static zsw_error upload_host_batch(zsw_context* ctx, const zsw_batch* reads, const ScoreDest* dest, hipStream_t stream, Staged* st, bool defer_bases_copy) {
+    const uint32_t n = st->b.n_reads;
+    size_t total = reads->offsets ? (size_t)reads->offsets[n] : (size_t)n * reads->fixed_len;
+    ZSW_HIP(ctx, ctx->s_bases.ensure(total + 16));
+    if (reads->encoding == ZSW_ENCODING_PACKED4) {  // half the bytes cross PCIe; the device spells them out as bytes again (one representative byte per residue index)
+        ZSW_HIP(ctx, ctx->s_packed.ensure((size_t)n * ((reads->fixed_len + 1) / 2) + 16));
+        if (!defer_bases_copy) ZSW_HIP(ctx, copy_packed_chunk(ctx, reads, 0, n, stream));
+    } else if (!defer_bases_copy) ZSW_HIP(ctx, hipMemcpyAsync(ctx->s_bases.p, reads->bases, total, hipMemcpyHostToDevice, stream));
+    st->b.bases = ctx->s_bases.as<uint8_t>();
+    st->b.offsets = nullptr;
+    st->max_len = reads->fixed_len;
+    if (reads->offsets) {
+        ZSW_HIP(ctx, ctx->s_offsets.ensure((size_t)(n + 1) * 8));
+        ZSW_HIP(ctx, hipMemcpyAsync(ctx->s_offsets.p, reads->offsets, (size_t)(n + 1) * 8, hipMemcpyHostToDevice, stream));
+        st->b.offsets = ctx->s_offsets.as<uint64_t>();
+        if (!offsets_monotone(reads->offsets, n, &st->max_len)) return fail(ctx, ZSW_ERR_INVALID_ARGUMENT, "offsets not monotone");
     }
-    // workspace
+    if (!dest) return ZSW_OK;  // the results stay in library workspace: nothing reads a staged score or status
+    ZSW_HIP(ctx, ctx->s_score.ensure((size_t)n * 4 + 4));
+    ZSW_HIP(ctx, ctx->s_status.ensure((size_t)n + 4));
+    st->dev.score = ctx->s_score.as<uint32_t>();
+    st->dev.status = ctx->s_status.as<uint8_t>();
+    if (dest->tier) {
+        ZSW_HIP(ctx, ctx->s_tier.ensure((size_t)n + 4));
+        st->dev.tier = ctx->s_tier.as<uint8_t>();
+    }
+    if (dest->ends()) {
+        ZSW_HIP(ctx, ctx->s_rend.ensure((size_t)n * 4 + 4));
+        ZSW_HIP(ctx, ctx->s_qend.ensure((size_t)n * 4 + 4));
+        st->dev.ref_end = ctx->s_rend.as<uint32_t>();
+        st->dev.query_end = ctx->s_qend.as<uint32_t>();
+    }
+    return ZSW_OK;
+}
+
+// step 2, a device batch: the caller's arrays as they are; the longest read of a ragged batch comes back from the device
+static zsw_error adopt_device_batch(zsw_context* ctx, const zsw_batch* reads, const ScoreDest* dest, hipStream_t stream, Staged* st) {
+    const uint32_t n = st->b.n_reads;
+    st->b.bases = reads->bases;
+    st->b.offsets = reads->offsets;
+    st->max_len = reads->fixed_len;
+    if (reads->offsets && n) {
+        ZSW_HIP(ctx, ctx->d_maxlen.ensure(4));
+        ZSW_HIP(ctx, hipMemsetAsync(ctx->d_maxlen.p, 0, 4, stream));
+        hipLaunchKernelGGL(maxlen_kernel, dim3(std::min<uint32_t>(1024, (n + 255) / 256)), dim3(256), 0, stream,
+                           reads->offsets, n, ctx->d_maxlen.as<uint32_t>());
+        uint32_t m = 0;
+        ZSW_HIP(ctx, hipMemcpyAsync(&m, ctx->d_maxlen.p, 4, hipMemcpyDeviceToHost, stream));
+        ZSW_HIP(ctx, hipStreamSynchronize(stream));
+        st->max_len = m;
+    }
+    if (dest) st->dev = *dest;
+    return ZSW_OK;
+}
+
+// step 3: the workspace every score launch may use (ScoreWorkspace), and the counters of ZSW_OPTION_MIN_SCORE
+static zsw_error common_score_workspace(zsw_context* ctx, const Against& t, const zsw_batch* reads, hipStream_t stream, Staged* st) {
+    const uint32_t n = st->b.n_reads;
     ZSW_HIP(ctx, ctx->d_fb_list.ensure((size_t)n * 4 + 4));
     ZSW_HIP(ctx, ctx->d_fb_count.ensure(4));
     if (reads->offsets || st->max_len > LONGEST_STRIP) ZSW_HIP(ctx, ctx->d_bucket_items.ensure((size_t)n * 4 + 4));
@@ -177,78 +173,80 @@ zsw_error stage(zsw_context* ctx, const zsw_batch* reads, hipStream_t stream, bo
         }
     }
     if (st->max_len > LONGEST_STRIP) {  // tile-by-tile scoring of long reads: boundary buffers for as many read pairs as 1 GiB holds
-        const size_t per_pair = std::max<size_t>(ctx->ref_len, 1) * 8, pairs = ((size_t)n + 1) / 2;
+        const size_t per_pair = std::max<size_t>(t.len, 1) * 8, pairs = ((size_t)n + 1) / 2;
         const size_t want = 2 * std::min<size_t>(pairs * per_pair, std::max<size_t>(per_pair, size_t(512) << 20));
         ZSW_HIP(ctx, ctx->d_tile_buf.ensure(want));
         ZSW_HIP(ctx, ctx->d_tile_state.ensure((size_t)n * 16 + 16));
     }
     ZSW_HIP(ctx, ctx->d_bucket_counts.ensure(64 * 4));
-    ctx->min_counts_valid = ctx->min_score != 0;
+    st->plan.min_counts = ctx->min_score != 0;
     if (ctx->min_score) {  // ZSW_OPTION_MIN_SCORE: the counters of zsw_min_score_counts for this call
         ZSW_HIP(ctx, ctx->d_min_counts.ensure(4 * 4));
         ZSW_HIP(ctx, hipMemsetAsync(ctx->d_min_counts.p, 0, 4 * 4, stream));
     }
-    ctx->prune_chunk = 0;
-    ctx->seed_ready = false;
-    ctx->chunk_ready = false;
-    const uint32_t flags = ctx->flags();
+    return ZSW_OK;
+}
+
+// step 4, the seeded exact pass: index of the target (first use after a change of sequence or matrix), 28 bytes + 4 bits per base
+// of workspace per read, the banded kernel's strip-boundary buffers and the worklist of the reads it hands back. If the device cannot spare them the full pass runs.
+static zsw_error plan_seeded_pass(zsw_context* ctx, const Against& t, const zsw_batch* reads, hipStream_t stream, Staged* st) {
+    const uint32_t n = st->b.n_reads, flags = ctx->flags();
     const bool any_size = (flags & ZSW_DEBUG_SCORE_PRUNE_ANY_SIZE) != 0;
-    // a shared-role call (zsw_capi_shared.hip) scores the reads against the profile sequence with the roles swapped and the matrix
-    // transposed: its index is seed_shared, over h_pseq
-    const bool shared = ctx->shared_call;
-    const size_t seq_len = shared ? ctx->pseq_len : ctx->ref_len;
-    if ((!shared || ctx->shared_seedable) && (flags & ZSW_DEBUG_SCORE_PRUNE) && !(flags & ZSW_DEBUG_PRUNE_STRIP) && n > 0 && (n >= SEED_MIN_READS || any_size) && seq_len > 0 &&
-        st->max_len >= SEED_MIN_LEN) {
-        // the seeded exact pass: index of the reference (first use after a change of reference or matrix), 28 bytes + 4 bits per base
-        // of workspace per read, the banded kernel's strip-boundary buffers and the worklist of the reads it hands back. If the device cannot spare them the full pass runs.
-        SeedIndex& index = shared ? ctx->seed_shared : ctx->seed;
-        if (!index.valid) {
-            const uint8_t* seq = shared ? ctx->h_pseq.data() : ctx->h_ref.data();
-            ZSW_HIP(ctx, seed_index_update(&index, shared ? ctx->h_sc_t : ctx->h_sc, seq, seq_len));
+    if (!(flags & ZSW_DEBUG_SCORE_PRUNE) || (flags & ZSW_DEBUG_PRUNE_STRIP) || n == 0 || !(n >= SEED_MIN_READS || any_size) || t.len == 0 ||
+        st->max_len < SEED_MIN_LEN)
+        return ZSW_OK;
+    if (!t.index->valid) ZSW_HIP(ctx, seed_index_update(t.index, *t.h_sc, t.h_seq, t.len));
+    if (!t.index->usable) return ZSW_OK;
+    // ragged batches: a region per length class (the banded pass's buffers are sized per region, by the reads in it)
+    // (ragged: the classes' sort temporaries and round-ups, and SEED_BAND_CLASS_MIN_GRID blocks of boundary buffer each)
+    const size_t want = seed_workspace_bytes(n, st->max_len) + 24 * seed_workspace_bytes(0, st->max_len) +
+                        (reads->offsets ? 24 * seed_workspace_bytes(std::min<uint32_t>(n, 2 * SEED_BAND_CLASS_MIN_GRID * 256), st->max_len, SEED_BAND_CLASS_MIN_GRID) : 0);
+    if (ctx->d_seed_work.ensure(want) == hipSuccess && ctx->d_seed_gtab.ensure(2 * (t.len + 2 * SEED_GTAB_PAD) * 8) == hipSuccess &&
+        ctx->d_prune_list.ensure((size_t)n * 4 + 4) == hipSuccess &&
+        ctx->d_prune_count.ensure(64 * 4) == hipSuccess) {
+        ZSW_HIP(ctx, hipMemsetAsync(ctx->d_prune_count.p, 0, 64 * 4, stream));  // [1] the call's total, [0], [2..] lists in flight
+        st->plan.seed = t.index;
+        // long references: the reads handed back are scored in chunks of rows (one key per read collects the chunks' results)
+        if (t.len >= 8192) {
+            st->plan.chunk_keys = ctx->d_chunk_keys.ensure((size_t)n * 8 + 8) == hipSuccess;
+            if (!st->plan.chunk_keys) (void)hipGetLastError();
         }
-        if (index.usable) {
-            // ragged batches: a region per length class (the banded pass's buffers are sized per region, by the reads in it)
-            // (ragged: the classes' sort temporaries and round-ups, and SEED_BAND_CLASS_MIN_GRID blocks of boundary buffer each)
-            const size_t want = seed_workspace_bytes(n, st->max_len) + 24 * seed_workspace_bytes(0, st->max_len) +
-                                (reads->offsets ? 24 * seed_workspace_bytes(std::min<uint32_t>(n, 2 * SEED_BAND_CLASS_MIN_GRID * 256), st->max_len, SEED_BAND_CLASS_MIN_GRID) : 0);
-            if (ctx->d_seed_work.ensure(want) == hipSuccess && ctx->d_seed_gtab.ensure(2 * (seq_len + 2 * SEED_GTAB_PAD) * 8) == hipSuccess &&
-                ctx->d_prune_list.ensure((size_t)n * 4 + 4) == hipSuccess &&
-                ctx->d_prune_count.ensure(64 * 4) == hipSuccess) {
-                ZSW_HIP(ctx, hipMemsetAsync(ctx->d_prune_count.p, 0, 64 * 4, stream));  // [1] the call's total, [0], [2..] lists in flight
-                ctx->seed_ready = true;
-                // long references: the reads handed back are scored in chunks of rows (one key per read collects the chunks' results)
-                if (seq_len >= 8192) {
-                    ctx->chunk_ready = ctx->d_chunk_keys.ensure((size_t)n * 8 + 8) == hipSuccess;
-                    if (!ctx->chunk_ready) (void)hipGetLastError();
-                }
-            } else {
-                (void)hipGetLastError();
-                ctx->d_seed_work.release();
-                ctx->err = "seeded pass skipped: workspace allocation failed (every cell is computed instead)";
-            }
-        }
+    } else {
+        (void)hipGetLastError();
+        ctx->d_seed_work.release();
+        ctx->err = "seeded pass skipped: workspace allocation failed (every cell is computed instead)";
     }
-    // the column-pruned pass (strip + window): the default first pass of 8..32-letter alphabets (the seeded pass's k-mer argument
-    // needs substitutions that cost something: it serves the 5-letter tables), a cross-check for the others (ZSW_DEBUG_PRUNE_STRIP)
+    return ZSW_OK;
+}
+
+// step 5, the column-pruned pass (strip + window): the default first pass of 8..32-letter alphabets (the seeded pass's k-mer argument
+// needs substitutions that cost something: it serves the 5-letter tables), a cross-check for the others (ZSW_DEBUG_PRUNE_STRIP)
+static zsw_error plan_pruned_pass(zsw_context* ctx, const Against& t, const zsw_batch* reads, hipStream_t stream, Staged* st) {
+    const uint32_t n = st->b.n_reads, flags = ctx->flags();
+    const bool any_size = (flags & ZSW_DEBUG_SCORE_PRUNE_ANY_SIZE) != 0;
     const bool wide_alphabet = ctx->h_sc.S > 7 && ctx->h_sc.S <= 32 && !(flags & ZSW_DEBUG_NO_WIDE);
-    if (!ctx->shared_call && (flags & ZSW_DEBUG_SCORE_PRUNE) && ((flags & ZSW_DEBUG_PRUNE_STRIP) || wide_alphabet) && n > 0 && (n >= PR_MIN_READS || any_size) &&
-        ctx->ref_len > 0 && (reads->offsets ? st->max_len > 64 : prune_class_for(st->max_len) >= 0)) {
-        const uint32_t chunk = prune_chunk_reads((uint32_t)n, (uint32_t)ctx->ref_len);
-        // a reference so long that the boundary streams of a round's reads no longer fill the chip: the full pass
-        if (chunk >= std::min<uint32_t>((uint32_t)n, PR_MIN_READS) || any_size) {
-            // the workspace is large (8 B per read pair and reference row): if the device cannot spare it, the full pass runs
-            if (ctx->d_prune.ensure(prune_workspace_bytes(chunk, (uint32_t)ctx->ref_len)) == hipSuccess &&
-                ctx->d_prune_list.ensure((size_t)n * 4 + 4) == hipSuccess && ctx->d_prune_count.ensure(64 * 4) == hipSuccess) {
-                ZSW_HIP(ctx, hipMemsetAsync(ctx->d_prune_count.p, 0, 64 * 4, stream));  // [0] the class in flight, [1] the call's total
-                ctx->prune_chunk = chunk;
-            } else {
-                (void)hipGetLastError();
-                ctx->d_prune.release();
-                ctx->err = "column-pruned pass skipped: workspace allocation failed (every cell is computed instead)";
-            }
-        }
+    if (!t.may_prune || !(flags & ZSW_DEBUG_SCORE_PRUNE) || !((flags & ZSW_DEBUG_PRUNE_STRIP) || wide_alphabet) || n == 0 || !(n >= PR_MIN_READS || any_size) ||
+        t.len == 0 || !(reads->offsets ? st->max_len > 64 : prune_class_for(st->max_len) >= 0))
+        return ZSW_OK;
+    const uint32_t chunk = prune_chunk_reads(n, (uint32_t)t.len);
+    // a reference so long that the boundary streams of a round's reads no longer fill the chip: the full pass
+    if (!(chunk >= std::min<uint32_t>(n, PR_MIN_READS) || any_size)) return ZSW_OK;
+    // the workspace is large (8 B per read pair and reference row): if the device cannot spare it, the full pass runs
+    if (ctx->d_prune.ensure(prune_workspace_bytes(chunk, (uint32_t)t.len)) == hipSuccess &&
+        ctx->d_prune_list.ensure((size_t)n * 4 + 4) == hipSuccess && ctx->d_prune_count.ensure(64 * 4) == hipSuccess) {
+        ZSW_HIP(ctx, hipMemsetAsync(ctx->d_prune_count.p, 0, 64 * 4, stream));  // [0] the class in flight, [1] the call's total
+        st->plan.prune_chunk = chunk;
+    } else {
+        (void)hipGetLastError();
+        ctx->d_prune.release();
+        ctx->err = "column-pruned pass skipped: workspace allocation failed (every cell is computed instead)";
     }
-    uint32_t need = std::max<uint32_t>(512, (st->max_len + 127) / 128 * 128);
+    return ZSW_OK;
+}
+
+// step 6: the rows of the exact 32-bit kernel
+static zsw_error exact_kernel_scratch(zsw_context* ctx, uint32_t max_len) {
+    uint32_t need = std::max<uint32_t>(512, (max_len + 127) / 128 * 128);
     if (need > ctx->scratch_len || !ctx->d_scratch.p) {
         // slots from a byte budget: 16,384 for reads up to 8 kb, down to 64 for genome-sized reads (2 rows of `need` ints per slot)
         size_t slots = EXACT_SCRATCH_BUDGET / (2 * (size_t)need * sizeof(int32_t)) / 64 * 64;
@@ -260,27 +258,38 @@ zsw_error stage(zsw_context* ctx, const zsw_batch* reads, hipStream_t stream, bo
     return ZSW_OK;
 }
 
-zsw_error stage_reads(zsw_context* ctx, const zsw_batch* reads, hipStream_t stream, Staged* st) {
-    uint32_t dummy_score = 0;
-    uint8_t dummy_status = 0;
-    const zsw_error ze = stage(ctx, reads, stream, false, false, &dummy_score, &dummy_status, nullptr, nullptr, nullptr, st);
-    st->d_score = nullptr;  // (a device batch's result arrays were the dummies, which go out of scope here)
-    st->d_status = nullptr;
-    return ze;
+// Brings a batch to the device (or validates device pointers), finds the longest read, sizes the workspace and plans the call's
+// passes: a function of its arguments and of the context's configuration and buffers.
+zsw_error stage(zsw_context* ctx, const Against& t, const zsw_batch* reads, const ScoreDest* dest, hipStream_t stream, Staged* st, bool defer_bases_copy) {
+    if (!ctx) return ZSW_ERR_INVALID_ARGUMENT;
+    ctx->score_launches.clear();  // zsw_debug_score_launches reports the launches of this call
+    zsw_error ze = check_batch(ctx, t, reads, dest);
+    if (ze != ZSW_OK) return ze;
+    ZSW_HIP(ctx, hipSetDevice(ctx->device));
+    *st = Staged{};
+    st->b.n_reads = st->b.n_items = (uint32_t)reads->n_reads;
+    st->b.fixed_len = reads->fixed_len;
+    ze = reads->mem == ZSW_MEM_HOST ? upload_host_batch(ctx, reads, dest, stream, st, defer_bases_copy) : adopt_device_batch(ctx, reads, dest, stream, st);
+    if (ze == ZSW_OK) ze = common_score_workspace(ctx, t, reads, stream, st);
+    if (ze == ZSW_OK) ze = plan_seeded_pass(ctx, t, reads, stream, st);
+    if (ze == ZSW_OK) ze = plan_pruned_pass(ctx, t, reads, stream, st);
+    if (ze != ZSW_OK) return ze;
+    ctx->last.handbacks_counted = st->plan.seed || st->plan.prune_chunk;
+    ctx->last.min_counts_valid = st->plan.min_counts;
+    return exact_kernel_scratch(ctx, st->max_len);
 }
 
-zsw_error stage_align(zsw_context* ctx, const zsw_batch* reads, zsw_alignment* out_aln, uint8_t* out_status, uint32_t* out_inc, uint8_t* out_op,
-                      uint64_t ciglet_cap, uint64_t* out_n_ciglets, hipStream_t stream, Staged* st) {
+zsw_error stage_align(zsw_context* ctx, const Against& t, const zsw_batch* reads, const AlignDest& dest, hipStream_t stream, Staged* st) {
     if (!ctx) return ZSW_ERR_INVALID_ARGUMENT;
-    if (!reads || !out_aln || !out_status || !out_n_ciglets || (ciglet_cap && (!out_inc || !out_op)))
+    if (!reads || !dest.aln || !dest.status || !dest.n_ciglets || (dest.ciglet_cap && (!dest.inc || !dest.op)))
         return fail(ctx, ZSW_ERR_INVALID_ARGUMENT, "null argument");
-    const zsw_error ze = stage_reads(ctx, reads, stream, st);
+    const zsw_error ze = stage(ctx, t, reads, nullptr, stream, st);
     if (ze != ZSW_OK) return ze;
-    *out_n_ciglets = 0;
+    *dest.n_ciglets = 0;
     return ZSW_OK;
 }
 
-ScoreWorkspace score_ws(zsw_context* ctx) {
+ScoreWorkspace score_ws(zsw_context* ctx, const Staged& st) {
     ScoreWorkspace w;
     w.scratch = ctx->d_scratch.as<int32_t>();
     w.slots = ctx->exact_slots;
@@ -293,40 +302,39 @@ ScoreWorkspace score_ws(zsw_context* ctx) {
     w.side = ctx->side;
     w.debug = ctx->flags();
     w.launch_log = &ctx->score_launches;
-    if (ctx->min_score && ctx->min_counts_valid) {
+    if (ctx->min_score && st.plan.min_counts) {
         w.min_score = ctx->min_score;
         w.min_counts = ctx->d_min_counts.as<uint32_t>();
     }
-    if (ctx->seed_ready) {
-        w.seed = ctx->shared_call ? &ctx->seed_shared : &ctx->seed;
+    if (st.plan.seed) {
+        w.seed = st.plan.seed;
         w.seed_work = ctx->d_seed_work.as<uint8_t>();
         w.seed_bytes = ctx->d_seed_work.cap;
         w.seed_gtab = ctx->d_seed_gtab.as<uint2>();
         w.band_dbg = ctx->band_dbg;
-        w.chunk_keys = ctx->chunk_ready ? ctx->d_chunk_keys.as<unsigned long long>() : nullptr;
+        w.chunk_keys = st.plan.chunk_keys ? ctx->d_chunk_keys.as<unsigned long long>() : nullptr;
         w.window_timer = &ctx->timer_window;
+    }
+    if (st.plan.seed || st.plan.prune_chunk) {
         w.prune_fail_list = ctx->d_prune_list.as<uint32_t>();
         w.prune_fail_count = ctx->d_prune_count.as<uint32_t>();
     }
-    if (ctx->prune_chunk) {
+    if (st.plan.prune_chunk) {
         w.prune_work = ctx->d_prune.as<uint8_t>();
         w.prune_bytes = ctx->d_prune.cap;
-        w.prune_chunk = ctx->prune_chunk;
-        w.prune_fail_list = ctx->d_prune_list.as<uint32_t>();
-        w.prune_fail_count = ctx->d_prune_count.as<uint32_t>();
+        w.prune_chunk = st.plan.prune_chunk;
     }
     return w;
 }
 
-zsw_error unstage(zsw_context* ctx, const zsw_batch* reads, hipStream_t stream, const Staged& st, uint32_t* out_score,
-                  uint8_t* out_status, uint8_t* out_tier, uint32_t* out_rend, uint32_t* out_qend) {
+zsw_error unstage(zsw_context* ctx, const zsw_batch* reads, hipStream_t stream, const Staged& st, const ScoreDest& dest) {
     if (reads->mem != ZSW_MEM_HOST) return ZSW_OK;
     const size_t n = reads->n_reads;
-    ZSW_HIP(ctx, hipMemcpyAsync(out_score, st.d_score, n * 4, hipMemcpyDeviceToHost, stream));
-    ZSW_HIP(ctx, hipMemcpyAsync(out_status, st.d_status, n, hipMemcpyDeviceToHost, stream));
-    if (st.d_tier && out_tier) ZSW_HIP(ctx, hipMemcpyAsync(out_tier, st.d_tier, n, hipMemcpyDeviceToHost, stream));
-    if (st.d_rend && out_rend) ZSW_HIP(ctx, hipMemcpyAsync(out_rend, st.d_rend, n * 4, hipMemcpyDeviceToHost, stream));
-    if (st.d_qend && out_qend) ZSW_HIP(ctx, hipMemcpyAsync(out_qend, st.d_qend, n * 4, hipMemcpyDeviceToHost, stream));
+    ZSW_HIP(ctx, hipMemcpyAsync(dest.score, st.dev.score, n * 4, hipMemcpyDeviceToHost, stream));
+    ZSW_HIP(ctx, hipMemcpyAsync(dest.status, st.dev.status, n, hipMemcpyDeviceToHost, stream));
+    if (st.dev.tier && dest.tier) ZSW_HIP(ctx, hipMemcpyAsync(dest.tier, st.dev.tier, n, hipMemcpyDeviceToHost, stream));
+    if (st.dev.ref_end && dest.ref_end) ZSW_HIP(ctx, hipMemcpyAsync(dest.ref_end, st.dev.ref_end, n * 4, hipMemcpyDeviceToHost, stream));
+    if (st.dev.query_end && dest.query_end) ZSW_HIP(ctx, hipMemcpyAsync(dest.query_end, st.dev.query_end, n * 4, hipMemcpyDeviceToHost, stream));
     ZSW_HIP(ctx, hipStreamSynchronize(stream));
     return ZSW_OK;
 }
@@ -334,31 +342,23 @@ zsw_error unstage(zsw_context* ctx, const zsw_batch* reads, hipStream_t stream, 
 constexpr uint32_t PIPE_CHUNK = 4'000'000;  // reads per chunk of the host-batch pipeline (600 MB at 150 bp; fewer, larger chunks keep the kernels near their large-batch rate)
 constexpr uint32_t PIPE_FIRST = 500'000;    // ... and of its first chunk, whose copy nothing hides
 
-zsw_error run_score(zsw_context* ctx, const zsw_batch* reads, const ResultRule& rule, bool want_ends, uint32_t* out_score,
-                    uint8_t* out_status, uint8_t* out_tier, uint32_t* out_rend, uint32_t* out_qend, void* stream_) {
+zsw_error run_score(zsw_context* ctx, const zsw_batch* reads, const ResultRule& rule, const ScoreDest& dest, void* stream_) {
     DeviceGuard device_guard(ctx);
     hipStream_t stream = (hipStream_t)stream_;
     Staged st;
     // fixed-length host batches of more than one chunk: the H2D copy of chunk k+1 overlaps the kernel of chunk k
     const bool pipelined = reads && reads->mem == ZSW_MEM_HOST && !reads->offsets && reads->fixed_len > 0 &&
                            reads->n_reads > PIPE_CHUNK && !(ctx && (ctx->flags() & ZSW_DEBUG_NO_PIPELINE));
-    zsw_error ze = stage(ctx, reads, stream, out_tier != nullptr, want_ends, out_score, out_status, out_tier, out_rend,
-                         out_qend, &st, pipelined);
+    zsw_error ze = stage(ctx, against_reference(ctx), reads, &dest, stream, &st, pipelined);
     if (ze != ZSW_OK) return ze;
     if (reads->n_reads == 0) return ZSW_OK;
-    ScoreOut out;
-    out.score = st.d_score;
-    out.status = st.d_status;
-    out.tier = st.d_tier;
-    out.ref_end = st.d_rend;
-    out.query_end = st.d_qend;
-    out.fb_list = ctx->d_fb_list.as<uint32_t>();
-    out.fb_count = ctx->d_fb_count.as<uint32_t>();
+    const ScoreOut out = score_out(ctx, st.dev);
+    const int mode = dest.ends() ? 2 : 0;
     if (!pipelined) {
         hipError_t e = launch_score(ctx->d_sc.as<ScoringDev>(), ctx->h_sc, st.b, st.max_len, ctx->d_ref.as<uint8_t>(),
-                                    (uint32_t)ctx->ref_len, rule, out, score_ws(ctx), stream, &ctx->timer, want_ends ? 2 : 0);
+                                    (uint32_t)ctx->ref_len, rule, out, score_ws(ctx, st), stream, &ctx->timer, mode);
         if (e != hipSuccess) return fail(ctx, ZSW_ERR_HIP, "score launch", e);
-        return unstage(ctx, reads, stream, st, out_score, out_status, out_tier, out_rend, out_qend);
+        return unstage(ctx, reads, stream, st, dest);
     }
     // chunks: a small first one (its copy is the only one nothing hides), then PIPE_CHUNK reads each. Packed reads (half the bytes: the
     // kernels of a chunk take about as long as the copy of the next one, twice as large) grow 0.5 - 1 - 2 - 4 M instead, so the device
@@ -388,11 +388,11 @@ zsw_error run_score(zsw_context* ctx, const zsw_batch* reads, const ResultRule& 
         const size_t first = starts[k], cnt = starts[k + 1] - starts[k];
         hipError_t e = hipEventRecord(ctx->copy_events[n_chunks + k], stream);
         if (e == hipSuccess) e = hipStreamWaitEvent(ctx->copy_stream, ctx->copy_events[n_chunks + k], 0);
-        if (e == hipSuccess) e = hipMemcpyAsync(out_score + first, st.d_score + first, cnt * 4, hipMemcpyDeviceToHost, ctx->copy_stream);
-        if (e == hipSuccess) e = hipMemcpyAsync(out_status + first, st.d_status + first, cnt, hipMemcpyDeviceToHost, ctx->copy_stream);
-        if (e == hipSuccess && st.d_tier && out_tier) e = hipMemcpyAsync(out_tier + first, st.d_tier + first, cnt, hipMemcpyDeviceToHost, ctx->copy_stream);
-        if (e == hipSuccess && st.d_rend && out_rend) e = hipMemcpyAsync(out_rend + first, st.d_rend + first, cnt * 4, hipMemcpyDeviceToHost, ctx->copy_stream);
-        if (e == hipSuccess && st.d_qend && out_qend) e = hipMemcpyAsync(out_qend + first, st.d_qend + first, cnt * 4, hipMemcpyDeviceToHost, ctx->copy_stream);
+        if (e == hipSuccess) e = hipMemcpyAsync(dest.score + first, out.score + first, cnt * 4, hipMemcpyDeviceToHost, ctx->copy_stream);
+        if (e == hipSuccess) e = hipMemcpyAsync(dest.status + first, out.status + first, cnt, hipMemcpyDeviceToHost, ctx->copy_stream);
+        if (e == hipSuccess && out.tier && dest.tier) e = hipMemcpyAsync(dest.tier + first, out.tier + first, cnt, hipMemcpyDeviceToHost, ctx->copy_stream);
+        if (e == hipSuccess && out.ref_end && dest.ref_end) e = hipMemcpyAsync(dest.ref_end + first, out.ref_end + first, cnt * 4, hipMemcpyDeviceToHost, ctx->copy_stream);
+        if (e == hipSuccess && out.query_end && dest.query_end) e = hipMemcpyAsync(dest.query_end + first, out.query_end + first, cnt * 4, hipMemcpyDeviceToHost, ctx->copy_stream);
         return e;
     };
     ZSW_HIP(ctx, copy_chunk(0));
@@ -409,7 +409,7 @@ zsw_error run_score(zsw_context* ctx, const zsw_batch* reads, const ResultRule& 
         if (out.ref_end) ok.ref_end = out.ref_end + first;
         if (out.query_end) ok.query_end = out.query_end + first;
         hipError_t e = launch_score(ctx->d_sc.as<ScoringDev>(), ctx->h_sc, bk, st.max_len, ctx->d_ref.as<uint8_t>(),
-                                    (uint32_t)ctx->ref_len, rule, ok, score_ws(ctx), stream, &ctx->timer, want_ends ? 2 : 0);
+                                    (uint32_t)ctx->ref_len, rule, ok, score_ws(ctx, st), stream, &ctx->timer, mode);
         if (e != hipSuccess) return fail(ctx, ZSW_ERR_HIP, "score launch", e);
         if (k + 1 < n_chunks) ZSW_HIP(ctx, copy_chunk(k + 1));  // issued after the launch: it runs under chunk k's kernel
         ZSW_HIP(ctx, results_back(k));
@@ -448,7 +448,7 @@ __global__ void ranges_combine_kernel(uint32_t n, const uint32_t* fscore, const 
 
 // can this call's batch take the reverse pass of the ranges as a second seeded pass (stage() has run)?
 static bool seeded_reverse_possible(zsw_context* ctx, const Staged& st) {
-    return ctx->seed_ready && !ctx->shared_call && !(ctx->flags() & ZSW_DEBUG_RANGES_EXACT_REVERSE) && ctx->ref_len > 0 && ctx->seed.valid && ctx->seed.usable &&
+    return st.plan.seed == &ctx->seed && !(ctx->flags() & ZSW_DEBUG_RANGES_EXACT_REVERSE) && ctx->ref_len > 0 && ctx->seed.valid && ctx->seed.usable &&
            st.max_len <= SEED_MAX_LEN;
 }
 
@@ -478,14 +478,8 @@ zsw_error ranges_device(zsw_context* ctx, const Staged& st, const ResultRule& ru
     for (int k : {RW_FSTATUS, RW_RSTATUS, RW_O5, RW_FTIER}) ZSW_HIP(ctx, ws[k].ensure((size_t)n + 4));
     ZSW_HIP(ctx, ws[RW_GTAB].ensure(ctx->ref_len * 8 + 8));
     ZSW_HIP(ctx, ws[RW_MIS].ensure(4));
-    ScoreOut fo;
-    fo.score = ws[RW_FSCORE].as<uint32_t>();
-    fo.status = ws[RW_FSTATUS].as<uint8_t>();
-    fo.tier = ws[RW_FTIER].as<uint8_t>();
-    fo.ref_end = ws[RW_FREND].as<uint32_t>();
-    fo.query_end = ws[RW_FQEND].as<uint32_t>();
-    fo.fb_list = ctx->d_fb_list.as<uint32_t>();
-    fo.fb_count = ctx->d_fb_count.as<uint32_t>();
+    ScoreOut fo = score_out(ctx, {ws[RW_FSCORE].as<uint32_t>(), ws[RW_FSTATUS].as<uint8_t>(), ws[RW_FTIER].as<uint8_t>(), ws[RW_FREND].as<uint32_t>(),
+                                  ws[RW_FQEND].as<uint32_t>()});
     // The reverse pass as a second seeded pass (as the shared role does it, zsw_capi_shared.hip): when this batch takes the seeded
     // pass, the forward pass also reports whether a read's maximum sits in ONE cell (mode 3). Then every alignment that scores it
     // ends there, i.e. lies inside the prefixes the reverse pass of striped.rs:355-388 is restricted to, and the cells of the
@@ -501,17 +495,11 @@ zsw_error ranges_device(zsw_context* ctx, const Staged& st, const ResultRule& ru
         fo.unique = ws[RW_UNIQ_F].as<uint8_t>();
     }
     hipError_t e = launch_score(ctx->d_sc.as<ScoringDev>(), ctx->h_sc, st.b, st.max_len, ctx->d_ref.as<uint8_t>(),
-                                (uint32_t)ctx->ref_len, rule, fo, score_ws(ctx), stream, nullptr, seeded_reverse ? 3 : 2);
+                                (uint32_t)ctx->ref_len, rule, fo, score_ws(ctx, st), stream, nullptr, seeded_reverse ? 3 : 2);
     if (e != hipSuccess) return fail(ctx, ZSW_ERR_HIP, "ranges forward pass", e);
     const uint32_t g256 = (n + 255) / 256;
     hipLaunchKernelGGL(ranges_prep_kernel, dim3(g256), dim3(256), 0, stream, n, fo.status, fo.query_end, ws[RW_QEM].as<uint32_t>());
-    ScoreOut ro;
-    ro.score = ws[RW_RSCORE].as<uint32_t>();
-    ro.status = ws[RW_RSTATUS].as<uint8_t>();
-    ro.ref_end = ws[RW_RRS].as<uint32_t>();
-    ro.query_end = ws[RW_RQS].as<uint32_t>();
-    ro.fb_list = ctx->d_fb_list.as<uint32_t>();
-    ro.fb_count = ctx->d_fb_count.as<uint32_t>();
+    const ScoreOut ro = score_out(ctx, {ws[RW_RSCORE].as<uint32_t>(), ws[RW_RSTATUS].as<uint8_t>(), nullptr, ws[RW_RRS].as<uint32_t>(), ws[RW_RQS].as<uint32_t>()});
     BatchDev rest = st.b;
     bool run_exact = true;
     if (seeded_reverse) {
@@ -532,7 +520,7 @@ zsw_error ranges_device(zsw_context* ctx, const Staged& st, const ResultRule& ru
             // the exact reverse kernel walks a read's prefixes for what the second tier costs per read, and always answers; only the
             // certificate of run_align, whose unsettled reads take the literal second pass, is worth the second tier
             o3.narrow_only = cert == nullptr;
-            ScoreWorkspace w = score_ws(ctx);
+            ScoreWorkspace w = score_ws(ctx, st);
             w.seed = &ctx->seed_rev;
             w.band_dbg = nullptr;
             w.min_score = 0;  // ZSW_OPTION_MIN_SCORE applies to the forward pass; a read below it is not SOME and nothing reads its reverse pass
@@ -558,7 +546,7 @@ zsw_error ranges_device(zsw_context* ctx, const Staged& st, const ResultRule& ru
     }
     if (run_exact) {
         e = launch_score_rev(ctx->d_sc.as<ScoringDev>(), ctx->h_sc, rest, st.max_len, ctx->d_ref.as<uint8_t>(), (uint32_t)ctx->ref_len,
-                             rule, ro, score_ws(ctx), fo.ref_end, ws[RW_QEM].as<uint32_t>(), fo.score, ws[RW_GTAB].as<uint2>(), stream);
+                             rule, ro, score_ws(ctx, st), fo.ref_end, ws[RW_QEM].as<uint32_t>(), fo.score, ws[RW_GTAB].as<uint2>(), stream);
         if (e != hipSuccess) return fail(ctx, ZSW_ERR_HIP, "ranges reverse pass", e);
     }
     out->score = ws[RW_O0].as<uint32_t>();
@@ -576,35 +564,32 @@ zsw_error ranges_device(zsw_context* ctx, const Staged& st, const ResultRule& ru
     return ZSW_OK;
 }
 
-zsw_error copy_ranges_out(zsw_context* ctx, const RangesDev& rd, uint32_t n, bool host, uint32_t* out_score, uint32_t* out_rs, uint32_t* out_re,
-                          uint32_t* out_qs, uint32_t* out_qe, uint8_t* out_status, uint8_t* out_tier, hipStream_t stream) {
+zsw_error copy_ranges_out(zsw_context* ctx, const RangesDev& rd, uint32_t n, bool host, const RangesDev& out, hipStream_t stream) {
     const hipMemcpyKind kind = host ? hipMemcpyDeviceToHost : hipMemcpyDeviceToDevice;
-    uint32_t* outs[5] = {out_score, out_rs, out_re, out_qs, out_qe};
+    uint32_t* outs[5] = {out.score, out.rs, out.re, out.qs, out.qe};
     uint32_t* devs[5] = {rd.score, rd.rs, rd.re, rd.qs, rd.qe};
     for (int k = 0; k < 5; ++k) ZSW_HIP(ctx, hipMemcpyAsync(outs[k], devs[k], (size_t)n * 4, kind, stream));
-    ZSW_HIP(ctx, hipMemcpyAsync(out_status, rd.status, n, kind, stream));
-    if (out_tier) ZSW_HIP(ctx, hipMemcpyAsync(out_tier, rd.tier, n, kind, stream));
+    ZSW_HIP(ctx, hipMemcpyAsync(out.status, rd.status, n, kind, stream));
+    if (out.tier) ZSW_HIP(ctx, hipMemcpyAsync(out.tier, rd.tier, n, kind, stream));
     if (host) ZSW_HIP(ctx, hipStreamSynchronize(stream));
     return ZSW_OK;
 }
 
-zsw_error run_ranges(zsw_context* ctx, const zsw_batch* reads, const ResultRule& rule, uint32_t* out_score, uint32_t* out_rs,
-                     uint32_t* out_re, uint32_t* out_qs, uint32_t* out_qe, uint8_t* out_status, uint8_t* out_tier, void* stream_) {
+zsw_error run_ranges(zsw_context* ctx, const zsw_batch* reads, const ResultRule& rule, const RangesDev& out, void* stream_) {
     DeviceGuard device_guard(ctx);
     hipStream_t stream = (hipStream_t)stream_;
     if (!ctx) return ZSW_ERR_INVALID_ARGUMENT;
-    if (!reads || !out_score || !out_rs || !out_re || !out_qs || !out_qe || !out_status)
-        return fail(ctx, ZSW_ERR_INVALID_ARGUMENT, "null argument");
+    if (!reads || !out.score || !out.rs || !out.re || !out.qs || !out.qe || !out.status) return fail(ctx, ZSW_ERR_INVALID_ARGUMENT, "null argument");
     const uint32_t n = (uint32_t)reads->n_reads;
     Staged st;
-    zsw_error ze = stage_reads(ctx, reads, stream, &st);
+    zsw_error ze = stage(ctx, against_reference(ctx), reads, nullptr, stream, &st);
     if (ze != ZSW_OK || n == 0) return ze;
     RangesDev rd;
     ctx->timer.begin(stream);
     ze = ranges_device(ctx, st, rule, stream, &rd);
     ctx->timer.end(stream);
     if (ze != ZSW_OK) return ze;
-    return copy_ranges_out(ctx, rd, n, reads->mem == ZSW_MEM_HOST, out_score, out_rs, out_re, out_qs, out_qe, out_status, out_tier, stream);
+    return copy_ranges_out(ctx, rd, n, reads->mem == ZSW_MEM_HOST, out, stream);
 }
 
 
@@ -712,8 +697,7 @@ __global__ void gather_meta_kernel(BatchDev b, const uint8_t* tier, const uint32
 // Shared tail of the alignment entry points: count + scan + packed write of the ciglets (reversal and SeqSrc::Query
 // inversion happen in the writer), then the records/statuses to the caller's arrays.
 zsw_error finish_alignments(zsw_context* ctx, DevBuf* ws, uint32_t n, bool host, const uint8_t* d_status, const uint8_t* d_tier,
-                            int invert, zsw_alignment* out_aln, uint8_t* out_status, uint8_t* out_tier, uint32_t* out_inc,
-                            uint8_t* out_op, uint64_t ciglet_cap, uint64_t* out_n_ciglets, hipStream_t stream) {
+                            int invert, const AlignDest& dest, hipStream_t stream) {
     const uint32_t nblocks = (n + 1023) / 1024;
     ZSW_HIP(ctx, ws[WS_BSUMS].ensure((size_t)nblocks * 8 + 8));
     ZSW_HIP(ctx, ws[WS_TOTAL].ensure(8));
@@ -723,10 +707,10 @@ zsw_error finish_alignments(zsw_context* ctx, DevBuf* ws, uint32_t n, bool host,
     uint64_t total = 0;
     ZSW_HIP(ctx, hipMemcpyAsync(&total, ws[WS_TOTAL].p, 8, hipMemcpyDeviceToHost, stream));
     ZSW_HIP(ctx, hipStreamSynchronize(stream));
-    *out_n_ciglets = total;
-    if (total > ciglet_cap) return fail(ctx, ZSW_ERR_INVALID_ARGUMENT, "ciglet capacity too small; required size returned");
-    uint32_t* d_inc = out_inc;
-    uint8_t* d_op = out_op;
+    *dest.n_ciglets = total;
+    if (total > dest.ciglet_cap) return fail(ctx, ZSW_ERR_INVALID_ARGUMENT, "ciglet capacity too small; required size returned");
+    uint32_t* d_inc = dest.inc;
+    uint8_t* d_op = dest.op;
     if (host) {
         ZSW_HIP(ctx, ws[WS_OINC].ensure(total * 4 + 4));
         ZSW_HIP(ctx, ws[WS_OOP].ensure(total + 4));
@@ -734,15 +718,15 @@ zsw_error finish_alignments(zsw_context* ctx, DevBuf* ws, uint32_t n, bool host,
         d_op = ws[WS_OOP].as<uint8_t>();
     }
     e = align_finalize(ws[WS_ALN].as<zsw_alignment>(), d_status, n, ws[WS_BSUMS].as<uint64_t>(), ws[WS_TOTAL].as<uint64_t>(),
-                       ws[WS_CIGSTART].as<uint64_t>(), ws[WS_CIGRAW].as<uint32_t>(), invert, d_inc, d_op, ciglet_cap, false, stream);
+                       ws[WS_CIGSTART].as<uint64_t>(), ws[WS_CIGRAW].as<uint32_t>(), invert, d_inc, d_op, dest.ciglet_cap, false, stream);
     if (e != hipSuccess) return fail(ctx, ZSW_ERR_HIP, "align write", e);
     const hipMemcpyKind kind = host ? hipMemcpyDeviceToHost : hipMemcpyDeviceToDevice;
-    ZSW_HIP(ctx, hipMemcpyAsync(out_aln, ws[WS_ALN].p, (size_t)n * sizeof(zsw_alignment), kind, stream));
-    ZSW_HIP(ctx, hipMemcpyAsync(out_status, d_status, n, kind, stream));
-    if (out_tier && d_tier) ZSW_HIP(ctx, hipMemcpyAsync(out_tier, d_tier, n, kind, stream));
+    ZSW_HIP(ctx, hipMemcpyAsync(dest.aln, ws[WS_ALN].p, (size_t)n * sizeof(zsw_alignment), kind, stream));
+    ZSW_HIP(ctx, hipMemcpyAsync(dest.status, d_status, n, kind, stream));
+    if (dest.tier && d_tier) ZSW_HIP(ctx, hipMemcpyAsync(dest.tier, d_tier, n, kind, stream));
     if (host && total) {
-        ZSW_HIP(ctx, hipMemcpyAsync(out_inc, d_inc, total * 4, kind, stream));
-        ZSW_HIP(ctx, hipMemcpyAsync(out_op, d_op, total, kind, stream));
+        ZSW_HIP(ctx, hipMemcpyAsync(dest.inc, d_inc, total * 4, kind, stream));
+        ZSW_HIP(ctx, hipMemcpyAsync(dest.op, d_op, total, kind, stream));
     }
     ZSW_HIP(ctx, hipStreamSynchronize(stream));
     return ZSW_OK;
@@ -750,12 +734,11 @@ zsw_error finish_alignments(zsw_context* ctx, DevBuf* ws, uint32_t n, bool host,
 
 // lanes_w*: lane count of the profile whose width answered (direct call: the caller's N for its one width).
 zsw_error run_align(zsw_context* ctx, const zsw_batch* reads, const ResultRule& rule, int lanes_w8, int lanes_w16, int lanes_w32,
-                    int invert, zsw_alignment* out_aln, uint8_t* out_status, uint8_t* out_tier, uint32_t* out_inc,
-                    uint8_t* out_op, uint64_t ciglet_cap, uint64_t* out_n_ciglets, void* stream_) {
+                    int invert, const AlignDest& dest, void* stream_) {
     DeviceGuard device_guard(ctx);
     hipStream_t stream = (hipStream_t)stream_;
     Staged st;
-    zsw_error ze = stage_align(ctx, reads, out_aln, out_status, out_inc, out_op, ciglet_cap, out_n_ciglets, stream, &st);
+    zsw_error ze = stage_align(ctx, against_reference(ctx), reads, dest, stream, &st);
     const uint32_t n = st.b.n_reads;
     if (ze != ZSW_OK || n == 0) return ze;
     const bool host = reads->mem == ZSW_MEM_HOST;
@@ -765,13 +748,7 @@ zsw_error run_align(zsw_context* ctx, const zsw_batch* reads, const ResultRule& 
     ZSW_HIP(ctx, ws[WS_TIER].ensure((size_t)n + 4));
     ZSW_HIP(ctx, ws[WS_REND].ensure((size_t)n * 4 + 4));
     // pass 1: packed score kernel with the reference-end row (sw_simd_align's `best` and `r_end`)
-    ScoreOut so;
-    so.score = ws[WS_SCORE].as<uint32_t>();
-    so.status = ws[WS_STATUS].as<uint8_t>();
-    so.tier = ws[WS_TIER].as<uint8_t>();
-    so.ref_end = ws[WS_REND].as<uint32_t>();
-    so.fb_list = ctx->d_fb_list.as<uint32_t>();
-    so.fb_count = ctx->d_fb_count.as<uint32_t>();
+    ScoreOut so = score_out(ctx, {ws[WS_SCORE].as<uint32_t>(), ws[WS_STATUS].as<uint8_t>(), ws[WS_TIER].as<uint8_t>(), ws[WS_REND].as<uint32_t>(), nullptr});
     // the seeded first pass leaves, per read it accepts, the row from which pass 2 may start with a zero state
     ZSW_HIP(ctx, ws[WS_SAFE].ensure((size_t)n * 4 + 4));
     ZSW_HIP(ctx, hipMemsetAsync(ws[WS_SAFE].p, 0xff, (size_t)n * 4, stream));
@@ -795,7 +772,7 @@ zsw_error run_align(zsw_context* ctx, const zsw_batch* reads, const ResultRule& 
         ze = certificate_pass(ctx, st, rd, cert.settled, nullptr, 0, invert, stream, &pass2_status);
         if (ze != ZSW_OK) return ze;
     } else {
-        e = launch_score(ctx->d_sc.as<ScoringDev>(), ctx->h_sc, st.b, st.max_len, ctx->d_ref.as<uint8_t>(), (uint32_t)ctx->ref_len, rule, so, score_ws(ctx), stream,
+        e = launch_score(ctx->d_sc.as<ScoringDev>(), ctx->h_sc, st.b, st.max_len, ctx->d_ref.as<uint8_t>(), (uint32_t)ctx->ref_len, rule, so, score_ws(ctx, st), stream,
                          nullptr, 1);
         if (e != hipSuccess) return fail(ctx, ZSW_ERR_HIP, "align pass 1", e);
         pass2_status = so.status;
@@ -953,32 +930,27 @@ zsw_error run_align(zsw_context* ctx, const zsw_batch* reads, const ResultRule& 
         if (again) return fail(ctx, ZSW_ERR_HIP, "alignment traceback did not complete with the full window");
     }
 
-    return finish_alignments(ctx, ws, n, host, so.status, so.tier, invert, out_aln, out_status, out_tier, out_inc, out_op, ciglet_cap,
-                             out_n_ciglets, stream);
+    return finish_alignments(ctx, ws, n, host, so.status, so.tier, invert, dest, stream);
 }
 
 // sw_align_3pass per read (three_pass.rs:21-104): ranges on the device, then the third pass (zsw_threepass.hip)
-zsw_error run_threepass(zsw_context* ctx, const zsw_batch* reads, const ResultRule& rule, int invert, zsw_alignment* out_aln,
-                        uint8_t* out_status, uint8_t* out_tier, uint32_t* out_inc, uint8_t* out_op, uint64_t ciglet_cap,
-                        uint64_t* out_n_ciglets, void* stream_) {
+zsw_error run_threepass(zsw_context* ctx, const zsw_batch* reads, const ResultRule& rule, int invert, const AlignDest& dest, void* stream_) {
     DeviceGuard device_guard(ctx);
     hipStream_t stream = (hipStream_t)stream_;
     Staged st;
-    zsw_error ze = stage_align(ctx, reads, out_aln, out_status, out_inc, out_op, ciglet_cap, out_n_ciglets, stream, &st);
+    zsw_error ze = stage_align(ctx, against_reference(ctx), reads, dest, stream, &st);
     if (ze != ZSW_OK || reads->n_reads == 0) return ze;
     RangesDev rd;
     ctx->timer.begin(stream);
     ze = ranges_device(ctx, st, rule, stream, &rd);
     if (ze != ZSW_OK) return ze;
-    return threepass_third_pass(ctx, st, rd, nullptr, 0, reads->mem == ZSW_MEM_HOST, invert, out_aln, out_status, out_tier, out_inc, out_op, ciglet_cap,
-                                out_n_ciglets, stream);
+    return threepass_third_pass(ctx, st, rd, nullptr, 0, reads->mem == ZSW_MEM_HOST, invert, dest, stream);
 }
 
 // The third pass over ranges that are already on the device (the caller opened ctx->timer's interval). pseq: non-null = the
 // shared-profile role (ThreePassArgs::pseq).
 zsw_error threepass_third_pass(zsw_context* ctx, const Staged& st, const RangesDev& rd, const uint8_t* pseq, uint32_t pseq_len, bool host, int invert,
-                               zsw_alignment* out_aln, uint8_t* out_status, uint8_t* out_tier, uint32_t* out_inc, uint8_t* out_op, uint64_t ciglet_cap,
-                               uint64_t* out_n_ciglets, hipStream_t stream) {
+                               const AlignDest& dest, hipStream_t stream) {
     const uint32_t n = st.b.n_reads;
     DevBuf* ws = ctx->a_ws;
     ThreePassArgs a;
@@ -1042,8 +1014,7 @@ zsw_error threepass_third_pass(zsw_context* ctx, const Staged& st, const RangesD
         if (again) return fail(ctx, ZSW_ERR_HIP, "3-pass alignment did not complete with full-size resources");
     }
     ctx->timer.end(stream);
-    return finish_alignments(ctx, ws, n, host, rd.status, rd.tier, invert, out_aln, out_status, out_tier, out_inc, out_op, ciglet_cap,
-                             out_n_ciglets, stream);
+    return finish_alignments(ctx, ws, n, host, rd.status, rd.tier, invert, dest, stream);
 }
 
 hipError_t launch_ranges_prep(uint32_t n, const uint8_t* fstatus, const uint32_t* fqend, uint32_t* qe_masked, hipStream_t stream) {
@@ -1072,8 +1043,7 @@ zsw_error zsw_align_batch(zsw_context* ctx, const zsw_batch* reads, zsw_int_type
     if (zsw_error ze = min_score_unsupported(ctx, "zsw_align_batch"); ze != ZSW_OK) return ze;
     ResultRule rule;
     if (zsw_error ze = rule_direct(ctx, int_type, lanes, &rule); ze != ZSW_OK) return ze;
-    return run_align(ctx, reads, rule, lanes, lanes, lanes, invert, out_aln, out_status, nullptr, out_inc, out_op, ciglet_cap,
-                     out_n_ciglets, stream);
+    return run_align(ctx, reads, rule, lanes, lanes, lanes, invert, {out_aln, out_status, nullptr, out_inc, out_op, ciglet_cap, out_n_ciglets}, stream);
 }
 
 zsw_error zsw_align_batch_from(zsw_context* ctx, const zsw_batch* reads, int from_width, int preset_bits, int invert,
@@ -1082,8 +1052,8 @@ zsw_error zsw_align_batch_from(zsw_context* ctx, const zsw_batch* reads, int fro
     if (zsw_error ze = min_score_unsupported(ctx, "zsw_align_batch_from"); ze != ZSW_OK) return ze;
     ResultRule rule;
     if (zsw_error ze = rule_cascade(ctx, from_width, preset_bits, &rule); ze != ZSW_OK) return ze;
-    return run_align(ctx, reads, rule, preset_bits / 8, preset_bits / 16, preset_bits / 32, invert, out_aln, out_status, out_tier,
-                     out_inc, out_op, ciglet_cap, out_n_ciglets, stream);
+    return run_align(ctx, reads, rule, preset_bits / 8, preset_bits / 16, preset_bits / 32, invert,
+                     {out_aln, out_status, out_tier, out_inc, out_op, ciglet_cap, out_n_ciglets}, stream);
 }
 
 int zsw_device_count(void) {
@@ -1241,14 +1211,14 @@ zsw_error zsw_score_batch(zsw_context* ctx, const zsw_batch* reads, zsw_int_type
                           uint32_t* out_score, uint8_t* out_status, void* stream) {
     ResultRule rule;
     if (zsw_error ze = rule_direct(ctx, int_type, lanes, &rule); ze != ZSW_OK) return ze;
-    return run_score(ctx, reads, rule, false, out_score, out_status, nullptr, nullptr, nullptr, stream);
+    return run_score(ctx, reads, rule, {out_score, out_status, nullptr, nullptr, nullptr}, stream);
 }
 
 zsw_error zsw_score_batch_from(zsw_context* ctx, const zsw_batch* reads, int from_width, int preset_bits,
                                uint32_t* out_score, uint8_t* out_status, uint8_t* out_tier, void* stream) {
     ResultRule rule;
     if (zsw_error ze = rule_cascade(ctx, from_width, preset_bits, &rule); ze != ZSW_OK) return ze;
-    return run_score(ctx, reads, rule, false, out_score, out_status, out_tier, nullptr, nullptr, stream);
+    return run_score(ctx, reads, rule, {out_score, out_status, out_tier, nullptr, nullptr}, stream);
 }
 
 zsw_error zsw_score_ends_batch(zsw_context* ctx, const zsw_batch* reads, zsw_int_type int_type, int lanes,
@@ -1258,7 +1228,7 @@ zsw_error zsw_score_ends_batch(zsw_context* ctx, const zsw_batch* reads, zsw_int
     if (!out_ref_end || !out_query_end) return fail(ctx, ZSW_ERR_INVALID_ARGUMENT, "null argument");
     ResultRule rule;
     if (zsw_error ze = rule_direct(ctx, int_type, lanes, &rule); ze != ZSW_OK) return ze;
-    return run_score(ctx, reads, rule, true, out_score, out_status, nullptr, out_ref_end, out_query_end, stream);
+    return run_score(ctx, reads, rule, {out_score, out_status, nullptr, out_ref_end, out_query_end}, stream);
 }
 
 zsw_error zsw_score_ranges_batch(zsw_context* ctx, const zsw_batch* reads, zsw_int_type int_type, int lanes,
@@ -1266,7 +1236,7 @@ zsw_error zsw_score_ranges_batch(zsw_context* ctx, const zsw_batch* reads, zsw_i
                                  uint32_t* out_query_start, uint32_t* out_query_end, uint8_t* out_status, void* stream) {
     ResultRule rule;
     if (zsw_error ze = rule_direct(ctx, int_type, lanes, &rule); ze != ZSW_OK) return ze;
-    return run_ranges(ctx, reads, rule, out_score, out_ref_start, out_ref_end, out_query_start, out_query_end, out_status, nullptr, stream);
+    return run_ranges(ctx, reads, rule, {out_score, out_ref_start, out_ref_end, out_query_start, out_query_end, out_status, nullptr}, stream);
 }
 
 zsw_error zsw_score_ranges_batch_from(zsw_context* ctx, const zsw_batch* reads, int from_width, int preset_bits,
@@ -1275,8 +1245,7 @@ zsw_error zsw_score_ranges_batch_from(zsw_context* ctx, const zsw_batch* reads, 
                                       void* stream) {
     ResultRule rule;
     if (zsw_error ze = rule_cascade(ctx, from_width, preset_bits, &rule); ze != ZSW_OK) return ze;
-    return run_ranges(ctx, reads, rule, out_score, out_ref_start, out_ref_end, out_query_start, out_query_end, out_status, out_tier,
-                      stream);
+    return run_ranges(ctx, reads, rule, {out_score, out_ref_start, out_ref_end, out_query_start, out_query_end, out_status, out_tier}, stream);
 }
 
 zsw_error zsw_align_3pass_batch(zsw_context* ctx, const zsw_batch* reads, zsw_int_type int_type, int lanes, int invert,
@@ -1284,7 +1253,7 @@ zsw_error zsw_align_3pass_batch(zsw_context* ctx, const zsw_batch* reads, zsw_in
                                 uint64_t ciglet_cap, uint64_t* out_n_ciglets, void* stream) {
     ResultRule rule;
     if (zsw_error ze = rule_direct(ctx, int_type, lanes, &rule); ze != ZSW_OK) return ze;
-    return run_threepass(ctx, reads, rule, invert, out_aln, out_status, nullptr, out_inc, out_op, ciglet_cap, out_n_ciglets, stream);
+    return run_threepass(ctx, reads, rule, invert, {out_aln, out_status, nullptr, out_inc, out_op, ciglet_cap, out_n_ciglets}, stream);
 }
 
 zsw_error zsw_align_3pass_batch_from(zsw_context* ctx, const zsw_batch* reads, int from_width, int preset_bits, int invert,
@@ -1292,7 +1261,7 @@ zsw_error zsw_align_3pass_batch_from(zsw_context* ctx, const zsw_batch* reads, i
                                      uint8_t* out_op, uint64_t ciglet_cap, uint64_t* out_n_ciglets, void* stream) {
     ResultRule rule;
     if (zsw_error ze = rule_cascade(ctx, from_width, preset_bits, &rule); ze != ZSW_OK) return ze;
-    return run_threepass(ctx, reads, rule, invert, out_aln, out_status, out_tier, out_inc, out_op, ciglet_cap, out_n_ciglets, stream);
+    return run_threepass(ctx, reads, rule, invert, {out_aln, out_status, out_tier, out_inc, out_op, ciglet_cap, out_n_ciglets}, stream);
 }
 
 zsw_error zsw_sneaky_snake_batch(zsw_context* ctx, const zsw_batch* reads, const uint32_t* ref_start, const uint32_t* ref_len,
@@ -1308,9 +1277,7 @@ zsw_error zsw_sneaky_snake_batch(zsw_context* ctx, const zsw_batch* reads, const
         return fail(ctx, ZSW_ERR_INVALID_ARGUMENT, "zsw_sneaky_snake_batch: zsw_batch.encoding must be ZSW_ENCODING_BYTES (the filter compares raw bytes)");
     const uint32_t n = (uint32_t)reads->n_reads;
     if (n == 0) return ZSW_OK;
-    if (reads->mem == ZSW_MEM_HOST && reads->offsets)
-        for (uint32_t i = 0; i < n; ++i)
-            if (reads->offsets[i + 1] < reads->offsets[i]) return fail(ctx, ZSW_ERR_INVALID_ARGUMENT, "offsets not monotone");
+    if (reads->mem == ZSW_MEM_HOST && reads->offsets && !offsets_monotone(reads->offsets, n)) return fail(ctx, ZSW_ERR_INVALID_ARGUMENT, "offsets not monotone");
     hipStream_t stream = (hipStream_t)stream_;
     ZSW_HIP(ctx, hipSetDevice(ctx->device));
     BatchDev b{};
@@ -1484,7 +1451,7 @@ zsw_error zsw_set_option(zsw_context* ctx, zsw_option option, int64_t value) {
     }
     if (option == ZSW_OPTION_MIN_SCORE && value >= 0 && value <= 0x7fffffffll) {
         ctx->min_score = (uint32_t)value;
-        if (!value) ctx->min_counts_valid = false;
+        if (!value) ctx->last.min_counts_valid = false;
         return ZSW_OK;
     }
     return fail(ctx, ZSW_ERR_INVALID_ARGUMENT, "unknown option or value");
@@ -1494,7 +1461,7 @@ zsw_error zsw_min_score_counts(zsw_context* ctx, uint64_t* out) {
     DeviceGuard device_guard(ctx);
     if (!ctx || !out) return ZSW_ERR_INVALID_ARGUMENT;
     out[0] = out[1] = out[2] = out[3] = 0;
-    if (!ctx->min_counts_valid || !ctx->d_min_counts.p) return ZSW_OK;
+    if (!ctx->last.min_counts_valid || !ctx->d_min_counts.p) return ZSW_OK;
     uint32_t c[3] = {0, 0, 0};
     ZSW_HIP(ctx, hipDeviceSynchronize());
     ZSW_HIP(ctx, hipMemcpy(c, ctx->d_min_counts.p, sizeof(c), hipMemcpyDeviceToHost));
@@ -1507,7 +1474,7 @@ zsw_error zsw_prune_rescored(zsw_context* ctx, uint64_t* out_reads) {
     DeviceGuard device_guard(ctx);
     if (!ctx || !out_reads) return ZSW_ERR_INVALID_ARGUMENT;
     *out_reads = 0;
-    if ((!ctx->prune_chunk && !ctx->seed_ready) || !ctx->d_prune_count.p) return ZSW_OK;
+    if (!ctx->last.handbacks_counted || !ctx->d_prune_count.p) return ZSW_OK;
     uint32_t cnt = 0;
     ZSW_HIP(ctx, hipDeviceSynchronize());
     ZSW_HIP(ctx, hipMemcpy(&cnt, ctx->d_prune_count.as<uint32_t>() + 1, 4, hipMemcpyDeviceToHost));

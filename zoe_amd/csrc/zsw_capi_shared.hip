@@ -35,9 +35,9 @@ __device__ __forceinline__ void ballot_append(bool take, uint32_t i, uint32_t* l
     }
 }
 
-__global__ void iota_some_kernel(uint32_t n, const uint8_t* status, const uint8_t* tier, uint8_t want_tier, uint32_t* list, uint32_t* count) {
+__global__ void iota_some_kernel(uint32_t n, const uint8_t* status, const uint8_t* tier, uint8_t tier_code, uint32_t* list, uint32_t* count) {
     const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
-    ballot_append(i < n && status[i] == ZSW_STATUS_SOME && tier[i] == want_tier, i, list, count);
+    ballot_append(i < n && status[i] == ZSW_STATUS_SOME && tier[i] == tier_code, i, list, count);
 }
 
 // reads whose ends the role-swapped seeded pass could not settle (unique[i] == 0): the list of the exact shared-role kernel
@@ -111,28 +111,8 @@ zsw_error check_shared(zsw_context* ctx) {
     return ZSW_OK;
 }
 
-// stage() wants a reference: the shared calls have none of their own, the profile sequence stands in. `seedable`: the call's
-// kernels can take the seeded pass (with the index of the profile sequence under the transposed matrix, ctx->seed_shared).
-struct SharedStage {
-    zsw_context* ctx;
-    bool ref_was_set;
-    size_t ref_len;
-    explicit SharedStage(zsw_context* c, bool seedable = false) : ctx(c), ref_was_set(c->reference_set), ref_len(c->ref_len) {
-        ctx->shared_call = true;
-        ctx->shared_seedable = seedable;
-        ctx->reference_set = true;
-        ctx->ref_len = ctx->pseq_len;
-    }
-    ~SharedStage() {
-        ctx->shared_call = false;
-        ctx->shared_seedable = false;
-        ctx->reference_set = ref_was_set;
-        ctx->ref_len = ref_len;
-    }
-};
-
 // score + ends of every read against the shared profile, on the device.
-// With the seeded pass staged (SharedStage(ctx, true) + stage()): the roles are swapped — the read is the profile of the ordinary
+// With the seeded pass planned (stage() against_profile_sequence()): the roles are swapped — the read is the profile of the ordinary
 // kernels, the shared sequence their reference, the matrix transposed — and the banded seeded pass runs at mode 3: score, both
 // ends under ITS tie rule (first row of the sequence, then first column of the read) and whether the maximum sits in exactly one
 // cell of the matrix. For such a read the tie rule does not matter and the ends are the shared role's with the names swapped
@@ -145,22 +125,19 @@ zsw_error shared_ends_device(zsw_context* ctx, const Staged& st, const ResultRul
     const uint32_t n = st.b.n_items;
     BatchDev rest = st.b;
     const uint32_t* rest_count = nullptr;
-    if (ctx->seed_ready && n > 0 && !st.b.items) {
+    if (st.plan.seed && n > 0 && !st.b.items) {
         DevBuf* ws = ctx->sh_ws;
         ZSW_HIP(ctx, ws[SH_UNIQUE].ensure((size_t)n + 4));
         ZSW_HIP(ctx, ws[SH_ULIST].ensure((size_t)n * 4 + 4));
         ZSW_HIP(ctx, ws[SH_UCOUNT].ensure(16));
         ZSW_HIP(ctx, hipMemsetAsync(ws[SH_UNIQUE].p, 0, n, stream));
         ZSW_HIP(ctx, hipMemsetAsync(ws[SH_UCOUNT].p, 0, 4, stream));
-        ScoreOut o2 = out;
-        o2.ref_end = out.query_end;   // rows of the swapped problem are positions of the profile sequence
-        o2.query_end = out.ref_end;   // its columns positions of the read
-        o2.fb_list = ctx->d_fb_list.as<uint32_t>();
-        o2.fb_count = ctx->d_fb_count.as<uint32_t>();
+        // rows of the swapped problem are positions of the profile sequence, its columns positions of the read
+        ScoreOut o2 = score_out(ctx, {out.score, out.status, out.tier, out.query_end, out.ref_end});
         o2.unique = ws[SH_UNIQUE].as<uint8_t>();
         o2.skip_handed_back = true;
         hipError_t e = launch_score(ctx->d_sc_t.as<ScoringDev>(), ctx->h_sc_t, st.b, st.max_len, ctx->d_pseq.as<uint8_t>(), (uint32_t)ctx->pseq_len, rule, o2,
-                                    score_ws(ctx), stream, nullptr, 3);
+                                    score_ws(ctx, st), stream, nullptr, 3);
         if (e != hipSuccess) return fail(ctx, ZSW_ERR_HIP, "shared ends: role-swapped seeded pass", e);
         hipLaunchKernelGGL(select_not_unique_kernel, dim3((n + 255) / 256), dim3(256), 0, stream, n, ws[SH_UNIQUE].as<uint8_t>(),
                            ws[SH_ULIST].as<uint32_t>(), ws[SH_UCOUNT].as<uint32_t>());
@@ -174,77 +151,65 @@ zsw_error shared_ends_device(zsw_context* ctx, const Staged& st, const ResultRul
     return ZSW_OK;
 }
 
-zsw_error run_score_shared(zsw_context* ctx, const zsw_batch* reads, const ResultRule& rule, uint32_t* out_score, uint8_t* out_status,
-                           uint8_t* out_tier, void* stream_) {
+zsw_error run_score_shared(zsw_context* ctx, const zsw_batch* reads, const ResultRule& rule, const ScoreDest& dest, void* stream_) {
     zsw_error ze = check_shared(ctx);
     if (ze != ZSW_OK) return ze;
     DeviceGuard device_guard(ctx);
     hipStream_t stream = (hipStream_t)stream_;
-    SharedStage guard(ctx, true);  // the score does not depend on the roles: the seeded pass applies with the sequence as its reference
-    Staged st;
-    ze = stage(ctx, reads, stream, out_tier != nullptr, false, out_score, out_status, out_tier, nullptr, nullptr, &st);
+    Staged st;  // the score does not depend on the roles: the seeded pass applies with the sequence as its reference
+    ze = stage(ctx, against_profile_sequence(ctx), reads, &dest, stream, &st);
     if (ze != ZSW_OK) return ze;
     if (reads->n_reads == 0) return ZSW_OK;
     // roles swapped: the read is the profile of the ordinary kernels, the shared sequence their reference, the matrix transposed
-    ScoreOut out;
-    out.score = st.d_score;
-    out.status = st.d_status;
-    out.tier = st.d_tier;
-    out.fb_list = ctx->d_fb_list.as<uint32_t>();
-    out.fb_count = ctx->d_fb_count.as<uint32_t>();
-    hipError_t e = launch_score(ctx->d_sc_t.as<ScoringDev>(), ctx->h_sc_t, st.b, st.max_len, ctx->d_pseq.as<uint8_t>(), (uint32_t)ctx->pseq_len, rule, out,
-                                score_ws(ctx), stream, &ctx->timer, 0);
+    hipError_t e = launch_score(ctx->d_sc_t.as<ScoringDev>(), ctx->h_sc_t, st.b, st.max_len, ctx->d_pseq.as<uint8_t>(), (uint32_t)ctx->pseq_len, rule,
+                                score_out(ctx, st.dev), score_ws(ctx, st), stream, &ctx->timer, 0);
     if (e != hipSuccess) return fail(ctx, ZSW_ERR_HIP, "shared score launch", e);
     const uint32_t n = (uint32_t)reads->n_reads;
-    hipLaunchKernelGGL(empty_is_unmapped_kernel, dim3((n + 255) / 256), dim3(256), 0, stream, n, st.d_status);
-    return unstage(ctx, reads, stream, st, out_score, out_status, out_tier, nullptr, nullptr);
+    hipLaunchKernelGGL(empty_is_unmapped_kernel, dim3((n + 255) / 256), dim3(256), 0, stream, n, st.dev.status);
+    return unstage(ctx, reads, stream, st, dest);
 }
 
-zsw_error run_ends_shared(zsw_context* ctx, const zsw_batch* reads, const ResultRule& rule, uint32_t* out_score, uint32_t* out_rend,
-                          uint32_t* out_qend, uint8_t* out_status, void* stream_) {
+zsw_error run_ends_shared(zsw_context* ctx, const zsw_batch* reads, const ResultRule& rule, const ScoreDest& dest, void* stream_) {
     zsw_error ze = check_shared(ctx);
     if (ze != ZSW_OK) return ze;
-    if (!out_rend || !out_qend) return fail(ctx, ZSW_ERR_INVALID_ARGUMENT, "null argument");
+    if (!dest.ends()) return fail(ctx, ZSW_ERR_INVALID_ARGUMENT, "null argument");
     DeviceGuard device_guard(ctx);
     hipStream_t stream = (hipStream_t)stream_;
-    SharedStage guard(ctx, true);
     Staged st;
-    ze = stage(ctx, reads, stream, false, true, out_score, out_status, nullptr, out_rend, out_qend, &st);
+    ze = stage(ctx, against_profile_sequence(ctx), reads, &dest, stream, &st);
     if (ze != ZSW_OK) return ze;
     if (reads->n_reads == 0) return ZSW_OK;
     ScoreOut out;
-    out.score = st.d_score;
-    out.status = st.d_status;
-    out.ref_end = st.d_rend;
-    out.query_end = st.d_qend;
+    out.score = st.dev.score;
+    out.status = st.dev.status;
+    out.ref_end = st.dev.ref_end;
+    out.query_end = st.dev.query_end;
     ctx->timer.begin(stream);
     ze = shared_ends_device(ctx, st, rule, out, stream);
     ctx->timer.end(stream);
     if (ze != ZSW_OK) return ze;
-    return unstage(ctx, reads, stream, st, out_score, out_status, nullptr, out_rend, out_qend);
+    return unstage(ctx, reads, stream, st, dest);
 }
 
 // sw_simd_score_ranges of the shared role for every read, on the device (rs / re: positions in the read, qs / qe: in the profile
 // sequence); opens ctx->timer's interval and leaves it open.
 zsw_error ranges_shared_device(zsw_context* ctx, const Staged& st, const ResultRule& rule, hipStream_t stream, RangesDev* out, uint8_t* settled = nullptr);
 
-zsw_error run_ranges_shared(zsw_context* ctx, const zsw_batch* reads, const ResultRule& rule, uint32_t* out_score, uint32_t* out_rs,
-                            uint32_t* out_re, uint32_t* out_qs, uint32_t* out_qe, uint8_t* out_status, uint8_t* out_tier, void* stream_) {
+zsw_error run_ranges_shared(zsw_context* ctx, const zsw_batch* reads, const ResultRule& rule, const RangesDev& out, void* stream_) {
     zsw_error ze = check_shared(ctx);
     if (ze != ZSW_OK) return ze;
-    if (!reads || !out_score || !out_rs || !out_re || !out_qs || !out_qe || !out_status) return fail(ctx, ZSW_ERR_INVALID_ARGUMENT, "null argument");
+    if (!reads || !out.score || !out.rs || !out.re || !out.qs || !out.qe || !out.status) return fail(ctx, ZSW_ERR_INVALID_ARGUMENT, "null argument");
     DeviceGuard device_guard(ctx);
     hipStream_t stream = (hipStream_t)stream_;
-    SharedStage guard(ctx, true);
     Staged st;
-    ze = stage_reads(ctx, reads, stream, &st);
+    ze = stage(ctx, against_profile_sequence(ctx), reads, nullptr, stream, &st);
     const uint32_t n = st.b.n_reads;
     if (ze != ZSW_OK || n == 0) return ze;
     RangesDev rd;
     ze = ranges_shared_device(ctx, st, rule, stream, &rd);
     if (ze != ZSW_OK) return ze;
     ctx->timer.end(stream);
-    return copy_ranges_out(ctx, rd, n, reads->mem == ZSW_MEM_HOST, out_score, out_rs, out_re, out_qs, out_qe, out_status, out_tier, stream);
+    return copy_ranges_out(ctx, rd, n, reads->mem == ZSW_MEM_HOST, out, stream);
 }
 
 // settled (optional, n bytes): 1 where both maxima of the read sit in one cell each (the two seeded passes agree), else 0
@@ -290,15 +255,12 @@ zsw_error ranges_shared_device(zsw_context* ctx, const Staged& st, const ResultR
             ZSW_HIP(ctx, ws[SH_UNIQUE_R].ensure((size_t)n + 4));
             ZSW_HIP(ctx, hipMemsetAsync(ws[SH_UNIQUE_R].p, 0, n, stream));
             BatchDev brev = st.b;  // the same bases: the seeded pass reads them back to front (ScoreOut::reads_reversed)
-            ScoreOut o3 = ro;
-            o3.ref_end = ro.query_end;   // rows of the swapped problem: positions of the reversed profile sequence
-            o3.query_end = ro.ref_end;   // columns: positions of the reversed read
-            o3.fb_list = ctx->d_fb_list.as<uint32_t>();
-            o3.fb_count = ctx->d_fb_count.as<uint32_t>();
+            // rows of the swapped problem: positions of the reversed profile sequence; columns: positions of the reversed read
+            ScoreOut o3 = score_out(ctx, {ro.score, ro.status, nullptr, ro.query_end, ro.ref_end});
             o3.unique = ws[SH_UNIQUE_R].as<uint8_t>();
             o3.skip_handed_back = true;
             o3.reads_reversed = true;
-            ScoreWorkspace w = score_ws(ctx);
+            ScoreWorkspace w = score_ws(ctx, st);
             w.seed = &ctx->seed_shared_rev;
             hipError_t e3 = launch_score(ctx->d_sc_t.as<ScoringDev>(), ctx->h_sc_t, brev, st.max_len, ctx->d_pseq_rev.as<uint8_t>(), (uint32_t)plen, rule, o3, w,
                                          stream, nullptr, 3);
@@ -330,33 +292,28 @@ zsw_error ranges_shared_device(zsw_context* ctx, const Staged& st, const ResultR
 
 // SharedProfiles::sw_align_from_i*_3pass (profile_set.rs:212-283, 552-560; profile.rs:536-552 -> three_pass.rs:21-104): the shared
 // role's ranges, then the third pass with `reference` = read i and `query` = the profile sequence (ScalarProfile over its sub-range).
-zsw_error run_threepass_shared(zsw_context* ctx, const zsw_batch* reads, const ResultRule& rule, int invert, zsw_alignment* out_aln, uint8_t* out_status,
-                               uint8_t* out_tier, uint32_t* out_inc, uint8_t* out_op, uint64_t ciglet_cap, uint64_t* out_n_ciglets, void* stream_) {
+zsw_error run_threepass_shared(zsw_context* ctx, const zsw_batch* reads, const ResultRule& rule, int invert, const AlignDest& dest, void* stream_) {
     zsw_error ze = check_shared(ctx);
     if (ze != ZSW_OK) return ze;
     DeviceGuard device_guard(ctx);
     hipStream_t stream = (hipStream_t)stream_;
-    SharedStage guard(ctx, true);
     Staged st;
-    ze = stage_align(ctx, reads, out_aln, out_status, out_inc, out_op, ciglet_cap, out_n_ciglets, stream, &st);
+    ze = stage_align(ctx, against_profile_sequence(ctx), reads, dest, stream, &st);
     if (ze != ZSW_OK || reads->n_reads == 0) return ze;
     RangesDev rd;
     ze = ranges_shared_device(ctx, st, rule, stream, &rd);
     if (ze != ZSW_OK) return ze;
-    return threepass_third_pass(ctx, st, rd, ctx->d_pseq.as<uint8_t>(), (uint32_t)ctx->pseq_len, reads->mem == ZSW_MEM_HOST, invert, out_aln, out_status, out_tier,
-                                out_inc, out_op, ciglet_cap, out_n_ciglets, stream);
+    return threepass_third_pass(ctx, st, rd, ctx->d_pseq.as<uint8_t>(), (uint32_t)ctx->pseq_len, reads->mem == ZSW_MEM_HOST, invert, dest, stream);
 }
 
 zsw_error run_align_shared(zsw_context* ctx, const zsw_batch* reads, const ResultRule& rule, int lanes_w8, int lanes_w16, int lanes_w32, int invert,
-                           zsw_alignment* out_aln, uint8_t* out_status, uint8_t* out_tier, uint32_t* out_inc, uint8_t* out_op, uint64_t ciglet_cap,
-                           uint64_t* out_n_ciglets, void* stream_) {
+                           const AlignDest& dest, void* stream_) {
     zsw_error ze = check_shared(ctx);
     if (ze != ZSW_OK) return ze;
     DeviceGuard device_guard(ctx);
     hipStream_t stream = (hipStream_t)stream_;
-    SharedStage guard(ctx, true);
     Staged st;
-    ze = stage_align(ctx, reads, out_aln, out_status, out_inc, out_op, ciglet_cap, out_n_ciglets, stream, &st);
+    ze = stage_align(ctx, against_profile_sequence(ctx), reads, dest, stream, &st);
     const uint32_t n = st.b.n_reads;
     if (ze != ZSW_OK || n == 0) return ze;
     const bool host = reads->mem == ZSW_MEM_HOST;
@@ -475,8 +432,7 @@ zsw_error run_align_shared(zsw_context* ctx, const zsw_batch* reads, const Resul
         ZSW_HIP(ctx, hipMemcpy(&again, ws[WS_FBCOUNT].p, 4, hipMemcpyDeviceToHost));
         if (again) return fail(ctx, ZSW_ERR_HIP, "shared alignment traceback did not complete");
     }
-    return finish_alignments(ctx, ws, n, host, so.status, so.tier, invert, out_aln, out_status, out_tier, out_inc, out_op, ciglet_cap, out_n_ciglets,
-                             stream);
+    return finish_alignments(ctx, ws, n, host, so.status, so.tier, invert, dest, stream);
 }
 
 }  // namespace
@@ -509,7 +465,7 @@ zsw_error zsw_score_shared_batch(zsw_context* ctx, const zsw_batch* reads, zsw_i
     if (zsw_error ze = min_score_unsupported(ctx, "zsw_score_shared_batch"); ze != ZSW_OK) return ze;
     ResultRule rule;
     if (zsw_error ze = rule_direct(ctx, int_type, lanes, &rule); ze != ZSW_OK) return ze;
-    return run_score_shared(ctx, reads, rule, out_score, out_status, nullptr, stream);
+    return run_score_shared(ctx, reads, rule, {out_score, out_status, nullptr, nullptr, nullptr}, stream);
 }
 
 zsw_error zsw_score_shared_batch_from(zsw_context* ctx, const zsw_batch* reads, int from_width, int preset_bits, uint32_t* out_score,
@@ -517,7 +473,7 @@ zsw_error zsw_score_shared_batch_from(zsw_context* ctx, const zsw_batch* reads, 
     if (zsw_error ze = min_score_unsupported(ctx, "zsw_score_shared_batch_from"); ze != ZSW_OK) return ze;
     ResultRule rule;
     if (zsw_error ze = rule_cascade(ctx, from_width, preset_bits, &rule); ze != ZSW_OK) return ze;
-    return run_score_shared(ctx, reads, rule, out_score, out_status, out_tier, stream);
+    return run_score_shared(ctx, reads, rule, {out_score, out_status, out_tier, nullptr, nullptr}, stream);
 }
 
 zsw_error zsw_score_ends_shared_batch(zsw_context* ctx, const zsw_batch* reads, zsw_int_type int_type, int lanes, uint32_t* out_score,
@@ -525,7 +481,7 @@ zsw_error zsw_score_ends_shared_batch(zsw_context* ctx, const zsw_batch* reads, 
     if (zsw_error ze = min_score_unsupported(ctx, "zsw_score_ends_shared_batch"); ze != ZSW_OK) return ze;
     ResultRule rule;
     if (zsw_error ze = rule_direct(ctx, int_type, lanes, &rule); ze != ZSW_OK) return ze;
-    return run_ends_shared(ctx, reads, rule, out_score, out_ref_end, out_query_end, out_status, stream);
+    return run_ends_shared(ctx, reads, rule, {out_score, out_status, nullptr, out_ref_end, out_query_end}, stream);
 }
 
 zsw_error zsw_score_ranges_shared_batch(zsw_context* ctx, const zsw_batch* reads, zsw_int_type int_type, int lanes, uint32_t* out_score,
@@ -534,7 +490,7 @@ zsw_error zsw_score_ranges_shared_batch(zsw_context* ctx, const zsw_batch* reads
     if (zsw_error ze = min_score_unsupported(ctx, "zsw_score_ranges_shared_batch"); ze != ZSW_OK) return ze;
     ResultRule rule;
     if (zsw_error ze = rule_direct(ctx, int_type, lanes, &rule); ze != ZSW_OK) return ze;
-    return run_ranges_shared(ctx, reads, rule, out_score, out_ref_start, out_ref_end, out_query_start, out_query_end, out_status, nullptr, stream);
+    return run_ranges_shared(ctx, reads, rule, {out_score, out_ref_start, out_ref_end, out_query_start, out_query_end, out_status, nullptr}, stream);
 }
 
 zsw_error zsw_score_ranges_shared_batch_from(zsw_context* ctx, const zsw_batch* reads, int from_width, int preset_bits, uint32_t* out_score,
@@ -543,7 +499,7 @@ zsw_error zsw_score_ranges_shared_batch_from(zsw_context* ctx, const zsw_batch* 
     if (zsw_error ze = min_score_unsupported(ctx, "zsw_score_ranges_shared_batch_from"); ze != ZSW_OK) return ze;
     ResultRule rule;
     if (zsw_error ze = rule_cascade(ctx, from_width, preset_bits, &rule); ze != ZSW_OK) return ze;
-    return run_ranges_shared(ctx, reads, rule, out_score, out_ref_start, out_ref_end, out_query_start, out_query_end, out_status, out_tier, stream);
+    return run_ranges_shared(ctx, reads, rule, {out_score, out_ref_start, out_ref_end, out_query_start, out_query_end, out_status, out_tier}, stream);
 }
 
 zsw_error zsw_align_shared_batch(zsw_context* ctx, const zsw_batch* reads, zsw_int_type int_type, int lanes, int invert, zsw_alignment* out_aln,
@@ -551,8 +507,7 @@ zsw_error zsw_align_shared_batch(zsw_context* ctx, const zsw_batch* reads, zsw_i
     if (zsw_error ze = min_score_unsupported(ctx, "zsw_align_shared_batch"); ze != ZSW_OK) return ze;
     ResultRule rule;
     if (zsw_error ze = rule_direct(ctx, int_type, lanes, &rule); ze != ZSW_OK) return ze;
-    return run_align_shared(ctx, reads, rule, lanes, lanes, lanes, invert, out_aln, out_status, nullptr, out_inc, out_op, ciglet_cap, out_n_ciglets,
-                            stream);
+    return run_align_shared(ctx, reads, rule, lanes, lanes, lanes, invert, {out_aln, out_status, nullptr, out_inc, out_op, ciglet_cap, out_n_ciglets}, stream);
 }
 
 zsw_error zsw_align_shared_batch_from(zsw_context* ctx, const zsw_batch* reads, int from_width, int preset_bits, int invert, zsw_alignment* out_aln,
@@ -561,8 +516,8 @@ zsw_error zsw_align_shared_batch_from(zsw_context* ctx, const zsw_batch* reads, 
     if (zsw_error ze = min_score_unsupported(ctx, "zsw_align_shared_batch_from"); ze != ZSW_OK) return ze;
     ResultRule rule;
     if (zsw_error ze = rule_cascade(ctx, from_width, preset_bits, &rule); ze != ZSW_OK) return ze;
-    return run_align_shared(ctx, reads, rule, preset_bits / 8, preset_bits / 16, preset_bits / 32, invert, out_aln, out_status, out_tier, out_inc,
-                            out_op, ciglet_cap, out_n_ciglets, stream);
+    return run_align_shared(ctx, reads, rule, preset_bits / 8, preset_bits / 16, preset_bits / 32, invert,
+                            {out_aln, out_status, out_tier, out_inc, out_op, ciglet_cap, out_n_ciglets}, stream);
 }
 
 zsw_error zsw_align_3pass_shared_batch(zsw_context* ctx, const zsw_batch* reads, zsw_int_type int_type, int lanes, int invert, zsw_alignment* out_aln,
@@ -570,7 +525,7 @@ zsw_error zsw_align_3pass_shared_batch(zsw_context* ctx, const zsw_batch* reads,
     if (zsw_error ze = min_score_unsupported(ctx, "zsw_align_3pass_shared_batch"); ze != ZSW_OK) return ze;
     ResultRule rule;
     if (zsw_error ze = rule_direct(ctx, int_type, lanes, &rule); ze != ZSW_OK) return ze;
-    return run_threepass_shared(ctx, reads, rule, invert, out_aln, out_status, nullptr, out_inc, out_op, ciglet_cap, out_n_ciglets, stream);
+    return run_threepass_shared(ctx, reads, rule, invert, {out_aln, out_status, nullptr, out_inc, out_op, ciglet_cap, out_n_ciglets}, stream);
 }
 
 zsw_error zsw_align_3pass_shared_batch_from(zsw_context* ctx, const zsw_batch* reads, int from_width, int preset_bits, int invert, zsw_alignment* out_aln,
@@ -579,7 +534,7 @@ zsw_error zsw_align_3pass_shared_batch_from(zsw_context* ctx, const zsw_batch* r
     if (zsw_error ze = min_score_unsupported(ctx, "zsw_align_3pass_shared_batch_from"); ze != ZSW_OK) return ze;
     ResultRule rule;
     if (zsw_error ze = rule_cascade(ctx, from_width, preset_bits, &rule); ze != ZSW_OK) return ze;
-    return run_threepass_shared(ctx, reads, rule, invert, out_aln, out_status, out_tier, out_inc, out_op, ciglet_cap, out_n_ciglets, stream);
+    return run_threepass_shared(ctx, reads, rule, invert, {out_aln, out_status, out_tier, out_inc, out_op, ciglet_cap, out_n_ciglets}, stream);
 }
 
 }  // extern "C"

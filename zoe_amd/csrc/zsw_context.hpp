@@ -50,7 +50,6 @@ struct zsw_context {
     int bias = 0;
     zsw::DevBuf d_sc, d_ref, d_fb_list, d_fb_count, d_scratch, d_maxlen, d_bucket_items, d_bucket_counts, d_tile_buf, d_tile_state;
     zsw::DevBuf d_prune, d_prune_list, d_prune_count;  // column-pruned score pass; the worklist and its counters also serve the seeded pass
-    uint32_t prune_chunk = 0;
     // seeded exact score pass (zsw_score_seed.hip): index of the reference under the current matrix (built with the first batch
     // that can use it, rebuilt after zsw_set_scoring / zsw_set_reference), a host copy of the reference to build it from
     zsw::SeedIndex seed;
@@ -60,8 +59,6 @@ struct zsw_context {
     zsw::DevBuf d_ref_rev;
     std::vector<uint8_t> h_ref;
     zsw::DevBuf d_seed_work, d_seed_gtab, d_chunk_keys;
-    bool seed_ready = false;  // this call's batch takes the seeded pass (workspace and worklist are in place)
-    bool chunk_ready = false;  // ... and d_chunk_keys holds a key per read (long references: the hand-back pass runs in chunks of rows)
     size_t ref_len = 0;
     uint32_t scratch_len = 0;
     size_t exact_slots = 0;
@@ -85,7 +82,13 @@ struct zsw_context {
     // by stage() while the option is on
     uint32_t min_score = 0;
     zsw::DevBuf d_min_counts;
-    bool min_counts_valid = false;
+    // What zsw_prune_rescored and zsw_min_score_counts report on: the last call that stage() planned (written there once its plan is
+    // complete; a call rejected before that leaves the record of the call before it). The only per-call state the context keeps:
+    // everything else about a call travels in its Staged value.
+    struct LastCall {
+        bool handbacks_counted = false;  // d_prune_count[1] counts this call's hand-backs (it took the seeded or the column-pruned pass)
+        bool min_counts_valid = false;   // d_min_counts holds this call's counters (zsw_set_option(MIN_SCORE, 0) clears it)
+    } last;
     // host batches: reads of chunk k+1 cross PCIe on this stream while chunk k computes
     hipStream_t copy_stream = nullptr;
     std::vector<hipEvent_t> copy_events;
@@ -97,14 +100,12 @@ struct zsw_context {
     std::vector<uint8_t> h_pseq;
     size_t pseq_len = 0;
     bool pseq_set = false;
-    bool shared_call = false;  // stage(): the call scores against d_pseq with the transposed matrix: its seeded pass uses seed_shared
     // index of the profile sequence under the transposed matrix: the seeded pass of the shared role's score calls (roles swapped:
     // the sequence is the ordinary kernels' reference); rebuilt after zsw_set_scoring / zsw_set_profile_sequence
     zsw::SeedIndex seed_shared;
     // the same for the REVERSED profile sequence (d_pseq_rev): the second pass of the shared role's sw_simd_score_ranges as a
     // seeded pass over the reversed reads (zsw_capi_shared.hip, run_ranges_shared); built with the first such call
     zsw::SeedIndex seed_shared_rev;
-    bool shared_seedable = false;  // set by the shared entry points whose kernels can take the seeded pass (score; ends with MODE 3)
     // strand-aware calls (zsw_strand.hip): the complement table (empty = the IUPAC default), workspace — the staged batch of a host
     // call, the oriented copy, the second batch of the reads scored on both strands and its results, 8 bytes per read of what the
     // seed kernel found, the list of unsettled reads and the counters of zsw_strand_counts — and the host copy a host batch is
@@ -293,54 +294,120 @@ inline zsw_error min_score_unsupported(zsw_context* ctx, const char* what) {
     return ZSW_ERR_UNSUPPORTED;
 }
 
+// are the n + 1 offsets of a host batch in ascending order? *longest (optional): the longest read
+inline bool offsets_monotone(const uint64_t* offsets, uint64_t n, uint32_t* longest = nullptr) {
+    uint32_t m = 0;
+    for (uint64_t i = 0; i < n; ++i) {
+        if (offsets[i + 1] < offsets[i]) return false;
+        m = std::max<uint32_t>(m, (uint32_t)(offsets[i + 1] - offsets[i]));
+    }
+    if (longest) *longest = m;
+    return true;
+}
+
+// How a call is put together: target -> stage -> plan -> run -> deliver. The entry point names what the reads are scored against
+// (Against) and where the results go (ScoreDest / AlignDest / RangesDev); stage() brings the batch to the device and decides the
+// passes the batch takes (CallPlan, inside Staged); the run_* functions launch from the Staged value; unstage() / copy_ranges_out() /
+// finish_alignments() deliver. stage() is a function of its arguments and of the context's configuration and buffers: what stays on
+// the context between calls is the growing buffers, the lazily built indices and the last-call record (zsw_context::last).
+
+// The target of a call: what the ordinary score kernels treat as their reference, the scoring that goes with it, the index that
+// serves its seeded pass.
+struct Against {
+    const uint8_t* d_seq;  // the sequence on the device, and the host copy the index is built from
+    const uint8_t* h_seq;
+    size_t len;
+    const ScoringDev *d_sc, *h_sc;
+    SeedIndex* index;
+    bool set;        // the sequence has been given
+    bool may_prune;  // the column-pruned pass may run
+};
+// the read-as-profile role: the reads against the context's reference
+inline Against against_reference(zsw_context* c) {
+    if (!c) return Against{};
+    return Against{c->d_ref.as<uint8_t>(), c->h_ref.data(), c->ref_len, c->d_sc.as<ScoringDev>(), &c->h_sc, &c->seed, c->reference_set, true};
+}
+// the shared role's score passes swap the roles: the profile sequence is the ordinary kernels' reference, the matrix transposed
+inline Against against_profile_sequence(zsw_context* c) {
+    if (!c) return Against{};
+    return Against{c->d_pseq.as<uint8_t>(), c->h_pseq.data(), c->pseq_len, c->d_sc_t.as<ScoringDev>(), &c->h_sc_t, &c->seed_shared, c->pseq_set, false};
+}
+
+// The result arrays of a score call (tier, ref_end, query_end: null = not wanted), and of an alignment call (tier: null = not wanted)
+struct ScoreDest {
+    uint32_t* score;
+    uint8_t *status, *tier;
+    uint32_t *ref_end, *query_end;
+    bool ends() const { return ref_end && query_end; }
+};
+struct AlignDest {
+    zsw_alignment* aln;
+    uint8_t *status, *tier;
+    uint32_t* inc;
+    uint8_t* op;
+    uint64_t ciglet_cap;
+    uint64_t* n_ciglets;
+};
+
+// The passes stage() decided this call's batch takes
+struct CallPlan {
+    SeedIndex* seed = nullptr;  // the seeded pass runs with this index (workspace and worklist are in place); null: no seeded pass
+    bool chunk_keys = false;    // ... and d_chunk_keys holds a key per read (long references: the hand-back pass runs in chunks of rows)
+    uint32_t prune_chunk = 0;   // reads per round of the column-pruned pass; 0: it does not run
+    bool min_counts = false;    // ZSW_OPTION_MIN_SCORE is on: d_min_counts was zeroed for this call
+};
+
 struct Staged {
     BatchDev b{};
     uint32_t max_len = 0;
-    uint32_t* d_score = nullptr;
-    uint8_t* d_status = nullptr;
-    uint8_t* d_tier = nullptr;
-    uint32_t* d_rend = nullptr;
-    uint32_t* d_qend = nullptr;
+    // where the kernels write the results: the caller's arrays (device batch) or the staging buffers (host batch); all null for a
+    // call whose results stay in library workspace
+    ScoreDest dev{};
+    CallPlan plan{};
 };
 
+// a ScoreOut over `d` with the context's fall-back list
+inline ScoreOut score_out(zsw_context* ctx, const ScoreDest& d) {
+    ScoreOut o;
+    o.score = d.score;
+    o.status = d.status;
+    o.tier = d.tier;
+    o.ref_end = d.ref_end;
+    o.query_end = d.query_end;
+    o.fb_list = ctx->d_fb_list.as<uint32_t>();
+    o.fb_count = ctx->d_fb_count.as<uint32_t>();
+    return o;
+}
+
 // zsw_capi.hip: the bodies of zsw_score_batch(_from) and zsw_align_3pass_batch(_from), which the strand-aware calls run on oriented batches
-zsw_error run_score(zsw_context* ctx, const zsw_batch* reads, const ResultRule& rule, bool want_ends, uint32_t* out_score, uint8_t* out_status,
-                    uint8_t* out_tier, uint32_t* out_rend, uint32_t* out_qend, void* stream);
-zsw_error run_threepass(zsw_context* ctx, const zsw_batch* reads, const ResultRule& rule, int invert, zsw_alignment* out_aln, uint8_t* out_status,
-                        uint8_t* out_tier, uint32_t* out_inc, uint8_t* out_op, uint64_t ciglet_cap, uint64_t* out_n_ciglets, void* stream);
-// zsw_capi.hip
-zsw_error stage(zsw_context* ctx, const zsw_batch* reads, hipStream_t stream, bool want_tier, bool want_ends, uint32_t* out_score,
-                uint8_t* out_status, uint8_t* out_tier, uint32_t* out_rend, uint32_t* out_qend, Staged* st, bool defer_bases_copy = false);
-// stage() for the calls whose results stay in library workspace (ranges, alignments): no score / status arrays of the caller
-zsw_error stage_reads(zsw_context* ctx, const zsw_batch* reads, hipStream_t stream, Staged* st);
-// prologue of the alignment calls: null checks, stage_reads(), *out_n_ciglets = 0 (the caller returns at once for an empty batch)
-zsw_error stage_align(zsw_context* ctx, const zsw_batch* reads, zsw_alignment* out_aln, uint8_t* out_status, uint32_t* out_inc, uint8_t* out_op,
-                      uint64_t ciglet_cap, uint64_t* out_n_ciglets, hipStream_t stream, Staged* st);
-ScoreWorkspace score_ws(zsw_context* ctx);
-zsw_error unstage(zsw_context* ctx, const zsw_batch* reads, hipStream_t stream, const Staged& st, uint32_t* out_score, uint8_t* out_status,
-                  uint8_t* out_tier, uint32_t* out_rend, uint32_t* out_qend);
+zsw_error run_score(zsw_context* ctx, const zsw_batch* reads, const ResultRule& rule, const ScoreDest& dest, void* stream);
+zsw_error run_threepass(zsw_context* ctx, const zsw_batch* reads, const ResultRule& rule, int invert, const AlignDest& dest, void* stream);
+// zsw_capi.hip. dest: null = the results stay in library workspace (ranges, alignments): no staging of score / status
+zsw_error stage(zsw_context* ctx, const Against& target, const zsw_batch* reads, const ScoreDest* dest, hipStream_t stream, Staged* st,
+                bool defer_bases_copy = false);
+// prologue of the alignment calls: null checks, stage(), *dest.n_ciglets = 0 (the caller returns at once for an empty batch)
+zsw_error stage_align(zsw_context* ctx, const Against& target, const zsw_batch* reads, const AlignDest& dest, hipStream_t stream, Staged* st);
+ScoreWorkspace score_ws(zsw_context* ctx, const Staged& st);
+zsw_error unstage(zsw_context* ctx, const zsw_batch* reads, hipStream_t stream, const Staged& st, const ScoreDest& dest);
 enum { WS_SCORE = 0, WS_STATUS, WS_TIER, WS_REND, WS_ITEMS, WS_RING, WS_CIG, WS_ALN, WS_CIGSTART, WS_CIGRAW, WS_BSUMS, WS_TOTAL,
        WS_FBLIST, WS_FBCOUNT, WS_OINC, WS_OOP, WS_CIG2, WS_RING2, WS_KEYS_IN, WS_KEYS_OUT, WS_VALS_IN, WS_SORT_TMP, WS_GTABLE, WS_FBMETA,
        WS_ITEMS2, WS_SAFE, WS_CERT_OK, WS_CERT_DONE, WS_CERT_STATUS };
 enum { RW_FSCORE = 0, RW_FSTATUS, RW_FREND, RW_FQEND, RW_RSCORE, RW_RSTATUS, RW_RRS, RW_RQS, RW_QEM, RW_GTAB, RW_MIS, RW_O0, RW_O1,
        RW_O2, RW_O3, RW_O4, RW_O5, RW_FTIER, RW_UNIQ_F, RW_UNIQ_R, RW_RBASES, RW_ULIST, RW_UCOUNT };
 zsw_error finish_alignments(zsw_context* ctx, DevBuf* ws, uint32_t n, bool host, const uint8_t* d_status, const uint8_t* d_tier, int invert,
-                            zsw_alignment* out_aln, uint8_t* out_status, uint8_t* out_tier, uint32_t* out_inc, uint8_t* out_op,
-                            uint64_t ciglet_cap, uint64_t* out_n_ciglets, hipStream_t stream);
-struct RangesDev {  // device arrays of sw_simd_score_ranges for every read (library workspace)
+                            const AlignDest& dest, hipStream_t stream);
+struct RangesDev {  // the arrays of sw_simd_score_ranges for every read: library workspace on the device, or the caller's (tier: may be null)
     uint32_t *score, *rs, *re, *qs, *qe;
     uint8_t *status, *tier;
 };
 // the ranges to the caller's arrays (a host batch: the call returns once they are there)
-zsw_error copy_ranges_out(zsw_context* ctx, const RangesDev& rd, uint32_t n, bool host, uint32_t* out_score, uint32_t* out_rs, uint32_t* out_re,
-                          uint32_t* out_qs, uint32_t* out_qe, uint8_t* out_status, uint8_t* out_tier, hipStream_t stream);
+zsw_error copy_ranges_out(zsw_context* ctx, const RangesDev& rd, uint32_t n, bool host, const RangesDev& out, hipStream_t stream);
 // the seed index of a reversed sequence (`seq` back to front, uploaded to `d_rev`) under `sc`, unless it is valid already
 zsw_error reversed_seed_index(zsw_context* ctx, SeedIndex* index, DevBuf* d_rev, const std::vector<uint8_t>& seq, const ScoringDev& sc, hipStream_t stream);
 // sw_align_3pass's third pass (zsw_threepass.hip) over ranges that are already on the device, results to the caller's arrays; the
 // caller has opened ctx->timer's interval. pseq: non-null = the shared-profile role (ThreePassArgs::pseq).
 zsw_error threepass_third_pass(zsw_context* ctx, const Staged& st, const RangesDev& rd, const uint8_t* pseq, uint32_t pseq_len, bool host, int invert,
-                               zsw_alignment* out_aln, uint8_t* out_status, uint8_t* out_tier, uint32_t* out_inc, uint8_t* out_op, uint64_t ciglet_cap,
-                               uint64_t* out_n_ciglets, hipStream_t stream);
+                               const AlignDest& dest, hipStream_t stream);
 // The certificate pass of sw_simd_align in both roles (tests/models/align_gapless_cert.cpp, align_onegap_cert.cpp): the classify
 // launches of zsw_threepass.hip write the alignment of every read of `rd` they can certify (settled[i]: both maxima of read i sit in
 // one cell each). *pass2_status: the statuses the literal second pass sees — a certified read does not take part. pseq: as above.

@@ -267,9 +267,7 @@ zsw_error check_strand_batch(zsw_context* ctx, const zsw_batch* reads, bool need
     if (reads->encoding != ZSW_ENCODING_BYTES) return fail(ctx, ZSW_ERR_INVALID_ARGUMENT, "unknown zsw_batch.encoding");
     if (reads->n_reads > 0x7fffffffull) return fail(ctx, ZSW_ERR_INVALID_ARGUMENT, "n_reads > 2^31-1 per call");
     if (reads->n_reads && !reads->bases) return fail(ctx, ZSW_ERR_INVALID_ARGUMENT, "null bases");
-    if (reads->mem == ZSW_MEM_HOST && reads->offsets)
-        for (uint64_t i = 0; i < reads->n_reads; ++i)
-            if (reads->offsets[i + 1] < reads->offsets[i]) return fail(ctx, ZSW_ERR_INVALID_ARGUMENT, "offsets not monotone");
+    if (reads->mem == ZSW_MEM_HOST && reads->offsets && !offsets_monotone(reads->offsets, reads->n_reads)) return fail(ctx, ZSW_ERR_INVALID_ARGUMENT, "offsets not monotone");
     return ZSW_OK;
 }
 
@@ -325,7 +323,7 @@ zsw_error score_strands_device(zsw_context* ctx, const zsw_batch* reads, size_t 
         hipLaunchKernelGGL(strand_nobound_kernel, dim3(g256), dim3(256), 0, stream, n, meta, ctx->strand_dbg);  // every read runs forward first
         ZSW_HIP(ctx, hipGetLastError());
     }
-    zsw_error ze = run_score(ctx, &first, rule, false, d_score, d_status, d_tier, nullptr, nullptr, stream);
+    zsw_error ze = run_score(ctx, &first, rule, {d_score, d_status, d_tier, nullptr, nullptr}, stream);
     if (ze != ZSW_OK) return ze;
     SettleArgs se;
     se.n = n;
@@ -377,8 +375,7 @@ zsw_error score_strands_device(zsw_context* ctx, const zsw_batch* reads, size_t 
         second.offsets = offs;
     }
     ZSW_HIP(ctx, launch_orient(o, stream));
-    ze = run_score(ctx, &second, rule, false, ws[ST_S2_SCORE].as<uint32_t>(), ws[ST_S2_STATUS].as<uint8_t>(), ws[ST_S2_TIER].as<uint8_t>(), nullptr, nullptr,
-                   stream);
+    ze = run_score(ctx, &second, rule, {ws[ST_S2_SCORE].as<uint32_t>(), ws[ST_S2_STATUS].as<uint8_t>(), ws[ST_S2_TIER].as<uint8_t>(), nullptr, nullptr}, stream);
     if (ze != ZSW_OK) return ze;
     MergeArgs m;
     m.n2 = n2;
@@ -553,7 +550,7 @@ zsw_error zsw_align_3pass_strands_batch_from(zsw_context* ctx, const zsw_batch* 
         oriented.bases = ws[ST_ORIENT_FINAL].as<uint8_t>();
     }
     // one alignment run, on the oriented batch
-    return run_threepass(ctx, &oriented, rule, invert, out_aln, out_status, out_tier, out_inc, out_op, ciglet_cap, out_n_ciglets, stream_);
+    return run_threepass(ctx, &oriented, rule, invert, {out_aln, out_status, out_tier, out_inc, out_op, ciglet_cap, out_n_ciglets}, stream_);
 }
 
 zsw_error zsw_strand_counts(zsw_context* ctx, uint64_t* out) {
