@@ -321,6 +321,8 @@ pub const ZSW_OPTION_EXACT_PRUNING: i32 = 1;
 pub const ZSW_OPTION_MIN_SCORE: i32 = 2;
 /// `zsw_launch_kind` of a `debug_score_launches` record that describes the row-chunked launch recorded after it
 pub const ZSW_LAUNCH_ROW_CHUNKS: u32 = 15;
+/// the most members a reference panel holds (`zsw_set_panel`)
+pub const ZSW_PANEL_MAX_REFS: u32 = 64;
 
 /// `zsw_int_type`: T of `StripedProfile<T, N, S>` (`math/integer.rs:231-238`)
 #[repr(i32)]
@@ -357,6 +359,10 @@ unsafe extern "C" {
     fn zsw_orient_batch(ctx: *mut ZswContext, reads: *const ZswBatch, strand: *const u8, out_bases: *mut u8, stream: *mut c_void) -> i32;
     fn zsw_align_3pass_strands_batch_from(ctx: *mut ZswContext, reads: *const ZswBatch, from_width: i32, preset_bits: i32, invert: i32, out_aln: *mut ZswAlignment, out_status: *mut u8, out_tier: *mut u8, out_strand: *mut u8, out_inc: *mut u32, out_op: *mut u8, ciglet_cap: u64, out_n_ciglets: *mut u64, stream: *mut c_void) -> i32;
     fn zsw_strand_counts(ctx: *mut ZswContext, out: *mut u64) -> i32;
+    fn zsw_set_panel(ctx: *mut ZswContext, seqs: *const u8, offsets: *const u64, n_refs: u32, mem: i32) -> i32;
+    fn zsw_score_panel_batch_from(ctx: *mut ZswContext, reads: *const ZswBatch, from_width: i32, preset_bits: i32, out_score: *mut u32, out_status: *mut u8, out_tier: *mut u8, out_ref: *mut u32, stream: *mut c_void) -> i32;
+    fn zsw_panel_gather_batch(ctx: *mut ZswContext, reads: *const ZswBatch, ref_of: *const u32, k: u32, out_bases: *mut u8, out_offsets: *mut u64, out_index: *mut u32, out_n: *mut u64, stream: *mut c_void) -> i32;
+    fn zsw_panel_counts(ctx: *mut ZswContext, out: *mut u64) -> i32;
     fn zsw_set_profile_sequence(ctx: *mut ZswContext, sequence: *const u8, len: usize, mem: i32) -> i32;
     fn zsw_score_shared_batch(ctx: *mut ZswContext, reads: *const ZswBatch, int_type: i32, lanes: i32, out_score: *mut u32, out_status: *mut u8, stream: *mut c_void) -> i32;
     fn zsw_score_shared_batch_from(ctx: *mut ZswContext, reads: *const ZswBatch, from_width: i32, preset_bits: i32, out_score: *mut u32, out_status: *mut u8, out_tier: *mut u8, stream: *mut c_void) -> i32;
@@ -394,6 +400,7 @@ unsafe extern "C" {
     fn zsw_debug_cert_records(ctx: *mut ZswContext, records: *mut i32) -> i32;
     fn zsw_debug_threepass_records(ctx: *mut ZswContext, records: *mut i32) -> i32;
     fn zsw_debug_strand_records(ctx: *mut ZswContext, records: *mut i32) -> i32;
+    fn zsw_debug_panel_records(ctx: *mut ZswContext, records: *mut i32) -> i32;
     fn zsw_debug_score_launches(ctx: *mut ZswContext, records: *mut u32, capacity: u32, out_n: *mut u32) -> i32;
     fn zsw_prune_rescored(ctx: *mut ZswContext, out_reads: *mut u64) -> i32;
     fn zsw_set_option(ctx: *mut ZswContext, option: i32, value: i64) -> i32;
@@ -1285,6 +1292,69 @@ impl GpuContext {
         // SAFETY: live context, four entries
         self.check(unsafe { zsw_strand_counts(self.raw, c.as_mut_ptr()) }, 0, 0)?;
         Ok(c)
+    }
+
+    /// `zsw_set_panel`: the members of a reference panel (1 ..= [`ZSW_PANEL_MAX_REFS`] non-empty sequences), independent of the
+    /// reference of the other calls.
+    pub fn set_panel<R: AsRef<[u8]>>(&self, members: &[R]) -> Result<(), GpuError> {
+        let batch = HostBatch::new(members);
+        // SAFETY: members.len() + 1 offsets into batch.bases, both copied by the call
+        self.check(unsafe { zsw_set_panel(self.raw, batch.bases.as_ptr(), batch.offsets.as_ptr(), members.len() as u32, ZSW_MEM_HOST) }, 0, 0)
+    }
+
+    /// `zsw_score_panel_batch_from`: per read `sw_score_from_i{from_width}` against the member of the panel that ranks highest
+    /// (Overflowed > Some by score > Unmapped), ties to the lowest member: (score, width that answered, member).
+    pub fn sw_score_panel_from_batch<const S: usize, Q: AsRef<[u8]>>(
+        &self, reads: &[Q], scoring: &Scoring<'_, S>, cascade: Cascade,
+    ) -> Result<Vec<(Result<MaybeAligned<u32>, ProfileError>, u8, u32)>, GpuError> {
+        let (w, map) = (scoring.flat_weights(), scoring.index_map());
+        let (go, ge) = (scoring.gap_open, scoring.gap_extend);
+        // SAFETY: pointers are valid for S*S / 256 bytes for the duration of the call
+        self.check(unsafe { zsw_set_scoring(self.raw, w.as_ptr(), S as i32, map.as_ptr(), i32::from(go), i32::from(ge)) }, go, ge)?;
+        let batch = HostBatch::new(reads);
+        let n = reads.len();
+        let (mut score, mut status, mut tier, mut member) = (vec![0u32; n.max(1)], vec![0u8; n.max(1)], vec![0u8; n.max(1)], vec![0u32; n.max(1)]);
+        // SAFETY: output arrays hold n entries
+        let code = unsafe {
+            zsw_score_panel_batch_from(self.raw, &batch.as_c(), cascade.from_width, cascade.preset_bits, score.as_mut_ptr(), status.as_mut_ptr(), tier.as_mut_ptr(),
+                                       member.as_mut_ptr(), ptr::null_mut())
+        };
+        self.check(code, go, ge)?;
+        Ok((0..n).map(|i| (maybe(status[i], || score[i]), tier[i], member[i])).collect())
+    }
+
+    /// `zsw_panel_gather_batch`: the reads with `ref_of[i] == k`, in input order, and which input reads they are.
+    pub fn panel_gather<Q: AsRef<[u8]>>(&self, reads: &[Q], ref_of: &[u32], k: u32) -> Result<(Vec<Vec<u8>>, Vec<u32>), GpuError> {
+        assert_eq!(reads.len(), ref_of.len());
+        let batch = HostBatch::new(reads);
+        let n = reads.len();
+        let (mut bases, mut offsets, mut index, mut m) = (vec![0u8; batch.bases.len().max(1)], vec![0u64; n + 1], vec![0u32; n.max(1)], 0u64);
+        // SAFETY: the output arrays are as large as the input's, ref_of holds one entry per read
+        let code = unsafe {
+            zsw_panel_gather_batch(self.raw, &batch.as_c(), ref_of.as_ptr(), k, bases.as_mut_ptr(), offsets.as_mut_ptr(), index.as_mut_ptr(), &mut m, ptr::null_mut())
+        };
+        self.check(code, 0, 0)?;
+        index.truncate(m as usize);
+        Ok(((0..m as usize).map(|j| bases[offsets[j] as usize..offsets[j + 1] as usize].to_vec()).collect(), index))
+    }
+
+    /// `zsw_panel_counts` of the last panel call: reads settled after one score, pairs scored in the first round, pairs scored in
+    /// the second round, reads scored against every member.
+    pub fn panel_counts(&self) -> Result<[u64; 4], GpuError> {
+        let mut c = [0u64; 4];
+        // SAFETY: live context, four entries
+        self.check(unsafe { zsw_panel_counts(self.raw, c.as_mut_ptr()) }, 0, 0)?;
+        Ok(c)
+    }
+
+    /// `zsw_debug_panel_records`: tests only — the panel call reports, per read, the first-choice member, whether the read was
+    /// settled after one score, and per member the support and the whole-reference bound (`2 + 2 * n_refs` `i32` per read in device
+    /// memory; null = off).
+    ///
+    /// # Safety
+    /// `records` must be null or device memory for `(2 + 2 * n_refs) * n_reads` `i32` that outlives the following calls.
+    pub unsafe fn debug_panel_records(&self, records: *mut i32) -> Result<(), GpuError> {
+        self.check(zsw_debug_panel_records(self.raw, records), 0, 0)
     }
 
     /// `zsw_debug_strand_records`: tests only — the strand-aware calls report, per read, the supports, the whole-reference bounds,

@@ -24,6 +24,7 @@ int main(void) {
         (fn)zsw_set_complement, (fn)zsw_score_strands_batch_from, (fn)zsw_orient_batch, (fn)zsw_align_3pass_strands_batch_from,
         (fn)zsw_strand_counts, (fn)zsw_debug_strand_records, (fn)zsw_debug_score_launches, (fn)zsw_min_score_counts, (fn)zsw_annotate_batch, (fn)zsw_sam_batch,
         (fn)zsw_pileup_batch, (fn)zsw_consensus_from_counts, (fn)zsw_fastq_parse_batch, (fn)zsw_sam_parse_batch, (fn)zsw_fasta_parse_batch,
+        (fn)zsw_set_panel, (fn)zsw_score_panel_batch_from, (fn)zsw_panel_gather_batch, (fn)zsw_panel_counts, (fn)zsw_debug_panel_records,
     };
     zsw_context* ctx = NULL;
     zsw_batch b;

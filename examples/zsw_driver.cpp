@@ -5,7 +5,7 @@
 //
 //   g++ -O2 -std=c++17 -Iinclude examples/zsw_driver.cpp -o examples/zsw_driver -Lzoe_amd -lzoe_sw_hip -Wl,-rpath,$PWD/zoe_amd
 //   ./examples/zsw_driver reference.txt reads.fastq [--score-only | --3pass | --both-strands] [--min-score T] [--nm] [--verbose-cigar] [--device-sam]
-//                         [--consensus FILE] [--device-fastq] [--from-sam FILE] [--device-fasta] [--ref-record K] [--fasta-reads]
+//                         [--consensus FILE] [--device-fastq] [--from-sam FILE] [--device-fasta] [--ref-record K] [--fasta-reads] [--panel]
 // --both-strands: every read is aligned on whichever strand scores higher (sw_align_strands_from_i8_3pass); a read answered by
 // its reverse complement gets flag 16, SEQ reverse complemented and QUAL reversed, and POS / CIGAR are those of that sequence.
 // --min-score T (with --3pass or --score-only, the calls ZSW_OPTION_MIN_SCORE covers): a read that scores less than T is written as
@@ -31,6 +31,12 @@
 // status 1 and a message naming the code and the record. On a one-record file the output is the same as without the flag.
 // --fasta-reads: the reads argument is FASTA (contigs, consensus sequences, reads without qualities), parsed on the GPU the same way;
 // QUAL is `*`. It does not go with --device-fastq or --from-sam. Without either flag, code path and output are what they were.
+// --panel: the reference file is multi-record FASTA, read as under --device-fasta, and every record is a member of a reference panel
+// (zsw_set_panel). One zsw_score_panel_batch_from call finds the member each read scores highest against (ties: the first record);
+// then per member with reads: zsw_panel_gather_batch, that member as the reference, sw_align_from_i8_3pass on the group. The lines
+// come out in input order with the member's name as RNAME, after @HD and one @SQ per record: per read the line that
+// `--device-fasta --ref-record K --3pass` writes for the read's best record K (a read unmapped everywhere: record 0's). It goes with
+// --device-fastq and --fasta-reads only.
 #include <algorithm>
 #include <cstdio>
 #include <cstdlib>
@@ -74,10 +80,11 @@ static std::string read_whole(const std::string& path) {
 
 int main(int argc, char** argv) {
     if (argc < 3) {
-        std::cerr << "usage: zsw_driver reference.(fa|txt) reads.fastq [--score-only | --3pass | --both-strands] [--min-score T] [--nm] [--verbose-cigar] [--device-sam] [--consensus FILE] [--device-fastq] [--from-sam FILE] [--device-fasta] [--ref-record K] [--fasta-reads]\n";
+        std::cerr << "usage: zsw_driver reference.(fa|txt) reads.fastq [--score-only | --3pass | --both-strands] [--min-score T] [--nm] [--verbose-cigar] [--device-sam] [--consensus FILE] [--device-fastq] [--from-sam FILE] [--device-fasta] [--ref-record K] [--fasta-reads] [--panel]\n";
         return 2;
     }
     bool score_only = false, three_pass = false, both_strands = false, nm = false, verbose_cigar = false, device_sam = false, device_fastq = false, device_fasta = false, fasta_reads = false;
+    bool panel = false;
     long long min_score = 0, ref_record = 0;
     std::string consensus_path, from_sam;
     for (int k = 3; k < argc; ++k) {
@@ -94,6 +101,7 @@ int main(int argc, char** argv) {
         else if (!std::strcmp(argv[k], "--ref-record") && k + 1 < argc) ref_record = std::atoll(argv[++k]);
         else if (!std::strcmp(argv[k], "--consensus") && k + 1 < argc) consensus_path = argv[++k];
         else if (!std::strcmp(argv[k], "--from-sam") && k + 1 < argc) from_sam = argv[++k];
+        else if (!std::strcmp(argv[k], "--panel")) panel = true;
         else {
             std::cerr << "zsw_driver: unknown argument " << argv[k] << '\n';
             return 2;
@@ -119,6 +127,15 @@ int main(int argc, char** argv) {
         std::cerr << "zsw_driver: --ref-record takes an index from 0 and goes with --device-fasta\n";
         return 2;
     }
+    if (panel && (both_strands || !from_sam.empty() || !consensus_path.empty())) {
+        std::cerr << "zsw_driver: --panel does not go with --both-strands, --from-sam or --consensus\n";
+        return 2;
+    }
+    if (panel && (score_only || min_score > 0 || nm || verbose_cigar || device_sam || ref_record > 0)) {
+        std::cerr << "zsw_driver: --panel writes the plain SAM lines of the 3-pass call; it does not go with --score-only, --min-score, --nm, --verbose-cigar, "
+                     "--device-sam or --ref-record\n";
+        return 2;
+    }
     try {
         std::string ref_name;
         std::unique_ptr<zoe::GpuContext> ctx_holder;
@@ -133,7 +150,13 @@ int main(int argc, char** argv) {
             return fa;
         };
         std::string reference;
-        if (device_fasta) {
+        zoe::FastaRecords panel_fa;  // --panel: every record of the reference file is a member
+        if (panel) {
+            panel_fa = parse_fasta_file(argv[1]);
+            if (panel_fa.sequences.empty() || panel_fa.sequences.size() > ZSW_PANEL_MAX_REFS)
+                throw std::runtime_error("--panel: the file has " + std::to_string(panel_fa.sequences.size()) + " records; a panel holds 1 to " +
+                                         std::to_string(ZSW_PANEL_MAX_REFS));
+        } else if (device_fasta) {
             zoe::FastaRecords fa = parse_fasta_file(argv[1]);
             if ((size_t)ref_record >= fa.sequences.size())
                 throw std::runtime_error("--ref-record " + std::to_string(ref_record) + ": the file has " + std::to_string(fa.sequences.size()) + " records");
@@ -191,6 +214,36 @@ int main(int argc, char** argv) {
         if (min_score > 0) ctx.set_min_score((uint32_t)min_score);
         const zoe::WeightMatrix weights = zoe::WeightMatrix::new_dna_matrix(2, -5, 'N');
         zoe::LocalProfilesBatch profiles(ctx, reads, weights, -10, -1);
+        if (panel) {  // the member each read belongs to from one panel call, then per member the 3-pass call on its gathered group
+            const std::vector<std::string>& members = panel_fa.sequences;
+            ctx.set_panel(members);
+            profiles.sw_score_panel_from_i8();
+            const std::vector<uint32_t> refs = profiles.last_refs();
+            std::vector<std::string> lines(reads.size());
+            for (uint32_t k = 0; k < members.size(); ++k) {
+                std::vector<uint32_t> index;
+                const std::vector<std::string> group = profiles.panel_gather(refs, k, &index);
+                if (group.empty()) continue;
+                zoe::LocalProfilesBatch group_profiles(ctx, group, weights, -10, -1);
+                const auto alns = group_profiles.sw_align_from_i8_3pass(members[k]);
+                for (size_t j = 0; j < group.size(); ++j) {
+                    const size_t i = index[j];
+                    std::ostringstream line;
+                    if (alns[j].is_some()) {
+                        const zoe::Alignment& a = alns[j].value;
+                        line << names[i] << "\t0\t" << panel_fa.names[k] << '\t' << a.ref_start + 1 << "\t255\t" << a.cigar() << "\t*\t0\t0\t" << reads[i] << '\t' << quals[i]
+                             << "\tAS:i:" << a.score << '\n';
+                    } else {
+                        line << names[i] << "\t4\t*\t0\t0\t*\t*\t0\t0\t" << reads[i] << '\t' << quals[i] << '\n';
+                    }
+                    lines[i] = line.str();
+                }
+            }
+            std::cout << "@HD\tVN:1.6\n";
+            for (size_t k = 0; k < members.size(); ++k) std::cout << "@SQ\tSN:" << panel_fa.names[k] << "\tLN:" << members[k].size() << '\n';
+            for (const std::string& line : lines) std::cout << line;
+            return 0;
+        }
         if (score_only) {
             auto scores = profiles.sw_score_from_i8(reference);
             for (size_t i = 0; i < reads.size(); ++i)

@@ -59,6 +59,9 @@ typedef enum zsw_status {
     ZSW_STATUS_BELOW_MIN_SCORE = 4
 } zsw_status;
 
+/* The most members a reference panel holds (zsw_set_panel, below) */
+#define ZSW_PANEL_MAX_REFS 64
+
 /* T of StripedProfile<T,N,S> (AlignableIntWidth, src/math/integer.rs:231-238). Unsigned types run
  * the biased algorithm on matrix.to_biased_matrix() (src/data/matrices/mod.rs:471-491). */
 typedef enum zsw_int_type { ZSW_I8 = 0, ZSW_I16 = 1, ZSW_I32 = 2, ZSW_U8 = 3, ZSW_U16 = 4, ZSW_U32 = 5 } zsw_int_type;
@@ -230,6 +233,57 @@ zsw_error zsw_align_3pass_strands_batch_from(zsw_context* ctx, const zsw_batch* 
  * never scored), out[1] settled on the reverse strand by proof, out[2] scored on both strands, out[3] answered as reverse.
  * out[0] + out[1] + out[2] = the reads of the call. Synchronises the device. */
 zsw_error zsw_strand_counts(zsw_context* ctx, uint64_t* out /* 4 entries */);
+
+/* ---- reference panels: the best of several references -------------------------------------- */
+/* A panel is n_refs sequences r_0 .. r_{n_refs-1}, 1 <= n_refs <= ZSW_PANEL_MAX_REFS — the segments and subtypes of a virus, say,
+ * as zsw_fasta_parse_batch hands them back. The context's scoring applies to all of them; the panel is independent of
+ * zsw_set_reference. With f = zsw_score_batch_from and R_k(i) = f(read_i) with r_k as the reference, the panel result of read i is
+ * R_k(i) of the member k that ranks highest — ZSW_STATUS_OVERFLOWED > ZSW_STATUS_SOME by score > ZSW_STATUS_UNMAPPED =
+ * ZSW_STATUS_EMPTY, as for the strands; ties go to the LOWEST k. out_ref[i] = that k; it is 0 for a read that is UNMAPPED or EMPTY
+ * against every member. Score, status and tier are bit for bit what f returns against r_k, for every input, on every run,
+ * whatever order the device work happens in.
+ * The library does not score every read against every member: k-mers of the read looked up in each member's index
+ * bound what the read can score against that member at all, the most promising member is scored first, and another member only if
+ * its bound does not already rank it below (or level, from a higher k). Same results for every input; ZSW_OPTION_EXACT_PRUNING = 0,
+ * or a matrix the index cannot serve, scores every read against every member.
+ * Not covered: zsw_group_*, the shared-profile role, panel forms of the ends, ranges, direct (one <T, N>) and alignment calls (take
+ * the group of a member with zsw_panel_gather_batch, zsw_set_reference that member and use any entry point on the group), strand
+ * and panel in one call, ZSW_OPTION_MIN_SCORE, ZSW_ENCODING_PACKED4. */
+
+/* The panel: member k is seqs[offsets[k] .. offsets[k + 1]) — exactly the `sequences` / `seq_offsets` arrays of
+ * zsw_fasta_parse_batch. Both arrays lie in host or in device memory (`mem`); device arrays are taken where they lie, as
+ * zsw_set_reference(.., ZSW_MEM_DEVICE) takes a reference. Errors: n_refs of 0 or above ZSW_PANEL_MAX_REFS and offsets that are
+ * not ascending (ZSW_ERR_INVALID_ARGUMENT), a member of length 0 (ZSW_ERR_EMPTY_SEQUENCE); the panel set before stays as it is.
+ * The context keeps a device copy and a host copy of the members and an index per member, built with the first panel call that can
+ * use it and rebuilt after zsw_set_scoring; everything is released in zsw_destroy. Replacing a panel synchronises the device. */
+zsw_error zsw_set_panel(zsw_context* ctx, const uint8_t* seqs, const uint64_t* offsets /* n_refs + 1 */, uint32_t n_refs, zsw_mem mem);
+
+/* zsw_score_batch_from under the contract above; out_tier is optional, out_ref is not. Host and device batches, fixed and ragged,
+ * ZSW_ENCODING_BYTES; ZSW_ENCODING_PACKED4 returns ZSW_ERR_UNSUPPORTED, and so does the call while ZSW_OPTION_MIN_SCORE is on.
+ * ZSW_ERR_NOT_CONFIGURED if no panel or no scoring is set. n_refs = 1 is the plain call with out_ref all 0.
+ * The call synchronises the stream twice: for the sizes of the groups of the first round (the reads by their first-choice member)
+ * and for the lengths of the lists of the second round (per member, the reads it still has to be scored for) — and, like every
+ * call, once more for a ragged device batch, whose size comes back from the device, and once per scored group of such a batch,
+ * whose longest read does. Device workspace: 2 * n_refs + 13 bytes per read, a compact copy of the largest group and its results
+ * (9 bytes per read) — for a host batch also the staged batch itself and its results; kept by the context until zsw_destroy.
+ * A host batch crosses PCIe whole, in one copy, before the first kernel, and stays on the device for both rounds.
+ * After the call zsw_prune_rescored reports on the last score pass the call ran, as after a strand-aware call. */
+zsw_error zsw_score_panel_batch_from(zsw_context* ctx, const zsw_batch* reads, int from_width, int preset_bits, uint32_t* out_score,
+                                     uint8_t* out_status, uint8_t* out_tier, uint32_t* out_ref, void* stream);
+
+/* The panel's zsw_orient_batch: the reads with ref_of[i] == k, in input order, as a batch of the input's layout — out_bases, and
+ * for a ragged batch out_offsets (*out_n + 1 entries; NULL for a fixed-length batch); out_index[j] = the input read the j-th
+ * output read is, *out_n their number. The output arrays are the caller's, as large as the input's (out_index: one entry per read),
+ * and live where reads->mem says, as ref_of does; a device batch is processed on the device (one synchronisation, for *out_n), a
+ * host batch on the host. Needs neither scoring nor panel. ZSW_ENCODING_PACKED4 returns ZSW_ERR_UNSUPPORTED. With it any entry
+ * point (3-pass, ranges, annotate, pile-up) runs per member: zsw_set_reference on member k, then the call on the group of k. */
+zsw_error zsw_panel_gather_batch(zsw_context* ctx, const zsw_batch* reads, const uint32_t* ref_of, uint32_t k, uint8_t* out_bases,
+                                 uint64_t* out_offsets, uint32_t* out_index, uint64_t* out_n, void* stream);
+
+/* Counters of the context's last panel score call: out[0] reads settled after one score (every other member was ruled out by
+ * proof; with n_refs = 1 every read), out[1] (read, member) pairs scored in the first round = the reads of the call, out[2] pairs
+ * scored in the second round, out[3] reads scored against every member. No device work: the call itself has read them. */
+zsw_error zsw_panel_counts(zsw_context* ctx, uint64_t* out /* 4 entries */);
 
 /* ---- shared profile: one profile, many sequences ------------------------------------------- */
 /* The other role of the striped functions (sw/mod.rs:63-67: "the profile can be aligned against any number of different
@@ -924,6 +978,16 @@ zsw_error zsw_debug_threepass_records(zsw_context* ctx, int32_t* records);
  * 8 int32 per read of the following calls, NULL = off (the default). Results do not change. */
 zsw_error zsw_debug_strand_records(zsw_context* ctx, int32_t* records);
 
+/* Tests only (tests/test_gpu_panel.py): zsw_score_panel_batch_from (zsw_panel.hip) writes, for every read, 2 + 2 * n_refs int32 into
+ * records[(2 + 2 * n_refs) * read]: [0] the first-choice member (the largest support of the anchor vote, ties to the lowest member),
+ * [1] 1 = settled after one score (every other member ruled out by proof), else 0, [2 .. 2 + n_refs) the supports of the anchor
+ * vote per member, [2 + n_refs .. 2 + 2 * n_refs) the whole-reference bounds per member (no local alignment of the read against
+ * that member scores more; -1: no bound). The host model (tests/models/panel_bound.cpp) computes all but [1] from the read, and [1]
+ * from the score against the first choice; the test requires equality. Without a usable index: first choice 0, supports 0, bounds
+ * -1. records: device memory for 2 + 2 * n_refs int32 per read of the following calls, NULL = off (the default). Results do not
+ * change. */
+zsw_error zsw_debug_panel_records(zsw_context* ctx, int32_t* records);
+
 /* Tests only (tests/test_gpu_strip_edges.py): which score kernels the context's last call launched. The score launchers
  * (launch_score and launch_score_rev, zsw_score.hip) note every kernel launch they issue in a host-side list that is emptied
  * when a call stages its batch; no device work, no synchronisation, results do not change. A record is four uint32:
@@ -966,7 +1030,8 @@ zsw_error zsw_debug_score_launches(zsw_context* ctx, uint32_t* records, uint32_t
  * Shared-profile role: zsw_score_shared_batch(_from) count the hand-backs of the role-swapped pass in the same way; the ends,
  * ranges and alignment calls of that role report 0, because their seeded passes rescore nothing — a read handed back joins the
  * reads with ties under the shared role's own kernel. After a strand-aware call: the hand-backs of the LAST score pass it ran —
- * the pass over the second batch (the reads scored on both strands), or the first pass if no read needed its other strand.
+ * the pass over the second batch (the reads scored on both strands), or the first pass if no read needed its other strand. After a panel call likewise: the hand-backs of the LAST score pass it ran —
+ * the last member's list of the second round, or the last group of the first round if no read needed a second member.
  * Diagnostics for tests and bench.py. */
 zsw_error zsw_prune_rescored(zsw_context* ctx, uint64_t* out_reads);
 

@@ -238,6 +238,24 @@ class GpuContext {
         check(zsw_min_score_counts(ctx_, c.data()));
         return c;
     }
+    // zsw_set_panel: the members of a reference panel (1 .. ZSW_PANEL_MAX_REFS non-empty sequences), independent of the reference
+    void set_panel(const std::vector<std::string>& members) {
+        std::vector<uint8_t> seqs;
+        std::vector<uint64_t> offsets(1, 0);
+        for (const std::string& m : members) {
+            seqs.insert(seqs.end(), m.begin(), m.end());
+            offsets.push_back(seqs.size());
+        }
+        seqs.push_back(0);
+        check(zsw_set_panel(ctx_, seqs.data(), offsets.data(), (uint32_t)members.size(), ZSW_MEM_HOST));
+    }
+    // zsw_panel_counts of the last panel call: reads settled after one score, pairs scored in the first / second round, reads
+    // scored against every member
+    std::vector<uint64_t> panel_counts() const {
+        std::vector<uint64_t> c(4, 0);
+        check(zsw_panel_counts(ctx_, c.data()));
+        return c;
+    }
     void check(zsw_error e) const {
         if (e == ZSW_OK) return;
         if (e >= 1 && e <= 4) throw ProfileError(e);
@@ -722,10 +740,44 @@ class LocalProfilesBatch : public ProfileBatchBase {
         for (size_t i = 0; i < size(); ++i) reads[i].assign(out.begin() + offsets_[i], out.begin() + offsets_[i + 1]);
         return reads;
     }
+    // Reference panels (zsw_score_panel_batch_from): per read sw_score_from_i{8,16,32} against the member of the context's panel
+    // (GpuContext::set_panel) that ranks highest, ties to the lowest member; last_refs() says which it was
+    std::vector<MaybeAligned<uint32_t>> sw_score_panel_from_i8() { return score_panel_from(8); }
+    std::vector<MaybeAligned<uint32_t>> sw_score_panel_from_i16() { return score_panel_from(16); }
+    std::vector<MaybeAligned<uint32_t>> sw_score_panel_from_i32() { return score_panel_from(32); }
+    // the member that answered each read of the last panel call
+    const std::vector<uint32_t>& last_refs() const { return ref_; }
+    // the reads with ref_of[i] == k, in input order (zsw_panel_gather_batch); index: which input read each of them is
+    std::vector<std::string> panel_gather(const std::vector<uint32_t>& ref_of, uint32_t k, std::vector<uint32_t>* index = nullptr) {
+        if (ref_of.size() != size()) throw GpuError(ZSW_ERR_INVALID_ARGUMENT, "one member per read");
+        zsw_batch b = batch();
+        std::vector<uint8_t> out(bases_.size() + 1);
+        std::vector<uint64_t> off(size() + 1);
+        std::vector<uint32_t> idx(size() + 1);
+        uint64_t m = 0;
+        ctx_.check(zsw_panel_gather_batch(ctx_.raw(), &b, ref_of.data(), k, out.data(), off.data(), idx.data(), &m, nullptr));
+        std::vector<std::string> reads(m);
+        for (size_t j = 0; j < m; ++j) reads[j].assign(out.begin() + off[j], out.begin() + off[j + 1]);
+        idx.resize(m);
+        if (index) index->swap(idx);
+        return reads;
+    }
     // the width that answered each read of the last cascade call (8, 16 or 32)
     const std::vector<uint8_t>& last_tiers() const { return tier_; }
 
   private:
+    std::vector<MaybeAligned<uint32_t>> score_panel_from(int width) {
+        const size_t n = size();
+        zsw_batch b = batch();
+        std::vector<uint32_t> score(n);
+        std::vector<uint8_t> status(n);
+        tier_.assign(n, 0);
+        ref_.assign(n, 0);
+        ctx_.check(zsw_score_panel_batch_from(ctx_.raw(), &b, width, preset_, score.data(), status.data(), tier_.data(), ref_.data(), nullptr));
+        std::vector<MaybeAligned<uint32_t>> out(n);
+        for (size_t i = 0; i < n; ++i) out[i] = {(Status)status[i], score[i]};
+        return out;
+    }
     std::vector<MaybeAligned<Alignment>> align_from(const std::string& seq, bool seq_is_query, int width, bool three_pass) {
         set_reference(seq);
         zsw_batch b = batch();
@@ -785,6 +837,7 @@ class LocalProfilesBatch : public ProfileBatchBase {
     }
     int preset_;
     std::vector<uint8_t> tier_, strand_;
+    std::vector<uint32_t> ref_;
 };
 
 // The other role of the striped functions (sw/mod.rs:63-67; SharedProfiles, profile_set.rs:552-560;

@@ -56,7 +56,9 @@ SYMBOLS = [
     "zsw_set_complement", "zsw_score_strands_batch_from", "zsw_orient_batch", "zsw_align_3pass_strands_batch_from", "zsw_strand_counts", "zsw_debug_strand_records", "zsw_debug_score_launches",
     "zsw_min_score_counts", "zsw_annotate_batch", "zsw_sam_batch", "zsw_pileup_batch", "zsw_consensus_from_counts", "zsw_fastq_parse_batch",
     "zsw_sam_parse_batch", "zsw_fasta_parse_batch",
+    "zsw_set_panel", "zsw_score_panel_batch_from", "zsw_panel_gather_batch", "zsw_panel_counts", "zsw_debug_panel_records",
 ]
+PANEL_MAX_REFS = 64
 
 
 class ZswBatch(C.Structure):
@@ -266,5 +268,10 @@ def load() -> C.CDLL:
     lib.zsw_fastq_parse_batch.argtypes = [vp, u8p, C.c_uint64, C.c_int, C.c_int, u8p, u8p, C.c_uint64, u64p, u8p, C.c_uint64, u64p, C.c_uint64, C.POINTER(C.c_uint64), vp]
     lib.zsw_sam_parse_batch.argtypes = [vp, u8p, C.c_uint64, C.c_int, C.c_int, C.c_char_p, C.c_uint32, C.c_uint32, C.POINTER(ZswSamParseOut), C.POINTER(C.c_uint64), vp]
     lib.zsw_fasta_parse_batch.argtypes = [vp, u8p, C.c_uint64, C.c_int, C.c_int, u8p, C.c_uint64, u64p, u8p, C.c_uint64, u64p, C.c_uint64, C.POINTER(C.c_uint64), vp]
+    lib.zsw_set_panel.argtypes = [vp, u8p, u64p, C.c_uint32, C.c_int]
+    lib.zsw_score_panel_batch_from.argtypes = [vp, C.POINTER(ZswBatch), C.c_int, C.c_int, u32p, u8p, u8p, u32p, vp]
+    lib.zsw_panel_gather_batch.argtypes = [vp, C.POINTER(ZswBatch), u32p, C.c_uint32, u8p, u64p, u32p, C.POINTER(C.c_uint64), vp]
+    lib.zsw_panel_counts.argtypes = [vp, C.POINTER(C.c_uint64)]
+    lib.zsw_debug_panel_records.argtypes = [vp, vp]
     _lib = lib
     return lib

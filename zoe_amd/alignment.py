@@ -362,6 +362,61 @@ class SwContext:
         self.check(self.lib.zsw_strand_counts(self.h, c))
         return tuple(int(x) for x in c)
 
+    def set_panel(self, seqs) -> int:
+        """zsw_set_panel: the members of a reference panel (1 .. _lib.PANEL_MAX_REFS non-empty sequences), independent of
+        `set_reference`. `seqs`: a list of byte strings, or the `FastaDeviceBatch` of `records.fasta_batch_from_text` — every record a
+        member, taken from device memory where it lies. Returns the number of members."""
+        if hasattr(seqs, "bases") and hasattr(seqs, "offsets") and hasattr(seqs, "n_records"):
+            n = int(seqs.n_records)
+            bases, off = seqs.bases.contiguous(), seqs.offsets.contiguous()
+            assert bases.is_cuda and off.is_cuda and off.dtype == _torch().int64 and off.numel() >= n + 1
+            self.check(self.lib.zsw_set_panel(self.h, bases.data_ptr(), off.data_ptr(), n, _lib.MEM_DEVICE), profile_errors=False)
+            self._panel_size = n
+            return n
+        seqs = [bytes(s) for s in seqs]
+        cat = np.frombuffer(b"".join(seqs) or b"\0", dtype=np.uint8)
+        off = np.zeros(len(seqs) + 1, dtype=np.uint64)
+        np.cumsum([len(s) for s in seqs], out=off[1:])
+        self.check(self.lib.zsw_set_panel(self.h, cat.ctypes.data, off.ctypes.data, len(seqs), _lib.MEM_HOST), profile_errors=False)
+        self._panel_size = len(seqs)
+        return len(seqs)
+
+    def panel_counts(self):
+        """zsw_panel_counts of the last panel call: (reads settled after one score, (read, member) pairs scored in the first round,
+        pairs scored in the second round, reads scored against every member)."""
+        c = (C.c_uint64 * 4)()
+        self.check(self.lib.zsw_panel_counts(self.h, c))
+        return tuple(int(x) for x in c)
+
+    def debug_panel_records(self, records=None):
+        """zsw_debug_panel_records (tests): the panel call writes 2 + 2 * n_refs int32 per read — the first-choice member, 1 = settled
+        after one score, the n_refs supports of the anchor vote, the n_refs whole-reference bounds (-1: none) — into `records` (a
+        CUDA int32 tensor of (2 + 2 * n_refs) * n_reads elements that the caller keeps alive); None switches it off."""
+        if records is not None:
+            assert records.is_cuda and records.dtype == _torch().int32 and records.is_contiguous()
+        self._panel_records = records
+        self.check(self.lib.zsw_debug_panel_records(self.h, C.c_void_p(records.data_ptr() if records is not None else None)))
+
+    def panel_gather(self, reads: "ReadBatch", ref_of, k: int):
+        """zsw_panel_gather_batch: (the reads with ref_of[i] == k as a ReadBatch of the input's layout, in input order; a CUDA int32
+        tensor with the input read each of them is). `ref_of`: a CUDA int32 tensor with one entry per read, e.g. `ScoreBatch.ref`."""
+        torch = _torch()
+        assert ref_of.is_cuda and ref_of.dtype == torch.int32 and ref_of.numel() >= reads.n_reads
+        ref_of = ref_of.contiguous()
+        n = reads.n_reads
+        dev = reads.bases.device
+        out = torch.empty_like(reads.bases)
+        index = torch.empty(max(n, 1), dtype=torch.int32, device=dev)
+        off = torch.empty(n + 1, dtype=torch.int64, device=dev) if reads.offsets is not None else None
+        m = C.c_uint64(0)
+        b = reads.c_batch()
+        self.check(self.lib.zsw_panel_gather_batch(self.h, C.byref(b), ref_of.data_ptr(), int(k), out.data_ptr(), off.data_ptr() if off is not None else None,
+                                                   index.data_ptr(), C.byref(m), self.stream()), profile_errors=False)
+        m = int(m.value)
+        if off is None:
+            return ReadBatch(out[:max(m * reads.fixed_len, 1)], m, fixed_len=reads.fixed_len, min_len=reads.fixed_len), index[:m]
+        return ReadBatch(out, m, offsets=off[:m + 1]), index[:m]
+
     def set_profile_sequence(self, sequence: bytes):
         """zsw_set_profile_sequence: the sequence the shared profile is built from (the library itself skips the work when it is the
         one already set: no copy of it is kept on this side, which another binding of the same context could leave stale)"""
@@ -572,6 +627,7 @@ class ScoreBatch:
     ref_start: Optional["object"] = None
     query_start: Optional["object"] = None
     strand: Optional["object"] = None  # strand-aware calls: 0 = the read as given, 1 = its reverse complement
+    ref: Optional["object"] = None  # panel calls: the member of the panel that answered (int32)
 
     def maybe_aligned(self, i: int):
         st = int(self.status[i])
@@ -1065,6 +1121,29 @@ class LocalProfilesBatch(_ProfileBatchBase):
 
     def sw_score_strands_from_i32(self, reference) -> ScoreBatch:
         return self._score_strands_from(reference, 32)
+
+    def _score_panel_from(self, width: int) -> ScoreBatch:
+        """zsw_score_panel_batch_from: per read sw_score_from_i{width} against the member of the context's panel
+        (`SwContext.set_panel`) that ranks highest, ties to the lowest member; ScoreBatch.ref says which one answered."""
+        torch = _torch()
+        self.ctx.set_scoring(self.matrix, self.gap_open, self.gap_extend)
+        n = self.reads.n_reads
+        dev = self.reads.bases.device
+        score, ref = (torch.empty(max(n, 1), dtype=torch.int32, device=dev) for _ in range(2))
+        status, tier = (torch.empty(max(n, 1), dtype=torch.uint8, device=dev) for _ in range(2))
+        b = self.reads.c_batch()
+        self.ctx.check(self.ctx.lib.zsw_score_panel_batch_from(self.ctx.h, C.byref(b), width, self.preset, score.data_ptr(), status.data_ptr(),
+                                                               tier.data_ptr(), ref.data_ptr(), self.ctx.stream()))
+        return ScoreBatch(score[:n], status[:n], tier=tier[:n], ref=ref[:n])
+
+    def sw_score_panel_from_i8(self) -> ScoreBatch:
+        return self._score_panel_from(8)
+
+    def sw_score_panel_from_i16(self) -> ScoreBatch:
+        return self._score_panel_from(16)
+
+    def sw_score_panel_from_i32(self) -> ScoreBatch:
+        return self._score_panel_from(32)
 
     def sw_align_strands_from_i8_3pass(self, seq: SeqSrc) -> AlignmentBatch:
         """zsw_align_3pass_strands_batch_from: sw_align_from_i8_3pass of the read or of its reverse complement, whichever scores

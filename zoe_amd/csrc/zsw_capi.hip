@@ -342,21 +342,21 @@ zsw_error unstage(zsw_context* ctx, const zsw_batch* reads, hipStream_t stream, 
 constexpr uint32_t PIPE_CHUNK = 4'000'000;  // reads per chunk of the host-batch pipeline (600 MB at 150 bp; fewer, larger chunks keep the kernels near their large-batch rate)
 constexpr uint32_t PIPE_FIRST = 500'000;    // ... and of its first chunk, whose copy nothing hides
 
-zsw_error run_score(zsw_context* ctx, const zsw_batch* reads, const ResultRule& rule, const ScoreDest& dest, void* stream_) {
+zsw_error run_score(zsw_context* ctx, const Against& target, const zsw_batch* reads, const ResultRule& rule, const ScoreDest& dest, void* stream_) {
     DeviceGuard device_guard(ctx);
     hipStream_t stream = (hipStream_t)stream_;
     Staged st;
     // fixed-length host batches of more than one chunk: the H2D copy of chunk k+1 overlaps the kernel of chunk k
     const bool pipelined = reads && reads->mem == ZSW_MEM_HOST && !reads->offsets && reads->fixed_len > 0 &&
                            reads->n_reads > PIPE_CHUNK && !(ctx && (ctx->flags() & ZSW_DEBUG_NO_PIPELINE));
-    zsw_error ze = stage(ctx, against_reference(ctx), reads, &dest, stream, &st, pipelined);
+    zsw_error ze = stage(ctx, target, reads, &dest, stream, &st, pipelined);
     if (ze != ZSW_OK) return ze;
     if (reads->n_reads == 0) return ZSW_OK;
     const ScoreOut out = score_out(ctx, st.dev);
     const int mode = dest.ends() ? 2 : 0;
     if (!pipelined) {
-        hipError_t e = launch_score(ctx->d_sc.as<ScoringDev>(), ctx->h_sc, st.b, st.max_len, ctx->d_ref.as<uint8_t>(),
-                                    (uint32_t)ctx->ref_len, rule, out, score_ws(ctx, st), stream, &ctx->timer, mode);
+        hipError_t e = launch_score(target.d_sc, *target.h_sc, st.b, st.max_len, target.d_seq, (uint32_t)target.len, rule, out, score_ws(ctx, st), stream,
+                                    &ctx->timer, mode);
         if (e != hipSuccess) return fail(ctx, ZSW_ERR_HIP, "score launch", e);
         return unstage(ctx, reads, stream, st, dest);
     }
@@ -408,8 +408,8 @@ zsw_error run_score(zsw_context* ctx, const zsw_batch* reads, const ResultRule& 
         if (out.tier) ok.tier = out.tier + first;
         if (out.ref_end) ok.ref_end = out.ref_end + first;
         if (out.query_end) ok.query_end = out.query_end + first;
-        hipError_t e = launch_score(ctx->d_sc.as<ScoringDev>(), ctx->h_sc, bk, st.max_len, ctx->d_ref.as<uint8_t>(),
-                                    (uint32_t)ctx->ref_len, rule, ok, score_ws(ctx, st), stream, &ctx->timer, mode);
+        hipError_t e = launch_score(target.d_sc, *target.h_sc, bk, st.max_len, target.d_seq, (uint32_t)target.len, rule, ok, score_ws(ctx, st), stream,
+                                    &ctx->timer, mode);
         if (e != hipSuccess) return fail(ctx, ZSW_ERR_HIP, "score launch", e);
         if (k + 1 < n_chunks) ZSW_HIP(ctx, copy_chunk(k + 1));  // issued after the launch: it runs under chunk k's kernel
         ZSW_HIP(ctx, results_back(k));
@@ -1125,6 +1125,7 @@ void zsw_destroy(zsw_context* ctx) {
     ctx->d_ref_rev.release();
     seed_index_release(&ctx->seed_shared);
     seed_index_release(&ctx->seed_shared_rev);
+    panel_release(ctx);
     ctx->timer.destroy();
     ctx->timer_window.destroy();
     if (ctx->side) {
@@ -1183,6 +1184,7 @@ zsw_error zsw_set_scoring(zsw_context* ctx, const int8_t* weights, int S, const 
     ctx->seed_rev.valid = false;
     ctx->seed_shared.valid = false;
     ctx->seed_shared_rev.valid = false;
+    panel_invalidate(ctx);
     return ZSW_OK;
 }
 
@@ -1211,14 +1213,14 @@ zsw_error zsw_score_batch(zsw_context* ctx, const zsw_batch* reads, zsw_int_type
                           uint32_t* out_score, uint8_t* out_status, void* stream) {
     ResultRule rule;
     if (zsw_error ze = rule_direct(ctx, int_type, lanes, &rule); ze != ZSW_OK) return ze;
-    return run_score(ctx, reads, rule, {out_score, out_status, nullptr, nullptr, nullptr}, stream);
+    return run_score(ctx, against_reference(ctx), reads, rule, {out_score, out_status, nullptr, nullptr, nullptr}, stream);
 }
 
 zsw_error zsw_score_batch_from(zsw_context* ctx, const zsw_batch* reads, int from_width, int preset_bits,
                                uint32_t* out_score, uint8_t* out_status, uint8_t* out_tier, void* stream) {
     ResultRule rule;
     if (zsw_error ze = rule_cascade(ctx, from_width, preset_bits, &rule); ze != ZSW_OK) return ze;
-    return run_score(ctx, reads, rule, {out_score, out_status, out_tier, nullptr, nullptr}, stream);
+    return run_score(ctx, against_reference(ctx), reads, rule, {out_score, out_status, out_tier, nullptr, nullptr}, stream);
 }
 
 zsw_error zsw_score_ends_batch(zsw_context* ctx, const zsw_batch* reads, zsw_int_type int_type, int lanes,
@@ -1228,7 +1230,7 @@ zsw_error zsw_score_ends_batch(zsw_context* ctx, const zsw_batch* reads, zsw_int
     if (!out_ref_end || !out_query_end) return fail(ctx, ZSW_ERR_INVALID_ARGUMENT, "null argument");
     ResultRule rule;
     if (zsw_error ze = rule_direct(ctx, int_type, lanes, &rule); ze != ZSW_OK) return ze;
-    return run_score(ctx, reads, rule, {out_score, out_status, nullptr, out_ref_end, out_query_end}, stream);
+    return run_score(ctx, against_reference(ctx), reads, rule, {out_score, out_status, nullptr, out_ref_end, out_query_end}, stream);
 }
 
 zsw_error zsw_score_ranges_batch(zsw_context* ctx, const zsw_batch* reads, zsw_int_type int_type, int lanes,

@@ -39,6 +39,8 @@ struct DevBuf {
     template <typename T> T* as() { return reinterpret_cast<T*>(p); }
 };
 
+struct Panel;  // zsw_panel.hpp
+
 }  // namespace zsw
 
 struct zsw_context {
@@ -114,6 +116,10 @@ struct zsw_context {
     zsw::DevBuf st_ws[24];
     std::vector<uint8_t> h_orient;
     int32_t* strand_dbg = nullptr;  // zsw_debug_strand_records
+    // reference panels (zsw_panel.hip, zsw_panel.hpp): the members of zsw_set_panel with an index each, the workspace of the panel
+    // calls and the counters of the last one; null until zsw_set_panel
+    zsw::Panel* panel = nullptr;
+    int32_t* panel_dbg = nullptr;  // zsw_debug_panel_records
     // zsw_annotate_batch (zsw_annotate.hip): the staged arrays of a host call, the verbose ciglet counts and their exclusive sum
     zsw::DevBuf an_ws[16];
     // zsw_sam_batch (zsw_sam.hip): the staged arrays of a host call, RNAME, the line lengths / starts, the lines' shapes, the text
@@ -379,8 +385,12 @@ inline ScoreOut score_out(zsw_context* ctx, const ScoreDest& d) {
     return o;
 }
 
-// zsw_capi.hip: the bodies of zsw_score_batch(_from) and zsw_align_3pass_batch(_from), which the strand-aware calls run on oriented batches
-zsw_error run_score(zsw_context* ctx, const zsw_batch* reads, const ResultRule& rule, const ScoreDest& dest, void* stream);
+// zsw_capi.hip: the bodies of zsw_score_batch(_from) and zsw_align_3pass_batch(_from), which the strand-aware calls run on oriented
+// batches and the panel call on the groups of a batch, each against its member (`target`)
+zsw_error run_score(zsw_context* ctx, const Against& target, const zsw_batch* reads, const ResultRule& rule, const ScoreDest& dest, void* stream);
+// zsw_panel.hip: the context's panel after zsw_set_scoring (its indices spell k-mers with the matrix's good residues), in zsw_destroy
+void panel_invalidate(zsw_context* ctx);
+void panel_release(zsw_context* ctx);
 zsw_error run_threepass(zsw_context* ctx, const zsw_batch* reads, const ResultRule& rule, int invert, const AlignDest& dest, void* stream);
 // zsw_capi.hip. dest: null = the results stay in library workspace (ranges, alignments): no staging of score / status
 zsw_error stage(zsw_context* ctx, const Against& target, const zsw_batch* reads, const ScoreDest* dest, hipStream_t stream, Staged* st,

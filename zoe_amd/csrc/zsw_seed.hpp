@@ -415,6 +415,25 @@ ZSW_SEED_HD bool seed_strand_settled(bool some_p, long long s_p, long long u_o, 
     return u_o < s_p || (u_o == s_p && p == 0);
 }
 
+// The panel decision (zsw_panel.hip): member p of a panel ran first and scored s_p (some_p: its status is SOME), u_k bounds
+// what the read scores against member k != p. True = k need not be scored: it ranks below p, or can at most tie it while k > p
+// (ties go to the lowest member). u_k < 0: no bound.
+ZSW_SEED_HD bool seed_panel_ruled_out(bool some_p, long long s_p, long long u_k, int p, int k) {
+    if (!some_p || u_k < 0) return false;
+    return u_k < s_p || (u_k == s_p && k > p);
+}
+// The members of a panel of n_refs still to score once p has: bit k set for every k != p the rule does not rule out.
+// u16[k]: member k's bound as seed_bound_u16 stores it (0xffff: none).
+ZSW_SEED_HD unsigned long long seed_panel_todo(int n_refs, int p, bool some_p, long long s_p, const uint16_t* u16) {
+    unsigned long long todo = 0;
+    for (int k = 0; k < n_refs; ++k) {
+        if (k == p) continue;
+        const uint32_t u = u16[k];
+        if (!seed_panel_ruled_out(some_p, s_p, u == 0xffffu ? -1ll : (long long)u, p, k)) todo |= 1ull << k;
+    }
+    return todo;
+}
+
 // ---- banded pass (seed_band_kernel): the computed cells are a band of diagonals around the anchor, strip by strip ----------
 // Strip k holds query columns [kC, (k+1)C) and the reference rows [top_k, bot_k) = [dt + kC - Wu, dt + (k+1)C + Wd) (clamped to
 // the reference; dt = the smaller / larger anchor of the lane's two reads). Cells of a strip's columns in rows < top_k lie ABOVE

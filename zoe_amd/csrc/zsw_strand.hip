@@ -323,7 +323,7 @@ zsw_error score_strands_device(zsw_context* ctx, const zsw_batch* reads, size_t 
         hipLaunchKernelGGL(strand_nobound_kernel, dim3(g256), dim3(256), 0, stream, n, meta, ctx->strand_dbg);  // every read runs forward first
         ZSW_HIP(ctx, hipGetLastError());
     }
-    zsw_error ze = run_score(ctx, &first, rule, {d_score, d_status, d_tier, nullptr, nullptr}, stream);
+    zsw_error ze = run_score(ctx, against_reference(ctx), &first, rule, {d_score, d_status, d_tier, nullptr, nullptr}, stream);
     if (ze != ZSW_OK) return ze;
     SettleArgs se;
     se.n = n;
@@ -375,7 +375,7 @@ zsw_error score_strands_device(zsw_context* ctx, const zsw_batch* reads, size_t 
         second.offsets = offs;
     }
     ZSW_HIP(ctx, launch_orient(o, stream));
-    ze = run_score(ctx, &second, rule, {ws[ST_S2_SCORE].as<uint32_t>(), ws[ST_S2_STATUS].as<uint8_t>(), ws[ST_S2_TIER].as<uint8_t>(), nullptr, nullptr}, stream);
+    ze = run_score(ctx, against_reference(ctx), &second, rule, {ws[ST_S2_SCORE].as<uint32_t>(), ws[ST_S2_STATUS].as<uint8_t>(), ws[ST_S2_TIER].as<uint8_t>(), nullptr, nullptr}, stream);
     if (ze != ZSW_OK) return ze;
     MergeArgs m;
     m.n2 = n2;
