@@ -933,7 +933,15 @@ typedef enum zsw_debug_flag {
      * By default a wavefront of a one-length batch whose walks all stay inside the reference (zsw_seed_diag.hpp:
      * diag_walk_is_interior) takes a copy of the column loop without the masks, and a wavefront whose lane partners all share
      * their anchor skips the sixteenth diagonal's cell */
-    ZSW_DEBUG_SEED_DIAG_MASKED = 1048576
+    ZSW_DEBUG_SEED_DIAG_MASKED = 1048576,
+    /* score: the whole list the seed kernel hands back is scored in the first tier's launch. By default a one-length call of
+     * 2,097,152 reads or more whose list is longer than a round of that launch (98,304 reads) and a slice cuts the last 16,384
+     * reads off it, which run as a launch of score_kernel_v2 on a side stream beside the second tier (zsw_handback.hpp:
+     * handback_slices) */
+    ZSW_DEBUG_SEED_NO_SLICES = 2097152,
+    /* score: slices at any batch size, for the tests: the last 128 reads of the list (if it has as many), and up to 128 reads in
+     * front of them as a second slice beside the sort (zsw_handback.hpp: HANDBACK_TINY_*) */
+    ZSW_DEBUG_SEED_TINY_SLICES = 4194304
 } zsw_debug_flag;
 zsw_error zsw_debug_set(zsw_context* ctx, uint32_t flags);
 

@@ -35,6 +35,8 @@ DEBUG_SEED_DIAG_LANE_EVENTS = 131072
 DEBUG_SEED_NO_COSCHEDULE = 262144
 DEBUG_SEED_PLAIN_KERNEL = 524288
 DEBUG_SEED_DIAG_MASKED = 1048576
+DEBUG_SEED_NO_SLICES = 2097152
+DEBUG_SEED_TINY_SLICES = 4194304
 # zsw_launch_kind: the first entry of a zsw_debug_score_launches record
 (LAUNCH_V1_FAST, LAUNCH_V1_BIASED, LAUNCH_V2, LAUNCH_WIDE, LAUNCH_V1_FAST_REV, LAUNCH_V1_BIASED_REV, LAUNCH_WIDE_REV, LAUNCH_TILE_V2, LAUNCH_TILE_WIDE,
  LAUNCH_TILE_W32, LAUNCH_EXACT32, LAUNCH_EXACT32_WORKLIST, LAUNCH_SEED_WINDOW, LAUNCH_SEED_BAND, LAUNCH_PRUNED, LAUNCH_ROW_CHUNKS) = range(16)

@@ -12,7 +12,7 @@ import sys
 HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, "csrc")
 LIB = os.path.join(HERE, "libzoe_sw_hip.so")
-SOURCES = ["zsw_capi.hip", "zsw_capi_shared.hip", "zsw_shared.hip", "zsw_score.hip", "zsw_align.hip", "zsw_align_pk8.hip", "zsw_align_pk16.hip", "zsw_align_pk32.hip", "zsw_align_pk64.hip", "zsw_group.hip", "zsw_threepass.hip", "zsw_filter.hip", "zsw_score_wide.hip", "zsw_score_w32.hip", "zsw_score_prune.hip", "zsw_score_seed.hip", "zsw_score_seed_m0.hip", "zsw_score_seed_m1.hip", "zsw_score_seed_m2.hip", "zsw_score_band.hip", "zsw_multi.hip", "zsw_strand.hip", "zsw_panel.hip", "zsw_annotate.hip", "zsw_sam.hip", "zsw_pileup.hip", "zsw_text.hip", "zsw_fastq.hip", "zsw_samtext.hip", "zsw_fasta.hip"]
+SOURCES = ["zsw_capi.hip", "zsw_capi_shared.hip", "zsw_shared.hip", "zsw_score.hip", "zsw_align.hip", "zsw_align_pk8.hip", "zsw_align_pk16.hip", "zsw_align_pk32.hip", "zsw_align_pk64.hip", "zsw_group.hip", "zsw_threepass.hip", "zsw_filter.hip", "zsw_score_wide.hip", "zsw_score_w32.hip", "zsw_score_prune.hip", "zsw_score_seed.hip", "zsw_score_seed_m0.hip", "zsw_score_seed_m1.hip", "zsw_score_seed_m2.hip", "zsw_score_band.hip", "zsw_handback_split.hip", "zsw_multi.hip", "zsw_strand.hip", "zsw_panel.hip", "zsw_annotate.hip", "zsw_sam.hip", "zsw_pileup.hip", "zsw_text.hip", "zsw_fastq.hip", "zsw_samtext.hip", "zsw_fasta.hip"]
 HEADERS = ["zsw_internal.hpp", "zsw_align_dev.hpp", "zsw_align_pk.hpp", "zsw_align_pk_kernel.hpp", "zsw_score_v1.hpp", "zsw_score_v2.hpp", "zsw_handback.hpp", "zsw_score_prune.hpp", "zsw_seed.hpp", "zsw_seed_packed.hpp", "zsw_seed_diag.hpp", "zsw_seed_diag_body.inc", "zsw_cert.hpp", "zsw_context.hpp", "zsw_shared.hpp", "zsw_score_seed.hpp", "zsw_score_seed_kernel.hpp", "zsw_align.hpp", "zsw_timer.hpp", "zsw_strand.hpp", "zsw_panel.hpp", "zsw_annotate.hpp", "zsw_sam.hpp", "zsw_pileup.hpp", "zsw_wave.hpp", "zsw_text.hpp", "zsw_text_dev.hpp", "zsw_fastq.hpp", "zsw_samtext.hpp", "zsw_fasta.hpp", "zsw_synth.h", "zsw_exports.map", os.path.join("..", "..", "include", "zoe_sw.h")]
 ARCH = "gfx950"
 # per-file code generation flags. Measured and rejected for zsw_align_pk*.hip: -mllvm -amdgpu-sched-strategy=max-ilp

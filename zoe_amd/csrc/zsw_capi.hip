@@ -161,10 +161,14 @@ static zsw_error common_score_workspace(zsw_context* ctx, const Against& t, cons
     ZSW_HIP(ctx, ctx->d_fb_list.ensure((size_t)n * 4 + 4));
     ZSW_HIP(ctx, ctx->d_fb_count.ensure(4));
     if (reads->offsets || st->max_len > LONGEST_STRIP) ZSW_HIP(ctx, ctx->d_bucket_items.ensure((size_t)n * 4 + 4));
-    if (reads->offsets && !ctx->side) {
+    // (a one-length call large enough for slices of its hand-back list runs them on two of these streams: zsw_handback.hpp)
+    const bool slices = !reads->offsets && !(ctx->flags() & ZSW_DEBUG_SEED_NO_SLICES) && (n >= HANDBACK_SLICE_MIN_CLASS || (ctx->flags() & ZSW_DEBUG_SEED_TINY_SLICES));
+    if ((reads->offsets || slices) && !ctx->side) {
         SideStreams* p = new (std::nothrow) SideStreams();
         if (p) {
-            bool ok = hipEventCreateWithFlags(&p->fork, hipEventDisableTiming) == hipSuccess;
+            bool ok = hipEventCreateWithFlags(&p->fork, hipEventDisableTiming) == hipSuccess &&
+                      hipEventCreateWithFlags(&p->seeded, hipEventDisableTiming) == hipSuccess &&
+                      hipEventCreateWithFlags(&p->shared, hipEventDisableTiming) == hipSuccess;
             for (int i = 0; ok && i < SideStreams::N; ++i)
                 ok = hipStreamCreateWithFlags(&p->s[i], hipStreamNonBlocking) == hipSuccess &&
                      hipEventCreateWithFlags(&p->join[i], hipEventDisableTiming) == hipSuccess;
@@ -1130,6 +1134,8 @@ void zsw_destroy(zsw_context* ctx) {
     ctx->timer_window.destroy();
     if (ctx->side) {
         (void)hipEventDestroy(ctx->side->fork);
+        (void)hipEventDestroy(ctx->side->seeded);
+        (void)hipEventDestroy(ctx->side->shared);
         for (int i = 0; i < SideStreams::N; ++i) {
             (void)hipStreamDestroy(ctx->side->s[i]);
             (void)hipEventDestroy(ctx->side->join[i]);

@@ -124,4 +124,87 @@ constexpr PairRange handback_block_range(uint32_t block, int G, uint32_t count) 
     return lo >= pairs ? PairRange{0u, 0u} : PairRange{(uint32_t)lo, (uint32_t)(hi < pairs ? hi : pairs)};
 }
 
+// ---- slices of the frozen list on side streams (zsw_score_seed.hip: launch_score_seeded; zsw_handback_split.hip) ---------------------
+// The co-scheduled launch runs at the issue roof, and the kernels around it leave the vector units idle: the sort in front of it
+// is memory-bound, the select / second tier / remainder behind it are a few thousand reads on an empty chip. The list is frozen
+// from the seed kernel on, so a bounded slice of it can leave the shared grid and run as a plain launch of score_kernel_v2 on a
+// side stream exactly there: `head` from behind the seed kernel (beside the sort), `tail` from behind the shared launch (beside
+// the second tier). Measured, the head loses — beside it the sort's longest kernel takes 1.28 ms instead of 0.1 — so
+// the default rule cuts no head (HANDBACK_HEAD_READS = 0); the tiny rule of the tests still does, and the code path is one.
+// list[0, n0) = shared | head | tail, in that order; n0 is on the device, so a one-thread kernel behind the seed
+// kernel evaluates handback_slices() there and the launches read their bounds from device words. Host model:
+// tests/models/handback_slices.cpp.
+//
+// Sizes. A resident wavefront of the shared launch's score body holds 32 reads (<4, C>: 16 pairs), a round of it — three
+// wavefronts on each of 1024 SIMDs — 98,304. A slice is all or nothing: a list that cannot give a whole slice AND leave the shared
+// launch a full round keeps today's launches.
+// The tail must not hold up the second tier: per SIMD its resident wavefronts share 512 VGPRs with one wavefront of
+// seed_band_kernel<48,2,0> and one of the remainder launch score_kernel_v2<32,5,0>. From -Rpass-analysis=kernel-resource-usage
+// (allocated in steps of 8): score_kernel_v2<4,38,0> 141 -> 144 (the widest four-lane row), <8,19,0> 96 (the eight-lane row that
+// holds the same reads), seed_band_kernel<48,2,0> 256, score_kernel_v2<32,5,0> 42 -> 48. That leaves 512 - 256 - 48 = 208 for
+// the tail: one wavefront of a four-lane configuration (a second one: 288 + 256 + 48 = 592, and the second tier's blocks would
+// wait for the slice to end), or two of <8,19> (192). Either way 1024 SIMDs hold 32,768 reads of the tail, its hard upper bound.
+// The configuration (HANDBACK_TAIL_G) and the size below the bound are measured: the tail is as long as ONE of its
+// wavefronts takes for its 2,000 rows on a SIMD it shares, 1.35 ms for a wavefront of <4,38> and for two of <8,19> — longer than
+// the 1.0 ms of the kernels it runs beside — and about half for one wavefront of <8,19>. So: eight lanes, one wavefront per SIMD.
+constexpr uint32_t HANDBACK_SIMDS = 1024;                 // 256 CUs x 4
+constexpr uint32_t HANDBACK_VGPRS_PER_SIMD = 512;
+constexpr uint32_t HANDBACK_VGPRS_BAND = 256;             // seed_band_kernel<48,2,0>
+constexpr uint32_t HANDBACK_VGPRS_REMAINDER = 48;         // score_kernel_v2<32,5,0>
+constexpr int HANDBACK_TAIL_G = 8;                        // lanes per pair of the tail's configuration: 4 = the class's own, 8 = its <8, C> row
+constexpr uint32_t HANDBACK_VGPRS_TAIL = HANDBACK_TAIL_G == 4 ? 144 : 96;
+constexpr uint32_t HANDBACK_TAIL_WAVES_PER_SIMD = (HANDBACK_VGPRS_PER_SIMD - HANDBACK_VGPRS_BAND - HANDBACK_VGPRS_REMAINDER) / HANDBACK_VGPRS_TAIL;
+static_assert(HANDBACK_TAIL_G == 4 || HANDBACK_TAIL_G == 8, "the register counts above are those of <4,38> and <8,19>");
+static_assert(HANDBACK_TAIL_WAVES_PER_SIMD >= 1 &&
+                  HANDBACK_TAIL_WAVES_PER_SIMD * HANDBACK_VGPRS_TAIL + HANDBACK_VGPRS_BAND + HANDBACK_VGPRS_REMAINDER <= HANDBACK_VGPRS_PER_SIMD,
+              "the second tier's blocks must find registers beside the tail slice");
+constexpr uint32_t HANDBACK_WAVE_READS = 2 * 64 / 4;      // reads per wavefront of a four-lane configuration
+constexpr uint32_t HANDBACK_TAIL_MAX_READS = HANDBACK_TAIL_WAVES_PER_SIMD * HANDBACK_SIMDS * (2 * 64 / HANDBACK_TAIL_G);  // 32,768
+constexpr uint32_t HANDBACK_TAIL_READS = HANDBACK_SIMDS * (2 * 64 / HANDBACK_TAIL_G);  // 16,384: one wavefront per SIMD
+static_assert(HANDBACK_TAIL_READS <= HANDBACK_TAIL_MAX_READS, "the tail's bound from the register file");
+constexpr uint32_t HANDBACK_HEAD_READS = 0;  // (tried: 32,768, one wavefront of the class's configuration per SIMD)
+constexpr uint32_t HANDBACK_ROUND_READS = 3 * HANDBACK_SIMDS * HANDBACK_WAVE_READS;                            // 98,304
+// Classes below this many reads plan no slice (their launches and launch logs are today's): the list of a smaller class reaches
+// round + slice only if more than 5 % of its reads have no anchor, where the band tiers, not the list, are the long part.
+constexpr uint32_t HANDBACK_SLICE_MIN_CLASS = 1u << 21;
+// ZSW_DEBUG_SEED_TINY_SLICES: slices at any class size, for the tests — a tail of exactly one block (128 reads) in front of
+// which a head of 1 .. 128 reads is cut, and no round kept: lists of 1 .. 127 reads are a head alone, 128 a tail alone, 129 both
+// with nothing left to the shared launch, 130 and more all three parts.
+constexpr uint32_t HANDBACK_TINY_TAIL_READS = 128, HANDBACK_TINY_HEAD_READS = 128, HANDBACK_TINY_HEAD_MIN = 1;
+
+struct ItemRange {
+    uint32_t first, end;
+};
+struct HandbackSlices {
+    ItemRange shared, head, tail;
+};
+// What the host knows of a call: the most reads each slice takes, the fewest it is worth a launch for, and what the shared launch keeps.
+struct HandbackSliceRule {
+    uint32_t keep;                 // the shared launch's part never drops below this because of a slice
+    uint32_t tail_reads, tail_min;
+    uint32_t head_reads, head_min;
+    constexpr bool head() const { return head_reads != 0; }
+    constexpr bool tail() const { return tail_reads != 0; }
+};
+// coscheduled: handback_coschedule(cc) holds for the call; own_stream: it runs on the caller's stream (the one-length route — a
+// length class of a ragged batch is on a side stream already); no_slices / tiny: ZSW_DEBUG_SEED_NO_SLICES / _TINY_SLICES.
+constexpr HandbackSliceRule handback_slice_rule(bool coscheduled, bool own_stream, uint32_t class_reads, bool no_slices, bool tiny) {
+    if (!coscheduled || !own_stream || no_slices) return HandbackSliceRule{0u, 0u, 0u, 0u, 0u};
+    if (tiny) return HandbackSliceRule{0u, HANDBACK_TINY_TAIL_READS, HANDBACK_TINY_TAIL_READS, HANDBACK_TINY_HEAD_READS, HANDBACK_TINY_HEAD_MIN};
+    if (class_reads < HANDBACK_SLICE_MIN_CLASS) return HandbackSliceRule{0u, 0u, 0u, 0u, 0u};
+    return HandbackSliceRule{HANDBACK_ROUND_READS, HANDBACK_TAIL_READS, HANDBACK_TAIL_READS, HANDBACK_HEAD_READS, HANDBACK_HEAD_READS};
+}
+// The three parts of list[0, n0). The tail is cut first (it is worth more: the idle time behind the shared launch is the longer).
+constexpr HandbackSlices handback_slices(uint32_t n0, const HandbackSliceRule& r) {
+    uint32_t avail = n0 > r.keep ? n0 - r.keep : 0u;
+    const uint32_t tail = (r.tail_reads && avail >= r.tail_min) ? (avail < r.tail_reads ? avail : r.tail_reads) : 0u;
+    avail -= tail;
+    const uint32_t head = (r.head_reads && avail >= r.head_min) ? (avail < r.head_reads ? avail : r.head_reads) : 0u;
+    const uint32_t s = n0 - tail - head;
+    return HandbackSlices{{0u, s}, {s, s + head}, {s + head, n0}};
+}
+// The device words a launch reads its range from: bounds[0] = shared.end = head.first, bounds[1] = head.end = tail.first; tail.end
+// is n0 itself. (ScoreArgsV2: n_items_dev -> a range's end, first_item_dev -> its first.)
+constexpr int HANDBACK_BOUND_WORDS = 2;
+
 }  // namespace zsw

@@ -85,10 +85,13 @@ struct ScoreOut {
 struct KernelTimer;
 
 // Side streams on which the length classes of a ragged batch run concurrently (forked from / joined to the caller's stream).
+// A one-length call runs the slices of its hand-back list on s[0] and s[1] (zsw_handback.hpp: handback_slices), forked at
+// `seeded` / `shared` and joined through join[0] / join[1].
 struct SideStreams {
     static constexpr int N = 8;
     hipStream_t s[N];
     hipEvent_t fork, join[N];
+    hipEvent_t seeded, shared;
 };
 
 // launchers (zsw_score.hip)

@@ -262,6 +262,9 @@ static hipError_t launch_table_cfg_v2(const ScoreArgsV2& a, int G, int C, int mo
     return hipErrorInvalidValue;
 }
 
+// (zsw_score_seed.hpp: the slices of the hand-back list are launched from zsw_score_seed.hip)
+hipError_t launch_score_v2_cfg(const ScoreArgsV2& a, int G, int C, int mode, hipStream_t stream) { return launch_table_cfg_v2(a, G, C, mode, stream); }
+
 // v2 needs: S <= 7; for query residues 0..3: s + ge in [-128, 127]; for residues >= 4: s + ge in [0, 255].
 static bool v2_ok(const ScoringDev& s, uint32_t debug) {
     if (debug & ZSW_DEBUG_SCORE_V1) return false;
@@ -685,9 +688,11 @@ static hipError_t score_handed_back_gated(const ScoreCall& c, const ScoreArgsV2&
 // Seeded exact pass (zsw_score_seed.hip) over the items of `bb` in strip configuration (g, cc): seed + sort + band or window kernel,
 // then score_kernel_v2 over the reads it hands back (device-side list; `counter` = its count, zeroed here). The workspace region
 // [work_off, work_off + seed_workspace_bytes(n_items)) and fail_list + list_off belong to this call alone.
+// slice_streams: non-null = `stream` is the caller's own (the one-length route) and slices of the co-scheduled hand-back list may
+// run on slice_streams->s[0] (head) and s[1] (tail), forked from and joined to `stream` here (zsw_handback.hpp: handback_slices).
 // hipErrorNotSupported: not switched on, or the batch does not qualify.
 static hipError_t seed_items(ScoreDispatch& d, const BatchDev& bb, int g, int cc, uint32_t longest, size_t work_off, uint32_t list_off, uint32_t* counter,
-                             uint32_t band_grid_cap, hipStream_t stream) {
+                             uint32_t band_grid_cap, const SideStreams* slice_streams, hipStream_t stream) {
     const ScoreCall& c = d.call;
     const ScoreWorkspace& ws = c.ws;
     if (!c.use_v2 || !ws.seed || !ws.seed_work || !ws.prune_fail_list || !(ws.debug & ZSW_DEBUG_SCORE_PRUNE) || (ws.debug & ZSW_DEBUG_PRUNE_STRIP))
@@ -709,10 +714,38 @@ static hipError_t seed_items(ScoreDispatch& d, const BatchDev& bb, int g, int cc
     ap.b = bb;
     const RowChunks rc = row_chunks_for(c, longest);
     static_assert(2 + NCLS <= 32, "the n0 words sit 32 behind their counters");
-    // (ws.prune_fail_count: 64 words, the counters in the first 2 + NCLS, the n0 word of each 32 behind it)
+    static_assert(2 + NCLS <= 32 - HANDBACK_BOUND_WORDS, "the slice bounds take the last words behind the n0 words");
+    // (ws.prune_fail_count: 64 words, the counters in the first 2 + NCLS, the n0 word of each 32 behind it, the slice bounds of the
+    // one-length route — whose counter is word 0 — in the last HANDBACK_BOUND_WORDS)
     const SeedRegion region = {ws.seed_work + work_off, work_bytes, ws.prune_fail_list + list_off, counter, counter + 32};
+    // Slices of the co-scheduled list: the rule as if the decision held (launch_score_seeded applies it only then). The tail runs in
+    // the class's own configuration with its tables (zsw_handback.hpp: the register budget).
+    HandbackSliceLaunch sl{};
+    sl.rule = handback_slice_rule(true, slice_streams != nullptr && counter == ws.prune_fail_count, bb.n_items, (ws.debug & ZSW_DEBUG_SEED_NO_SLICES) != 0,
+                                  (ws.debug & ZSW_DEBUG_SEED_TINY_SLICES) != 0);
+    const bool slices = sl.rule.head() || sl.rule.tail();
+    ScoreArgsV2 tail_tabs = c.v2;
+    if (slices) {
+        sl.bounds = ws.prune_fail_count + 64 - HANDBACK_BOUND_WORDS;
+        sl.head = slice_streams->s[0];
+        sl.tail = slice_streams->s[1];
+        sl.seeded = slice_streams->seeded;
+        sl.shared = slice_streams->shared;
+        sl.tail_tabs = &ap;
+        sl.tail_G = g;
+        sl.tail_C = cc;
+        // HANDBACK_TAIL_G lanes per pair, if that is not the class's own: the narrowest such row that holds the reads, with its
+        // tables (as score_handed_back_gated builds them); none, or no tables: the class's configuration
+        for (int k = 0; k < N_ASCENDING_CFGS && HANDBACK_TAIL_G != g && sl.tail_G == g; ++k) {
+            if (kCfgs[k].G != HANDBACK_TAIL_G || (uint32_t)(kCfgs[k].G * kCfgs[k].C) < longest || !build_tables_v2(c.h_sc, kCfgs[k].G, &tail_tabs)) continue;
+            tail_tabs.b = bb;
+            sl.tail_tabs = &tail_tabs;
+            sl.tail_G = kCfgs[k].G;
+            sl.tail_C = kCfgs[k].C;
+        }
+    }
     bool coscheduled = false;
-    pe = launch_score_seeded(ap, g, cc, longest, ws, region, c.mode, band, band_grid_cap, rc.enabled, &coscheduled, stream);
+    pe = launch_score_seeded(ap, g, cc, longest, ws, region, c.mode, band, band_grid_cap, rc.enabled, &coscheduled, slices ? &sl : nullptr, stream);
     if (pe != hipSuccess) return pe;
     // out.skip_handed_back (the shared-profile role's passes, the seeded reverse pass of the ranges): the caller recomputes every
     // read without the `unique` flag by other means, the handed-back reads among them — scoring them here would be thrown away
@@ -722,6 +755,16 @@ static hipError_t seed_items(ScoreDispatch& d, const BatchDev& bb, int g, int cc
     ap.first_item_dev = coscheduled ? region.n0 : nullptr;  // (not co-scheduled: n0 is not written, and nothing changes)
     pe = rc.enabled ? score_handed_back_chunked(c, ap, rc, g, cc, bb.n_items, stream) : score_handed_back_gated(c, ap, g, cc, longest, bb.n_items, stream);
     if (pe != hipSuccess) return pe;
+    // the slices join here, behind the caller's own launches (which they ran beside) and in front of everything that reads what a
+    // slice wrote: its results, and the saturation worklist it may have appended to (finish_worklist)
+    if (coscheduled && slices) {
+        for (int i = 0; i < 2; ++i) {
+            if (!(i == 0 ? sl.rule.head() : sl.rule.tail())) continue;
+            pe = hipEventRecord(slice_streams->join[i], slice_streams->s[i]);
+            if (pe == hipSuccess) pe = hipStreamWaitEvent(stream, slice_streams->join[i], 0);
+            if (pe != hipSuccess) return pe;
+        }
+    }
     // zsw_prune_rescored counts the reads scored over all their cells HERE: a pass whose handed-back reads the caller settles by
     // other means (the reversed pass of the ranges, the shared role's ends) adds nothing
     hipLaunchKernelGGL(add_count_kernel, dim3(1), dim3(1), 0, stream, counter, ws.prune_fail_count + 1);
@@ -848,7 +891,7 @@ static hipError_t score_ragged(ScoreDispatch& d, hipStream_t stream, KernelTimer
             const Cfg& cf = kCfgs[kBucketCfg[k]];
             const uint32_t grid_cap = seed_band_class_cap(counts[k], n_seedable);
             e = seed_items(d, class_items(c, starts[k], counts[k]), cf.G, cf.C, caps.cap[k], work_off, starts[k], ws.prune_fail_count + 2 + k, grid_cap,
-                           fork ? side->s[used % SideStreams::N] : stream);
+                           nullptr, fork ? side->s[used % SideStreams::N] : stream);
             if (e == hipSuccess) {
                 ++used;
                 work_off += seed_workspace_bytes(counts[k], caps.cap[k], grid_cap);
@@ -948,7 +991,7 @@ static hipError_t launch_score_passes(const ScoringDev* d_sc, const ScoringDev& 
         if (timer) timer->begin(stream);
         e = hipErrorNotSupported;
         int Gs = 0, Cs = 0;
-        if (score_config_for(max_len, &Gs, &Cs)) e = seed_items(d, b, Gs, Cs, max_len, 0, 0, ws.prune_fail_count, SEED_BAND_MAX_GRID, stream);
+        if (score_config_for(max_len, &Gs, &Cs)) e = seed_items(d, b, Gs, Cs, max_len, 0, 0, ws.prune_fail_count, SEED_BAND_MAX_GRID, ws.side, stream);
         const int cls = prune_class_for(max_len);
         if (e == hipErrorNotSupported && cls >= 0) e = prune_items(c, b, cls, b.n_items, stream);
         if (e == hipErrorNotSupported) e = launch_one(c, b, G, C, stream);

@@ -308,8 +308,26 @@ bool seed_applicable(const SeedIndex& ix, uint32_t max_len, uint32_t ref_len, ui
     return (uint64_t)ix.params.maxw * max_len + 8 < limit;  // no score can leave the packed range
 }
 
+// A slice of the frozen hand-back list: a plain launch of score_kernel_v2 in configuration G x C of `a` over list[*first, *end) —
+// at most `most` reads — on `side`, once `after`, recorded here on `from`, has happened.
+static hipError_t launch_handback_slice(ScoreArgsV2 a, int G, int C, const uint32_t* list, const uint32_t* first, const uint32_t* end, uint32_t most,
+                                        hipEvent_t after, hipStream_t from, hipStream_t side, std::vector<uint32_t>* launch_log) {
+    hipError_t e = hipEventRecord(after, from);
+    if (e == hipSuccess) e = hipStreamWaitEvent(side, after, 0);
+    if (e != hipSuccess) return e;
+    a.b.items = list;
+    a.b.n_items = most;
+    a.n_items_dev = end;
+    a.first_item_dev = first;
+    a.gate_lo = 0;
+    a.gate_hi = 0xffffffffu;
+    note_launch(launch_log, ZSW_LAUNCH_V2, G, C, 0);
+    return launch_score_v2_cfg(a, G, C, 0, side);
+}
+
 hipError_t launch_score_seeded(const ScoreArgsV2& a2, int G, int C, uint32_t max_len, const ScoreWorkspace& ws, const SeedRegion& r, int mode,
-                               const ScoreArgsV2* band_tabs, uint32_t band_grid_cap, bool row_chunks, bool* coscheduled, hipStream_t stream) {
+                               const ScoreArgsV2* band_tabs, uint32_t band_grid_cap, bool row_chunks, bool* coscheduled, const HandbackSliceLaunch* slices,
+                               hipStream_t stream) {
     const uint32_t n = a2.b.n_items;
     const SeedIndex& ix = *ws.seed;
     // ZSW_OPTION_MIN_SCORE: min_threshold(), 0 = off (also where the caller settles the handed-back reads itself)
@@ -320,6 +338,19 @@ hipError_t launch_score_seeded(const ScoreArgsV2& a2, int G, int C, uint32_t max
     if (!r.work || !ws.seed_gtab || r.work_bytes < seed_workspace_bytes(n, max_len, band_grid_cap)) return hipErrorNotSupported;
     // the banded kernel (zsw_score_band.hip) when a strip's rows fit one drift period of the doubled scoring
     const bool band = band_tabs != nullptr && seed_band_applicable(ix.params, max_len, band_tabs->K, band_tabs->limit);
+    // score-only calls of at least this many short reads walk a narrow band first (SEED_NARROW_*)
+    const uint32_t narrow_min_reads = (ws.debug & ZSW_DEBUG_SEED_WIDE_BAND) ? 0xffffffffu : (ws.debug & ZSW_DEBUG_SCORE_PRUNE_ANY_SIZE) ? 0u : SEED_NARROW_MIN_READS;
+    const bool two_tiers = band && max_len <= SEED_NARROW_MAX_LEN && n >= narrow_min_reads;
+    // score only, as the first of two tiers: the band diagonal by diagonal (seed_diag_kernel) instead of 16-column strips
+    const bool diagonal = two_tiers && mode == 0 && !a2.out.narrow_only && !(ws.debug & ZSW_DEBUG_SEED_STRIP_FIRST_TIER) && seed_diag_applicable(max_len, band_tabs->K);
+    // The full pass over the reads the seed kernel hands back may run inside the first tier's launch (zsw_handback.hpp:
+    // handback_coschedule); n0, one word per counter (the length classes of a ragged batch have their own), then holds how
+    // many reads of the list that launch and its slices scored, and the caller's launches score the rest.
+    const CoscheduleCase cc{mode, two_tiers && !a2.out.narrow_only, diagonal, G, min_thr != 0, row_chunks, a2.out.skip_handed_back,
+                            (ws.debug & ZSW_DEBUG_SEED_NO_COSCHEDULE) != 0};  // (the fields in the struct's order)
+    const bool cosched = handback_coschedule(cc);
+    const HandbackSliceRule slice_rule = cosched && slices ? slices->rule : HandbackSliceRule{0u, 0u, 0u, 0u, 0u};
+    const bool sliced = slice_rule.head() || slice_rule.tail();
     const size_t per = round256((size_t)n * 4 + 8);
     uint32_t* keys = reinterpret_cast<uint32_t*>(r.work);
     uint32_t* keys_out = reinterpret_cast<uint32_t*>(r.work + per);
@@ -379,7 +410,20 @@ hipError_t launch_score_seeded(const ScoreArgsV2& a2, int G, int C, uint32_t max
         hipLaunchKernelGGL((seed_kernel<true, false>), dim3((n + 255) / 256), dim3(256), 0, stream, s);
     else
         hipLaunchKernelGGL((seed_kernel<false, false>), dim3((n + 255) / 256), dim3(256), 0, stream, s);
-    hipError_t e = hipcub::DeviceRadixSort::SortPairs(temp, temp_bytes, (const uint32_t*)keys, keys_out, (const uint32_t*)ids, order, (int)n, 0,
+    hipError_t e = hipSuccess;
+    if (cosched) {
+        // Invariant: the first tier has b1.retry != nullptr and no bail-out (b1.bail_check is false), so it appends nothing to
+        // fail_list: from here to the second tier the list and *fail_count are frozen. *n0 — written here, on the stream, behind the
+        // seed kernel — is the count the co-scheduled launch and its slices cover together, each its own part (bounds), and what
+        // the second tier appends behind it is the caller's (first_item_dev = n0).
+        e = launch_handback_split(r.fail_count, r.n0, sliced ? slices->bounds : nullptr, slice_rule, stream);
+        // the head slice: beside the sort, whose kernels leave the vector units idle
+        if (e == hipSuccess && slice_rule.head())
+            e = launch_handback_slice(a2, G, C, r.fail_list, slices->bounds, slices->bounds + 1, slice_rule.head_reads, slices->seeded, stream, slices->head,
+                                      ws.launch_log);
+        if (e != hipSuccess) return e;
+    }
+    e = hipcub::DeviceRadixSort::SortPairs(temp, temp_bytes, (const uint32_t*)keys, keys_out, (const uint32_t*)ids, order, (int)n, 0,
                                                       key_bits, stream);
     if (e != hipSuccess) return e;
 
@@ -428,9 +472,7 @@ hipError_t launch_score_seeded(const ScoreArgsV2& a2, int G, int C, uint32_t max
         uint32_t* accepted = queue2 + 1;
         b.next_pair = queue2;
         if (ws.window_timer) ws.window_timer->begin(stream);
-        // score-only calls of at least this many short reads walk a narrow band first (SEED_NARROW_*)
-        const uint32_t narrow_min_reads = (ws.debug & ZSW_DEBUG_SEED_WIDE_BAND) ? 0xffffffffu : (ws.debug & ZSW_DEBUG_SCORE_PRUNE_ANY_SIZE) ? 0u : SEED_NARROW_MIN_READS;
-        if (max_len <= SEED_NARROW_MAX_LEN && n >= narrow_min_reads) {
+        if (two_tiers) {
             // two tiers: every read in a narrow band; the reads whose bounds fail there, still in anchor order, in the full band.
             // The sort's input values and output keys are free by now: flags and the second tier's order.
             uint8_t* retry = reinterpret_cast<uint8_t*>(ids);
@@ -449,26 +491,19 @@ hipError_t launch_score_seeded(const ScoreArgsV2& a2, int G, int C, uint32_t max
             b1.diag_lane_events = (ws.debug & ZSW_DEBUG_SEED_DIAG_LANE_EVENTS) != 0;
             b1.diag_masked = (ws.debug & ZSW_DEBUG_SEED_DIAG_MASKED) != 0;
             note_launch(ws.launch_log, ZSW_LAUNCH_SEED_BAND, G, C, mode);
-            // score only, as the first of two tiers: the band diagonal by diagonal (seed_diag_kernel) instead of 16-column strips
-            const bool diagonal = mode == 0 && !a2.out.narrow_only && !(ws.debug & ZSW_DEBUG_SEED_STRIP_FIRST_TIER) && seed_diag_applicable(max_len, band_tabs->K);
-            // The full pass over the reads the seed kernel hands back may run inside this launch (zsw_handback.hpp:
-            // handback_coschedule); n0, one word per counter (the length classes of a ragged batch have their own), then holds how
-            // many reads of the list that launch scored, and the caller's launches score the rest.
-            const CoscheduleCase cc{mode, !a2.out.narrow_only, diagonal, G, min_thr != 0, row_chunks, a2.out.skip_handed_back,
-                                    (ws.debug & ZSW_DEBUG_SEED_NO_COSCHEDULE) != 0};  // (the fields in the struct's order)
-            if (handback_coschedule(cc)) {
-                // The full pass over the reads the seed kernel listed, in the first tier's grid. Invariant: b1.retry != nullptr and
-                // no bail-out (b1.bail_check is false), so the tier appends nothing to fail_list: the list and *fail_count are
-                // frozen for the whole launch, and *n0 — copied here, on the stream, behind the seed kernel — is the count every
-                // block of the launch reads. What the second tier appends behind it is the caller's (first_item_dev = n0).
-                e = hipMemcpyAsync(r.n0, r.fail_count, 4, hipMemcpyDeviceToDevice, stream);
-                if (e != hipSuccess) return e;
+            if (cosched) {
+                // The full pass over the reads the seed kernel listed, in the first tier's grid (the invariant: above, at the split
+                // kernel): every block of the launch reads the same count — the whole frozen list, or its shared part.
                 ScoreArgsV2 hb = a2;
                 hb.b.items = r.fail_list;
-                hb.n_items_dev = r.fail_count;
+                hb.n_items_dev = sliced ? slices->bounds : r.fail_count;
                 note_launch(ws.launch_log, ZSW_LAUNCH_V2, G, C, 0);
                 e = launch_seed_diag_handback(b1, hb, G, C, stream);
                 *coscheduled = true;
+                // the tail slice: beside the select, the second tier and the remainder launch, a few thousand reads on an empty chip
+                if (e == hipSuccess && slice_rule.tail())
+                    e = launch_handback_slice(*slices->tail_tabs, slices->tail_G, slices->tail_C, r.fail_list, slices->bounds + 1, r.n0, slice_rule.tail_reads,
+                                              slices->shared, stream, slices->tail, ws.launch_log);
             } else {
                 e = launch_seed_band(b1, mode, true, stream, diagonal);
             }

@@ -152,6 +152,18 @@ struct SeedRegion {
     uint32_t* fail_count;  // ... and the list's count (not reset by launch_score_seeded)
     uint32_t* n0;          // the device word for the co-scheduled part of the list (below)
 };
+// The slices of the co-scheduled list (zsw_handback.hpp: handback_slices) as launch_score_seeded launches them. The head runs on
+// `head` once `seeded` — recorded behind the seed kernel and the split kernel — has happened, in the class's configuration; the
+// tail on `tail` once `shared`, recorded behind the first tier's launch, has happened, in configuration tail_G x tail_C of
+// tail_tabs. Streams and events are the context's; no stream is stored anywhere else.
+struct HandbackSliceLaunch {
+    HandbackSliceRule rule;
+    uint32_t* bounds;  // HANDBACK_BOUND_WORDS device words of this call alone
+    hipStream_t head, tail;
+    hipEvent_t seeded, shared;
+    const ScoreArgsV2* tail_tabs;
+    int tail_G, tail_C;
+};
 // Seeds, sorts and runs the banded kernel — or the window kernel, in strip configuration G x C of a2's tables — over the items of
 // a2.b; reads without an anchor and reads whose bounds fail are appended to r.fail_list. Index, per-row tables, debug bits (decoded
 // where each is used), band records, window timer, launch log and minimum-score counters are the workspace's; a2.out says whether
@@ -160,8 +172,16 @@ struct SeedRegion {
 // row_chunks: the caller cuts the hand-backs into chunks of rows, the one fact of handback_coschedule only it knows. If that decision
 // holds, *r.fail_count as the seed kernel left it is copied to *r.n0 and the first tier's launch scores fail_list[0, *n0) itself,
 // with a2's tables: the caller's launches start at *n0 (ScoreArgsV2::first_item_dev). *coscheduled: whether that happened.
+// slices (null: none): then, and only then, the parts of list[0, *n0) that slices->rule cuts off run as launches of their own on
+// the slice streams, and the caller joins those streams before it reads what they wrote.
 hipError_t launch_score_seeded(const ScoreArgsV2& a2, int G, int C, uint32_t max_len, const ScoreWorkspace& ws, const SeedRegion& r, int mode,
-                               const ScoreArgsV2* band_tabs, uint32_t band_grid_cap, bool row_chunks, bool* coscheduled, hipStream_t stream);
+                               const ScoreArgsV2* band_tabs, uint32_t band_grid_cap, bool row_chunks, bool* coscheduled, const HandbackSliceLaunch* slices,
+                               hipStream_t stream);
+// zsw_handback_split.hip, one thread behind the seed kernel: *n0 = *count, and (bounds != null) bounds[0 .. HANDBACK_BOUND_WORDS) =
+// the bounds of handback_slices(*count, rule)
+hipError_t launch_handback_split(const uint32_t* count, uint32_t* n0, uint32_t* bounds, const HandbackSliceRule& rule, hipStream_t stream);
+// zsw_score.hip: a plain launch of score_kernel_v2<G, C, mode> (hipErrorInvalidValue: no such row of the configuration list)
+hipError_t launch_score_v2_cfg(const ScoreArgsV2& a, int G, int C, int mode, hipStream_t stream);
 // (Re)builds the index for a reference given as residue indices on the host.
 hipError_t seed_index_update(SeedIndex* ix, const ScoringDev& sc, const uint8_t* h_ref, size_t ref_len);
 void seed_index_release(SeedIndex* ix);
